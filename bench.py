@@ -3,11 +3,15 @@
 (decoder forward + flow NLL + backward; no optimizer, no data loading) on synthetic
 fixed-length batches, B=32 per GPU, 80 mel, T=800 (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
 One process per GPU; N > 1 adds the bucketed RCCL gradient all-reduce overlapped with
-backward (rad_mmm_amd/ddp.py).  Rank 0 prints ONE JSON line.  Extra objects:
+backward (rad_mmm_amd/ddp.py).  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and
+prints the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = wall time of the timed
+steps / K) with the run's configuration and loss.  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (dump_outputs).  --full adds every other measurement and check (N > 1: also the RCCL world check and
+the per-bucket all-reduce timings, the in-step launch timing and the saturation report).  Extra objects of --full:
   roofline     dominant kernel (dilated k=5 1024->1024 conv GEMM on the split-operand path: f16 hi.hi product + FP8
                cross terms by default) timed live with HIP events on the launch stream: algorithmic FLOP per launch /
                avg duration against the dense f16 MFMA peak; traffic from profiles/pmc_dominant.json (static)
@@ -15,7 +19,9 @@ backward (rad_mmm_amd/ddp.py).  Rank 0 prints ONE JSON line.  Extra objects:
   wn_stack     the north_star's derived view: algorithmic fp32 bytes of the WN stack / step time
   cpu_baseline the CPU oracle (a port of the reference's arithmetic) timed on the host cores
                on a bounded sample of the same workload (rank 0, N=1 only)
-Other workloads beside the headline line: --full-step (the whole training step of the reference's loop), --config joint
+  roofline_hbm / roofline_mfma / process_group_overhead_ms / saturation   static per-kernel figures quoted from the
+               committed traces, and the split producers' saturation counters
+Other workloads beside the headline line (with or without --full): --full-step (the whole training step of the reference's loop), --config joint
 (BASELINE configs[3]: RADMMM decoder + the four attribute predictors in ONE step, with its own parity block against the CPU
 oracle's restatement of TTSModel.training_step), --config radmmm / radmmm_splines (configs[2] / configs[4]).
 """
@@ -207,6 +213,62 @@ def host_threads() -> int:
     except Exception:
         pass
     return max(1, min(n, 32))
+
+
+DUMP_BUDGET_BYTES = 56_000_000      # --dump-outputs writes less than 64 MB in all
+DUMP_GRAD_SAMPLE = 4096             # gradient entries kept per parameter
+DUMP_SEED = 20240                   # fixes every sampled position
+
+
+def _detached(out):
+    """the decoder's output dict without its autograd graph (kept from one timed step to the next by --dump-outputs)"""
+    return {k: (v.detach() if torch.is_tensor(v) else [t.detach() if torch.is_tensor(t) else t for t in v]
+                if isinstance(v, (list, tuple)) else v) for k, v in out.items()}
+
+
+def dump_outputs(path, out, losses, module):
+    """--dump-outputs: what the timed step computed in its last step, as path/<name>.npy: the decoder's outputs (z_mel,
+    log_s_<flow>, log_det_W, context_w_spkvec), every loss term (float64) and the parameter gradients the backward left
+    (grad_norms: float64 norm of each in named_parameters order; grad_sample: DUMP_GRAD_SAMPLE entries of each at seeded
+    positions).  If the whole would pass DUMP_BUDGET_BYTES, the largest arrays keep a seeded sample of their elements
+    (flattened) so that the total fits: the positions depend only on the shapes, so two builds compare element for element.
+    -> {name: shape written}"""
+    arrays = {"z_mel": out["z_mel"].float().cpu().numpy()}
+    for i, ls in enumerate(out["log_s_list"]):
+        arrays[f"log_s_{i}"] = ls.float().cpu().numpy()
+    arrays["log_det_W"] = np.array([float(t) if torch.is_tensor(t) else np.nan for t in out["log_det_W_list"]], np.float64)
+    if torch.is_tensor(out.get("context_w_spkvec")):
+        arrays["context_w_spkvec"] = out["context_w_spkvec"].float().cpu().numpy()
+    for name, (val, _) in losses.items():
+        if torch.is_tensor(val) or isinstance(val, float):
+            arrays[name.replace("/", "_")] = np.array([float(val)], np.float64)
+    norms, picks = [], []
+    for i, (_, p) in enumerate(module.named_parameters()):
+        g = p.grad
+        if g is None:
+            norms.append(np.nan)
+            continue
+        g = g.detach().reshape(-1)
+        norms.append(float(torch.linalg.vector_norm(g.double())))
+        n = min(g.numel(), DUMP_GRAD_SAMPLE)
+        idx = np.sort(np.random.default_rng([DUMP_SEED, i]).choice(g.numel(), n, replace=False))
+        picks.append(g[torch.from_numpy(idx).to(g.device)].float())
+    arrays["grad_norms"] = np.array(norms, np.float64)
+    arrays["grad_sample"] = torch.cat(picks).cpu().numpy() if picks else np.zeros(0, np.float32)
+    # fit the budget: arrays in ascending size each take at most an even share of what is left
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES:
+        left, names = DUMP_BUDGET_BYTES, sorted(arrays, key=lambda k: (arrays[k].nbytes, k))
+        for j, k in enumerate(names):
+            a, share = arrays[k], left // (len(names) - j)
+            if a.nbytes > share:
+                n = max(1, share // a.itemsize)
+                idx = np.sort(np.random.default_rng([DUMP_SEED, a.size]).choice(a.size, n, replace=False))
+                arrays[k] = a = a.reshape(-1)[idx]
+            left -= a.nbytes
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def _latest_trace(suffix):
@@ -690,6 +752,13 @@ def main():
                     help="launch only the roofline leg's kernel (the PMC passes of tools/pmc_dominant.sh wrap this)")
     ap.add_argument("--joint-parity-utts", type=int, default=4,
                     help="--config joint: utterances of the bench batch the CPU oracle runs the whole joint step on")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement and check: the dominant kernel's roofline, the "
+                         "exact-split / throughput legs, the CPU baseline with its parity figures, the saturation report, the "
+                         "static per-kernel rooflines (N > 1: the RCCL world check and per-bucket all-reduce timings)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (decoder outputs, loss terms, gradient "
+                         "norms and a seeded sample of the gradients) as DIR/<name>.npy, under 64 MB in all (rank 0)")
     args = ap.parse_args()
     if args.config == "joint":
         args.full_step = True
@@ -785,11 +854,15 @@ def main():
 
     from rad_mmm_amd.ddp import reduce_loss_dict
     glob = {"handle": None}                   # the last step's coalesced loss-term reduce
+    last = {}                                 # --dump-outputs: the latest step's outputs, without their graph
 
     def step():
         reducer.prepare()
         out = dec(gb["mel"], gb["spk"], gb["context"], sl, gb["f0"], gb["energy"], gb["accent"])
         losses = crit(out, None, sl, 0)
+        if args.dump_outputs:
+            last["out"] = _detached(out)
+            last["losses"] = {k: ((v[0].detach() if torch.is_tensor(v[0]) else v[0]), v[1]) for k, v in losses.items()}
         loss = losses["loss_mel"][0]
         if use_dist:
             # what the reference's loop does with `self.log(..., sync_dist=True)` per term and step
@@ -830,6 +903,9 @@ def main():
         dt = float(tt)
     ms_per_step = dt / args.steps * 1e3
     frames_per_s = world * B * T * args.steps / dt
+    if args.dump_outputs and rank == 0:       # before any leg that runs more steps
+        dump_outputs(args.dump_outputs, last["out"], last["losses"], dec)
+        last.clear()
     loss_val = float(loss.detach())
     # the mean over ranks of the last timed step's loss terms (rank 0 alone would print its own utterances' NLL)
     loss_global = ({k: float(v) for k, v in glob["handle"].wait().items()} if glob["handle"] is not None else None)
@@ -841,8 +917,6 @@ def main():
                  "gemm_cu_budget": os.environ.get("RADMMM_GEMM_CUS"),
                  "nccl_env": {k: v for k, v in os.environ.items() if k.startswith(("NCCL_", "RCCL_"))}}
     if use_dist:
-        ones = torch.ones(1, device=dev)
-        dist.all_reduce(ones)
         per_step = []
         per_bucket = None
         for ev in comm_ev:
@@ -853,36 +927,40 @@ def main():
         exp_ms = float(np.median(per_step)) if per_step else None
         worst = torch.tensor([exp_ms or 0.0], device=dev, dtype=torch.float64)
         dist.all_reduce(worst, op=dist.ReduceOp.MAX)
-        dist_info.update(rccl_world_size=dist.get_world_size(), rccl_allreduce_of_ones=float(ones),
+        dist_info.update(rccl_world_size=dist.get_world_size(),
                          reduce_op="avg" if reducer._avg else "sum + scale",
                          exposed_comm_ms_median_rank0=exp_ms, exposed_comm_ms_median_slowest_rank=float(worst),
                          exposed_comm_ms_per_bucket_mean_rank0=([x / len(per_step) for x in per_bucket] if per_bucket else None),
                          bucket_order=[reducer.buckets[i]["key"] for i in reducer._order],
                          bucket_mbytes=[round(reducer.buckets[i]["flat"].numel() * 4 / 1e6, 1) for i in reducer._order])
-        # what the pinned channels deliver: every bucket all-reduced on its own (nothing else running), three times each
-        # -- algorithm bandwidth = bytes / time, bus bandwidth = 2 (n - 1) / n of that (the ring's per-link load)
-        bw = []
-        scratch = {}
-        for i in reducer._order:
-            flat = reducer.buckets[i]["flat"]
-            buf = scratch.setdefault(flat.numel(), torch.empty_like(flat))
-            buf.copy_(flat)
-            dist.all_reduce(buf)
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(3):
+        if args.full:
+            ones = torch.ones(1, device=dev)
+            dist.all_reduce(ones)
+            # what the pinned channels deliver: every bucket all-reduced on its own (nothing else running), three times each
+            # -- algorithm bandwidth = bytes / time, bus bandwidth = 2 (n - 1) / n of that (the ring's per-link load)
+            bw = []
+            scratch = {}
+            for i in reducer._order:
+                flat = reducer.buckets[i]["flat"]
+                buf = scratch.setdefault(flat.numel(), torch.empty_like(flat))
+                buf.copy_(flat)
                 dist.all_reduce(buf)
-            e1.record()
-            torch.cuda.synchronize()
-            t = torch.tensor([e0.elapsed_time(e1) / 3.0], device=dev, dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            gbs = flat.numel() * 4 / (float(t) * 1e-3) / 1e9
-            bw.append({"bucket": reducer.buckets[i]["key"], "ms": round(float(t), 3), "algbw_gbs": round(gbs, 1),
-                       "busbw_gbs": round(gbs * 2 * (world - 1) / max(world, 1), 1)})
-        del scratch
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(3):
+                    dist.all_reduce(buf)
+                e1.record()
+                torch.cuda.synchronize()
+                t = torch.tensor([e0.elapsed_time(e1) / 3.0], device=dev, dtype=torch.float64)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                gbs = flat.numel() * 4 / (float(t) * 1e-3) / 1e9
+                bw.append({"bucket": reducer.buckets[i]["key"], "ms": round(float(t), 3), "algbw_gbs": round(gbs, 1),
+                           "busbw_gbs": round(gbs * 2 * (world - 1) / max(world, 1), 1)})
+            del scratch
+            dist_info.update(rccl_allreduce_of_ones=float(ones), allreduce_alone_per_bucket=bw)
         exposed_share = float(worst) / median_ms if median_ms else 0.0
-        dist_info.update(allreduce_alone_per_bucket=bw, exposed_comm_share_of_step=exposed_share)
+        dist_info.update(exposed_comm_share_of_step=exposed_share)
         if world > 1 and exposed_share > 0.05:
             note = (f"exposed gradient communication is {100 * exposed_share:.1f} % of the step (> 5 %): the "
                     f"{os.environ.get('NCCL_MAX_NCHANNELS', 'default')} RCCL channels this run is pinned to (rad_mmm_amd/ddp.py "
@@ -902,7 +980,7 @@ def main():
     # the dominant kernel's launches INSIDE the training step, each bracketed by HIP events on its stream, over three more
     # steps -- on EVERY rank (a step issues the gradient all-reduces: rank 0 must not run one alone); rank 0 reports its own
     in_step = []
-    if dec.gemm_precision in ("h3", "f8x"):
+    if args.full and dec.gemm_precision in ("h3", "f8x"):
         from rad_mmm_amd import _lib as L
         Nrows = B * (T // cfg.n_group_size)
         L.LAUNCH_EVENTS.clear()
@@ -926,50 +1004,80 @@ def main():
             pass
         return {"saturated_passes": gs.saturated_passes, "x8_saturated_passes": gs.x8_saturated_passes,
                 "x8_adaptations": gs.x8_adaptations, "x8_grad_exp": gs.x8_grad_exp, "nonfinite_passes": gs.nonfinite_passes}
-    sat_report = saturation_report() if use_dist else None      # (one GPU: taken at the end, after the side legs)
+    sat_report = saturation_report() if use_dist and args.full else None      # (one GPU: taken at the end, after the side legs)
     if rank == 0:
         N = B * (T // cfg.n_group_size)
         h3 = dec.gemm_precision in ("h3", "f8x")
         f8x = dec.gemm_precision == "f8x"
+        # split-f16 path: every fp32 product is three f16 MFMA products (Ah*Bh + Ah*Bl + Al*Bh) on the f16 matrix cores
+        # (f8x: 1 f16 + 2 FP8 products at twice the rate); executed MFMA work in f16-equivalent products
         if h3:
-            # split-f16 path: every fp32 product is three f16 MFMA products (Ah*Bh + Ah*Bl + Al*Bh) on the f16 matrix
-            # cores.  `achieved` counts the ALGORITHMIC flops of the launch (2*M*N*K*taps) against the dense
-            # f16 MFMA peak the kernel runs on; `executed_*` counts the 3x MFMA flops really issued (pipe utilisation).
-            kdur_iso, kflop = time_dominant_kernel_h3(N, T // cfg.n_group_size, nprod=2 if f8x else 3)
-            # ... and the same launches INSIDE the training step (the WN in_layer forward convs: same descriptor class),
-            # each bracketed by HIP events on its stream, over three more steps.  Back to back the kernel runs into the
-            # chip's power limit (MFMA at full tilt throttles the clock); in the step it alternates with memory-bound
-            # kernels.  The in-step average is what rocprofv3's kernel trace of the step shows for this kernel
-            # (profiles/r05_kernel_stats.json) and what `achieved` is priced on; the back-to-back figure stays beside it.
-            kdur = float(np.mean(in_step)) if in_step else kdur_iso
-            n_in_step = len(in_step)
-            # executed MFMA work in f16-equivalent products: 3 f16 products, or 1 f16 + 2 FP8 products at twice the rate
             nprod, peak = (2.0 if f8x else 3.0), PEAK_F16_MFMA_TFLOPS
             kname = (("rowgemm_win_kernel<7,SPLIT> (rowgemm_win.hip: shared A window over the 5 taps; WN in_layer conv fwd, M=%d "
                       "N=1024 K=5x1024, hi.hi f16 MFMA + both cross terms in one block-scaled FP8 MFMA per 32-deep k step)" % N)
                      if f8x else
                      ("rowgemm_h3d_kernel<MB,3> (rowgemm_h3w.hip; WN in_layer conv fwd, M=%d N=1024 K=5x1024, 3 f16 MFMA "
                       "products per fp32 product)" % N))
-            prec = ("f16 hi.hi product + FP8 (e4m3) cross terms, fp32 accumulate (this run's parity figures: `parity_vs_cpu`)"
-                    if f8x else "split-f16 x3 MFMA products, fp32 accumulate (this run's parity figures: `parity_vs_cpu`)")
+            prec = ("f16 hi.hi product + FP8 (e4m3) cross terms, fp32 accumulate (parity figures with --full: `parity_vs_cpu`)"
+                    if f8x else "split-f16 x3 MFMA products, fp32 accumulate (parity figures with --full: `parity_vs_cpu`)")
         else:
-            kdur, kflop = time_dominant_kernel(N, T // cfg.n_group_size)
-            kdur_iso, n_in_step = kdur, 0
             nprod, peak = 1.0, PEAK_FP32_MFMA_TFLOPS
             kname = "rowgemm_f32_kernel<0> (WN in_layer conv fwd, M=%d N=1024 K=5x1024)" % N
             prec = "fp32 MFMA"
-        achieved = kflop / kdur / 1e12
-        # HBM-side bytes per launch: PMC counters need rocprofv3 around the process, so they cannot be read in-run;
-        # tools/pmc_dominant.sh measures this same launch (FETCH_SIZE / WRITE_SIZE in their own passes, the guide's
-        # gfx950 corrections) and writes profiles/pmc_dominant.json, which is quoted here and labelled static
-        traffic, traffic_src = None, None
-        try:
-            with open(os.path.join(ROOT, "profiles", "pmc_dominant.json")) as f:
-                pm = json.load(f)
-            if h3 and pm.get("M") == N:
-                traffic, traffic_src = pm["traffic_bytes_per_launch"], pm["source"]
-        except Exception:
-            pass
+        roofline = None
+        if args.full:
+            if h3:
+                # `achieved` counts the ALGORITHMIC flops of the launch (2*M*N*K*taps) against the dense f16 MFMA
+                # peak the kernel runs on; `executed_*` counts the MFMA flops really issued (pipe utilisation).
+                kdur_iso, kflop = time_dominant_kernel_h3(N, T // cfg.n_group_size, nprod=2 if f8x else 3)
+                # ... and the same launches INSIDE the training step (the WN in_layer forward convs: same descriptor class),
+                # each bracketed by HIP events on its stream, over three more steps.  Back to back the kernel runs into the
+                # chip's power limit (MFMA at full tilt throttles the clock); in the step it alternates with memory-bound
+                # kernels.  The in-step average is what rocprofv3's kernel trace of the step shows for this kernel
+                # (profiles/r05_kernel_stats.json) and what `achieved` is priced on; the back-to-back figure stays beside it.
+                kdur = float(np.mean(in_step)) if in_step else kdur_iso
+                n_in_step = len(in_step)
+            else:
+                kdur, kflop = time_dominant_kernel(N, T // cfg.n_group_size)
+                kdur_iso, n_in_step = kdur, 0
+            achieved = kflop / kdur / 1e12
+            # HBM-side bytes per launch: PMC counters need rocprofv3 around the process, so they cannot be read in-run;
+            # tools/pmc_dominant.sh measures this same launch (FETCH_SIZE / WRITE_SIZE in their own passes, FETCH_SIZE
+            # corrected for gfx950) and writes profiles/pmc_dominant.json, which is quoted here and labelled static
+            traffic, traffic_src = None, None
+            try:
+                with open(os.path.join(ROOT, "profiles", "pmc_dominant.json")) as f:
+                    pm = json.load(f)
+                if h3 and pm.get("M") == N:
+                    traffic, traffic_src = pm["traffic_bytes_per_launch"], pm["source"]
+            except Exception:
+                pass
+            roofline = {"bound": "mfma", "kernel": kname,
+                        "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+                        "frac_algorithmic": achieved / peak, "frac_executed": nprod * achieved / peak,
+                        "avg_launch_ms": kdur * 1e3, "avg_launch_measured": (f"HIP events around the {n_in_step} launches of this "
+                                                                             "descriptor class in three training steps" if n_in_step
+                                                                             else "HIP events around 20 back-to-back launches"),
+                        "avg_launch_ms_back_to_back": kdur_iso * 1e3,
+                        "flop_per_launch": kflop, "executed_mfma_flop_per_launch": nprod * kflop,
+                        "executed_mfma_tflops": nprod * achieved,
+                        # fp32 operands and result once = A 52 MB + W 21 MB + C 52 MB at M = 12 800
+                        "algorithmic_bytes_per_launch": N * 1024 * 4 * 2 + 5 * 1024 * 1024 * 4,
+                        # what this kernel's formats move at best: split A (hi + 8-bit cross array, 4 B/element), split
+                        # weights (4 B) and the output's split pair (4 B; since round 5 no fp32 copy beside it under the
+                        # FP8-cross scheme: 8 B with one), each once
+                        "own_format_bytes_per_launch": (N * 1024 * (8 if f8x else 12) + 5 * 1024 * 1024 * 4) if h3 else None,
+                        "traffic": traffic, "traffic_static": traffic is not None, "traffic_source": traffic_src,
+                        # FETCH_SIZE counts L2 -> fabric requests, Infinity-Cache hits included (MI355X HBM path): with 8
+                        # XCDs = 8 private L2s an operand is fetched once per XCD that uses it.  The tile sequence gives an XCD
+                        # r x c = 29 tiles (r row tiles of 224 rows x 4 KB, c column tiles of 5.2 MB of weights); r A + c B is
+                        # minimal at c = 2 (the shipped order: r = 14.5): 13.3 + 10.5 MB per XCD = 190 MB of reads per launch
+                        # for 73 MB of operands -- the floor of this counter for any 8-L2 mapping, not re-reads from HBM
+                        "traffic_floor_8_private_l2": (190.4e6 + N * 1024 * (4.0 if f8x else 8.0)) if (h3 and N == 12800) else None,
+                        # what a pure v_mfma_f32_32x32x16_f16 loop sustains on THIS data distribution (uniform random
+                        # operands throttle the clock to ~1.55 GHz; zeros reach 2230): profiles/r01_mfma_dep.txt
+                        "peak_measured_random_operands": 1620.0 if h3 else None,
+                        "frac_executed_of_measured_peak": (nprod * achieved / 1620.0) if h3 else None}
         fl = algorithmic_flops_per_frame(cfg)
         by = algorithmic_bytes_per_frame(cfg) + 3 * 4 * sum(p.numel() for p in dec.parameters()) / (B * T)
         res = {
@@ -994,32 +1102,6 @@ def main():
             "loss_mel_global": (loss_global or {}).get("loss_mel"),
             "loss_terms_global": loss_global,
             "distributed": dist_info,
-            "roofline": {"bound": "mfma", "kernel": kname,
-                         "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                         "frac_algorithmic": achieved / peak, "frac_executed": nprod * achieved / peak,
-                         "avg_launch_ms": kdur * 1e3, "avg_launch_measured": (f"HIP events around the {n_in_step} launches of this "
-                                                                              "descriptor class in three training steps" if n_in_step
-                                                                              else "HIP events around 20 back-to-back launches"),
-                         "avg_launch_ms_back_to_back": kdur_iso * 1e3,
-                         "flop_per_launch": kflop, "executed_mfma_flop_per_launch": nprod * kflop,
-                         "executed_mfma_tflops": nprod * achieved,
-                         # fp32 operands and result once = A 52 MB + W 21 MB + C 52 MB at M = 12 800
-                         "algorithmic_bytes_per_launch": N * 1024 * 4 * 2 + 5 * 1024 * 1024 * 4,
-                         # what this kernel's formats move at best: split A (hi + 8-bit cross array, 4 B/element), split
-                         # weights (4 B) and the output's split pair (4 B; since round 5 no fp32 copy beside it under the
-                         # FP8-cross scheme: 8 B with one), each once
-                         "own_format_bytes_per_launch": (N * 1024 * (8 if f8x else 12) + 5 * 1024 * 1024 * 4) if h3 else None,
-                         "traffic": traffic, "traffic_static": traffic is not None, "traffic_source": traffic_src,
-                         # FETCH_SIZE counts L2 -> fabric requests, Infinity-Cache hits included (MI355X_MICROARCH.md, HBM): with 8
-                         # XCDs = 8 private L2s an operand is fetched once per XCD that uses it.  The tile sequence gives an XCD
-                         # r x c = 29 tiles (r row tiles of 224 rows x 4 KB, c column tiles of 5.2 MB of weights); r A + c B is
-                         # minimal at c = 2 (the shipped order: r = 14.5): 13.3 + 10.5 MB per XCD = 190 MB of reads per launch
-                         # for 73 MB of operands -- the floor of this counter for any 8-L2 mapping, not re-reads from HBM
-                         "traffic_floor_8_private_l2": (190.4e6 + N * 1024 * (4.0 if f8x else 8.0)) if (h3 and N == 12800) else None,
-                         # what a pure v_mfma_f32_32x32x16_f16 loop sustains on THIS data distribution (uniform random
-                         # operands throttle the clock to ~1.55 GHz; zeros reach 2230): profiles/r01_mfma_dep.txt
-                         "peak_measured_random_operands": 1620.0 if h3 else None,
-                         "frac_executed_of_measured_peak": (nprod * achieved / 1620.0) if h3 else None},
             "step_flops": {"algorithmic_tflop_per_step": fl * B * T / 1e12,
                            "achieved_tflops_per_gpu": fl * B * T / (ms_per_step * 1e-3) / 1e12,
                            "frac_of_fp32_mfma_peak": fl * B * T / (ms_per_step * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS},
@@ -1027,6 +1109,8 @@ def main():
                          "achieved": by * B * T / (ms_per_step * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
                          "frac": by * B * T / (ms_per_step * 1e-3) / 1e9 / PEAK_HBM_GBS},
         }
+        if roofline is not None:
+            res["roofline"] = roofline
         def side_leg(mode, steps=5):
             """time `steps` steps with the decoder switched to another product scheme (same weights, same batch)"""
             prev = dec.gemm_precision
@@ -1047,14 +1131,14 @@ def main():
             os.environ["RADMMM_PRECISION"] = prev
             return dts, float(lv.detach())
 
-        if world == 1 and f8x and not args.no_throughput_mode:
+        if args.full and world == 1 and f8x and not args.no_throughput_mode:
             # the three-f16-product scheme (2e-6 instead of 4e-5 on z): same kernels, 3/2 of the MFMA work
             dt3, l3 = side_leg("h3")
             res["exact_split_mode"] = {"dtype": "split-f16 x3 MFMA products (RADMMM_PRECISION=h3), fp32 accumulate", "steps": 5,
                                        "ms_per_step": dt3 * 1e3, "statistic": "median", "value": B * T / dt3, "unit": "mel-frames/s", "loss_mel": l3,
                                        "loss_rel_diff_vs_default_mode": abs(l3 - loss_val) / abs(loss_val),
                                        "within_parity_bar": True}
-        if world == 1 and h3 and not args.no_throughput_mode:
+        if args.full and world == 1 and h3 and not args.no_throughput_mode:
             # BASELINE's config label for this workload says "bf16": the same kernels with ONE fp16 MFMA product per
             # fp32 product (operands rounded to fp16, fp32 accumulate).  Reported beside, never as, `value`: this mode is
             # outside north_star's 1e-4 parity bar.
@@ -1064,7 +1148,7 @@ def main():
                                       "loss_mel": l16, "loss_rel_diff_vs_parity_mode": abs(l16 - loss_val) / abs(loss_val),
                                       "within_parity_bar": False}
         hip_out = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the decoder's outputs on the bench batch for `parity_vs_cpu`, taken BEFORE any leg that updates the weights
             # (the full-step leg and --optimizer run RAdam on them; the oracle runs on the initial state)
             if opt is not None:
@@ -1079,18 +1163,19 @@ def main():
             reducer.detach()                          # the step-wide reducer of that leg takes over the decoder's parameters
             res["full_step"] = full_step_leg(dec, cfg, CFG, gb, B, T, dev, median_ms, joint=args.config == "joint",
                                              parity_utts=0 if args.no_cpu_baseline else args.joint_parity_utts)
-        # what the split producers reported over the whole run (ops.GradScale; published without host synchronisation)
-        res["saturation"] = sat_report if sat_report is not None else saturation_report()
-        res["roofline_hbm"] = hbm_rooflines(dec, cfg, B, T)
-        res["roofline_mfma"] = mfma_rooflines(dec, cfg, B, T)
-        # what the process-group path costs a step at world size 1 (an A/B of two processes on one box cannot
-        # be taken from inside one run: quoted from the committed measurement, with what it was made of)
-        res["process_group_overhead_ms"] = {
-            "value": 0.5, "static": True, "source": "profiles/r06_pg_overhead.txt",
-            "what": "RADMMM_BENCH_SPAWN=1 (RCCL at world size 1, bucketed all-reduce inside the step) minus the default run, same box, "
-                    "alternating: 41.66 / 41.67 against 41.14 / 41.22 ms; was +1.8 ms (41.84 / 41.69 against 39.97 / 39.93) until the "
-                    "one-rank ReduceOp.AVG -- RCCL's oneRankReduce<FuncPreMulSum>: 17 launches rewriting 876 MB beside the GEMMs, "
-                    "1.31 ms of kernel time per step -- became an in-place SUM at world size 1 (rad_mmm_amd/ddp.py)"}
+        if args.full:
+            # what the split producers reported over the whole run (ops.GradScale; published without host synchronisation)
+            res["saturation"] = sat_report if sat_report is not None else saturation_report()
+            res["roofline_hbm"] = hbm_rooflines(dec, cfg, B, T)
+            res["roofline_mfma"] = mfma_rooflines(dec, cfg, B, T)
+            # what the process-group path costs a step at world size 1 (an A/B of two processes on one box cannot
+            # be taken from inside one run: quoted from the committed measurement, with what it was made of)
+            res["process_group_overhead_ms"] = {
+                "value": 0.5, "static": True, "source": "profiles/r06_pg_overhead.txt",
+                "what": "RADMMM_BENCH_SPAWN=1 (RCCL at world size 1, bucketed all-reduce inside the step) minus the default run, same box, "
+                        "alternating: 41.66 / 41.67 against 41.14 / 41.22 ms; was +1.8 ms (41.84 / 41.69 against 39.97 / 39.93) until the "
+                        "one-rank ReduceOp.AVG -- RCCL's oneRankReduce<FuncPreMulSum>: 17 launches rewriting 876 MB beside the GEMMs, "
+                        "1.31 ms of kernel time per step -- became an in-place SUM at world size 1 (rad_mmm_amd/ddp.py)"}
         if hip_out is not None:
             res["cpu_baseline"], res["parity_vs_cpu"] = cpu_baseline(cfg, sd, batch, hip_out)
     if use_dist:

@@ -47,7 +47,7 @@ def test_bench_control_flow_at_world_size_two_on_one_gpu():
     timing, in-step launch timing, saturation report, JSON line from rank 0."""
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", "29611", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--batch", "8", "--frames", "400"], capture_output=True, text=True, timeout=600,
+                        "--warmup", "1", "--batch", "8", "--frames", "400", "--full"], capture_output=True, text=True, timeout=600,
                        env=_env(RADMMM_BENCH_SHARE_GPU="1", RADMMM_BENCH_BACKEND="gloo", RADMMM_CHECK_SATURATION="1"), cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     line = [l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1]

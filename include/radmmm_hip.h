@@ -608,6 +608,36 @@ int radmmm_sumsq(const float* x, int64_t n, float* partial, radmmm_stream_t stre
 int radmmm_radam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* clip_coef, float beta1,
                       float beta2, float eps, float step_size, float wd_lr, int use_denom, radmmm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * HiFi-GAN vocoder and STFT denoiser (vocoders/hifigan_models.py:104-247, vocoders/hifigan_denoiser.py:25-58,
+ * audio_processing.py:195-291).  Every convolution is a radmmm_rowgemm_f32 launch (conv_pre and the resblock convs
+ * with taps/dil; ConvTranspose1d(k, u, p) as ONE row GEMM with N = u*Cout over a packed polyphase weight; the inverse
+ * STFT's overlap-add the same way).  These entry points are what surrounds them.  `lens` / `frames` are int32 device
+ * arrays [B] (NULL: all rows valid); rows at or past an item's length are written as 0.
+ *   voc_lrelu        y[r, c] = leaky_relu(x[r, c] / div, slope), c < cols (0 in cols <= c < ldy), rows = B*T
+ *   voc_conv_post    out[r] = tanh(bias[0] + sum_tap sum_c leaky_relu(x[r + tap - taps/2, c] / div, slope) *
+ *                    w[tap*ldw + c]) with the shifted row inside the item (taps odd, taps*ldw <= 4096)
+ *   voc_reflect_pad  xpad[b*pitch + p] = audio[b*lda + reflect(p - pad)] inside [0, lens[b]) for p < lens[b] + 2 pad,
+ *                    0 beyond (caller guarantees lens[b] > pad)
+ *   voc_spec_bins    spec rows [re 0..cutoff | im cutoff..2 cutoff]: mag' = max(|bin| - bias[c]*strength, 0); bin *=
+ *                    mag'/|bin| (|bin| == 0: (mag', 0)).  mag_out != NULL: mag_out[r*cutoff + c] = |bin| only
+ *   voc_istft_finish y [B][pitch] (overlap-add already trimmed by n_fft/2): sample n < (frames[b]-1)*hop is divided by
+ *                    the window sum-square envelope of frames[b] frames at n + n_fft/2 where it exceeds FLT_MIN
+ *                    (winsq: fp64 [n_fft] squared window), times n_fft/hop; 0 beyond
+ *   voc_normalize    audio[b, 0:lens[b]] /= max |audio[b, 0:lens[b]]|
+ * ------------------------------------------------------------------------------------ */
+int radmmm_voc_lrelu(const float* x, int ldx, float* y, int ldy, int rows, int cols, int T, const int32_t* lens,
+                     float div, float slope, radmmm_stream_t stream);
+int radmmm_voc_conv_post(const float* x, int ldx, const float* w, int ldw, const float* bias, float* out, int rows,
+                         int C, int taps, int T, const int32_t* lens, float div, float slope, radmmm_stream_t stream);
+int radmmm_voc_reflect_pad(const float* audio, int lda, const int32_t* lens, float* xpad, int B, int S, int pad,
+                           int pitch, radmmm_stream_t stream);
+int radmmm_voc_spec_bins(float* spec, int lds, int rows, int cutoff, const float* bias, float strength, float* mag_out,
+                         radmmm_stream_t stream);
+int radmmm_voc_istft_finish(float* y, int B, int pitch, const int32_t* frames, const double* winsq, int n_fft, int hop,
+                            radmmm_stream_t stream);
+int radmmm_voc_normalize(float* audio, int lda, const int32_t* lens, int B, int S, radmmm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

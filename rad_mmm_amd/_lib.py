@@ -205,6 +205,12 @@ def _load() -> C.CDLL:
         "radmmm_mas_width1": [p, p, p, p, p, i, i, i, p],
         "radmmm_mas_width1_prob": [p, p, p, p, p, i, i, i, p],
         "radmmm_stft_mel": [p, p, p, p, p, i, i, i, i, i, f, p],
+        "radmmm_voc_lrelu": [p, i, p, i, i, i, i, p, f, f, p],
+        "radmmm_voc_conv_post": [p, i, p, i, p, p, i, i, i, i, p, f, f, p],
+        "radmmm_voc_reflect_pad": [p, i, p, p, i, i, i, i, p],
+        "radmmm_voc_spec_bins": [p, i, i, i, p, f, p, p],
+        "radmmm_voc_istft_finish": [p, i, i, p, p, i, i, p],
+        "radmmm_voc_normalize": [p, i, p, i, i, p],
     }
     missing = [n for n in sig if not hasattr(lib, n)]
     if missing:

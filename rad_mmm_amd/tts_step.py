@@ -226,3 +226,24 @@ class TTSTrainingStep(nn.Module):
         for v, w in losses.values():
             loss = v * w if loss is None else loss + v * w
         return loss, losses, outputs
+
+    # ---- audio out (tts_lightning_modules.py:568-579) ------------------------------------------------------------------
+    # (generator, denoiser) of rad_mmm_amd.vocoder (load_hifigan_vocoder), as the reference's `synth_vocoder`; a plain
+    # tuple, so the vocoder's weights never enter this module's state_dict
+    synth_vocoder = None
+
+    def vocode_mels(self, mels: torch.Tensor, out_lens, strength: float = 0.001, normalize: bool = True):
+        """One waveform per utterance (numpy fp32, out_lens[b] * hop samples), each scaled to max|x| = 1 with normalize,
+        through ONE batched generator + denoiser pass.  mels [B, 80, T] descaled, out_lens a SequenceLength (its host
+        lengths are used: the only synchronisation is the final copy to the host) or lengths in frames.  The reference
+        passes `mels` rather than `current_mel` to get_audio_for_mels (tts_lightning_modules.py:572-573, which vocodes
+        mels[0]) and so returns utterance 0 B times; this returns each utterance at its own length."""
+        from .vocoder import vocode
+        if self.synth_vocoder is None:
+            raise RuntimeError("vocode_mels: attach a vocoder first (step.synth_vocoder = load_hifigan_vocoder(...))")
+        generator, denoiser = self.synth_vocoder
+        lens = out_lens.lengths_host if isinstance(out_lens, SequenceLength) else out_lens
+        audio, s_lens = vocode(generator, denoiser, mels, lens, strength=strength, normalize=normalize)
+        audio = audio.cpu().numpy()
+        s_lens = s_lens.cpu().tolist()
+        return [audio[b, :s_lens[b]].copy() for b in range(len(s_lens))]

@@ -1,0 +1,477 @@
+"""HiFi-GAN generator + STFT denoiser, batched on the GPU: mel -> waveform (reference vocoders/hifigan_models.py:104-247,
+vocoders/hifigan_denoiser.py:25-58, audio_processing.py:195-291, vocoders/vocoder_utils.py:35-48, 104-132).
+
+The reference vocodes one utterance at a time on the CPU.  Here a batch [B, 80, T] with per-item lengths goes through
+one launch sequence; item b equals a call with item b alone (every layer treats rows at or past the item's length,
+times the stage's upsample product, as zeros, and the denoiser reflects at the item's own length) and everything past
+its length is exactly 0.
+
+Layout: channels-last rows ([B*T, C] fp32, row r = b*T + t) as in the rest of the package.  Every convolution is a
+radmmm_rowgemm_f32 launch (exact fp32 MFMA):
+  * Conv1d(k, dilation d): taps = k, dil = d, length-masked operand rows.
+  * ConvTranspose1d(k, u, p): in channels-last the u output rows i*u .. i*u+u-1 are contiguous, so the layer is ONE
+    row GEMM with N = u*Cout over a window of input rows, reading input row i and writing the [rows][u*Cout] view of
+    the output; its weight is packed once (pack_polyphase, zeros where a tap does not reach a phase).
+  * the inverse STFT is the same polyphase GEMM (u = hop, k = n_fft, N = hop), the trim folded into the packing.
+leaky_relu of a conv's operand, conv_post + tanh, the reflect pad, the bin rescale, the window-sum division and the
+normalisation are kernels of csrc/vocoder.hip.
+"""
+from __future__ import annotations
+
+import json
+import warnings
+from typing import Optional, Tuple, Union
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import ops
+from ._lib import RadmmmError, check, f32c, fp32_region, lib, ptr, rowgemm, stream
+from .audio_processing import _hann_periodic, windowed_dft_basis
+
+LRELU_SLOPE = 0.1          # hifigan_models.py:52 (the final leaky_relu before conv_post uses torch's default 0.01)
+POST_SLOPE = 0.01
+N_MEL = 80
+
+
+def get_padding(kernel_size: int, dilation: int = 1) -> int:
+    return int((kernel_size * dilation - dilation) / 2)
+
+
+def _cfg(h, key, default=None):
+    if isinstance(h, dict):
+        return h.get(key, default)
+    return getattr(h, key, default)
+
+
+def fold_weight_norm(v: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """torch weight_norm with its default dim = 0: w = g * v / ||v[i]|| over all dimensions but the first.  For a
+    ConvTranspose1d weight [Cin, Cout, k] the first dimension is the INPUT channel.  Any device (the CPU restatement of
+    what radmmm_weightnorm_fwd computes)."""
+    n = v.reshape(v.shape[0], -1).norm(dim=1)
+    shape = (-1,) + (1,) * (v.dim() - 1)
+    return v * (g.reshape(shape) / n.reshape(shape))
+
+
+def polyphase_shifts(k: int, u: int, p: int, off: int = 0) -> int:
+    """half width h of the tap window (taps = 2h + 1) of pack_polyphase"""
+    h = 0
+    for j in range(k):
+        r = (j - p) % u
+        s = (r + p - j) // u
+        h = max(h, abs(off + s))
+    return h
+
+
+def pack_polyphase(w: torch.Tensor, u: int, p: int, off: int = 0, ldk: Optional[int] = None) -> torch.Tensor:
+    """ConvTranspose1d weight w [Cin, Cout, k] (stride u, padding p) -> Wp [taps, u*Cout, ldk] (K-contiguous, zero
+    padded to ldk >= Cin) such that output sample o = (g + off) * u + r is
+
+        y[o, co] = sum_tap sum_ci x[g + tap - taps//2, ci] * Wp[tap, r*Cout + co, ci]
+
+    i.e. a centred `taps`-tap row GEMM over the input rows writing output row group g.  Output o receives input i
+    through tap j = o + p - i*u; with o = q*u + r and i = q + s that is j = r + p - s*u.  off shifts the output rows
+    by whole groups (the inverse STFT's n_fft/2 trim).  Works on any device."""
+    Cin, Cout, k = w.shape
+    ldk = ldk or Cin
+    h = polyphase_shifts(k, u, p, off)
+    j = torch.arange(k)
+    r = (j - p) % u
+    s = (r + p - j) // u
+    tap = off + s + h
+    Wp = torch.zeros(2 * h + 1, u, Cout, ldk, dtype=w.dtype, device=w.device)
+    Wp[tap.to(w.device), r.to(w.device), :, :Cin] = w.permute(2, 1, 0)
+    return Wp.reshape(2 * h + 1, u * Cout, ldk)
+
+
+def remap_old_keys(state_dict: dict) -> dict:
+    """Generator.load_state_dict's remap of old checkpoints (hifigan_models.py:207-219): a 5-part key
+    resblocks.N.<convs>.<n>.<param> becomes resblocks.{N//3}.{N%3}.<convs>.<n>.<param>."""
+    out = {}
+    for k, v in state_dict.items():
+        nk = k
+        if "resblocks" in k:
+            parts = k.split(".")
+            if len(parts) == 5:
+                layer = int(parts[1])
+                nk = f"resblocks.{layer // 3}.{layer % 3}.{'.'.join(parts[2:])}"
+        out[nk] = v
+    return out
+
+
+def _wn(m: nn.Module) -> nn.Module:
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        return nn.utils.weight_norm(m)
+
+
+def _unwn(m: nn.Module) -> None:
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        nn.utils.remove_weight_norm(m)
+
+
+class _ResBlock1(nn.Module):
+    def __init__(self, channels, kernel_size=3, dilation=(1, 3, 5)):
+        super().__init__()
+        self.kernel_size, self.dilation = kernel_size, tuple(dilation)
+        self.convs1 = nn.ModuleList([_wn(nn.Conv1d(channels, channels, kernel_size, 1, dilation=d,
+                                                   padding=get_padding(kernel_size, d))) for d in dilation])
+        self.convs2 = nn.ModuleList([_wn(nn.Conv1d(channels, channels, kernel_size, 1, dilation=1,
+                                                   padding=get_padding(kernel_size, 1))) for _ in dilation])
+
+    def plan(self):
+        """[(conv, dilation, lrelu its output, residual add)] in order"""
+        out = []
+        for c1, c2, d in zip(self.convs1, self.convs2, self.dilation):
+            out.append((c1, d, True, False))
+            out.append((c2, 1, False, True))
+        return out
+
+
+class _ResBlock2(nn.Module):
+    def __init__(self, channels, kernel_size=3, dilation=(1, 3)):
+        super().__init__()
+        self.kernel_size, self.dilation = kernel_size, tuple(dilation)
+        self.convs = nn.ModuleList([_wn(nn.Conv1d(channels, channels, kernel_size, 1, dilation=d,
+                                                  padding=get_padding(kernel_size, d))) for d in dilation])
+
+    def plan(self):
+        return [(c, d, False, True) for c, d in zip(self.convs, self.dilation)]
+
+
+def _conv_weight(m: nn.Module) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    if hasattr(m, "weight_g"):
+        return m.weight_v, m.weight_g
+    return m.weight, None
+
+
+def _lens_arg(lens, B: int, T: int, dev: torch.device):
+    """-> (device int32 [B], host int64 [B] or None).  Host lengths are copied through pinned memory without a
+    synchronisation; device lengths are used as they are."""
+    if lens is None:
+        host = torch.full((B,), T, dtype=torch.int64)
+    elif isinstance(lens, torch.Tensor) and lens.is_cuda:
+        return lens.to(torch.int32), None
+    else:
+        host = torch.as_tensor(lens, dtype=torch.int64).reshape(-1).cpu()
+    if host.numel() != B:
+        raise ValueError(f"lens has {host.numel()} entries for a batch of {B}")
+    if bool((host < 1).any()) or bool((host > T).any()):
+        raise ValueError(f"lens must lie in [1, {T}], got {host.tolist()}")
+    return _to_device(host, dev), host
+
+
+def _to_device(host: torch.Tensor, dev: torch.device) -> torch.Tensor:
+    return host.to(torch.int32).pin_memory().to(dev, non_blocking=True)
+
+
+class HiFiGANGenerator(nn.Module):
+    """HiFi-GAN Generator(h) (hifigan_models.py:172-247): same sub-module and state_dict names (conv_pre, ups.{i},
+    resblocks.{i}.{j}.convs1/convs2/convs.{n}, conv_post with .weight_g/.weight_v/.bias), forward on the GPU.
+
+    forward(mel [B, 80, T], lens=None) -> audio [B, 1, T * prod(upsample_rates)], zero past lens[b] * hop.
+    lens: host (list / CPU tensor: no synchronisation) or device lengths in mel frames."""
+
+    def __init__(self, h):
+        super().__init__()
+        blur = _cfg(h, "gaussian_blur", None) or {"p_blurring": 0.0}
+        if float(blur.get("p_blurring", 0.0)) > 0.0:
+            raise ValueError("HiFiGANGenerator: the Gaussian blur augmentation (p_blurring > 0) is not supported")
+        self.upsample_rates = [int(u) for u in _cfg(h, "upsample_rates")]
+        self.upsample_kernel_sizes = [int(k) for k in _cfg(h, "upsample_kernel_sizes")]
+        self.resblock_kernel_sizes = [int(k) for k in _cfg(h, "resblock_kernel_sizes")]
+        self.resblock_dilation_sizes = [list(d) for d in _cfg(h, "resblock_dilation_sizes")]
+        c0 = int(_cfg(h, "upsample_initial_channel"))
+        self.resblock_type = str(_cfg(h, "resblock"))
+        if self.resblock_type not in ("1", "2"):
+            raise ValueError(f"resblock must be '1' or '2', got {self.resblock_type!r}")
+        self.num_kernels = len(self.resblock_kernel_sizes)
+        self.num_upsamples = len(self.upsample_rates)
+        for u, k in zip(self.upsample_rates, self.upsample_kernel_sizes):
+            if (k - u) % 2:
+                raise ValueError(f"upsample kernel {k} with rate {u}: output length is not T*u (k - u must be even)")
+        for k in self.resblock_kernel_sizes:
+            if k % 2 == 0:
+                raise ValueError(f"resblock kernel {k}: only odd kernels keep the length")
+        for i in range(self.num_upsamples + 1):
+            if (c0 >> i) % 4 or (c0 >> i) << i != c0:
+                raise ValueError(f"upsample_initial_channel {c0}: every stage's width must be a multiple of 4")
+        self.hop = int(np.prod(self.upsample_rates))
+        self.conv_pre = _wn(nn.Conv1d(N_MEL, c0, 7, 1, padding=3))
+        res = _ResBlock1 if self.resblock_type == "1" else _ResBlock2
+        self.ups = nn.ModuleList()
+        for i, (u, k) in enumerate(zip(self.upsample_rates, self.upsample_kernel_sizes)):
+            self.ups.append(_wn(nn.ConvTranspose1d(c0 // (2 ** i), c0 // (2 ** (i + 1)), k, u, padding=(k - u) // 2)))
+        self.resblocks = nn.ModuleList()
+        ch = c0
+        for i in range(self.num_upsamples):
+            ch = c0 // (2 ** (i + 1))
+            self.resblocks.append(nn.ModuleList([res(ch, k, d) for k, d in
+                                                 zip(self.resblock_kernel_sizes, self.resblock_dilation_sizes)]))
+        self.conv_post = _wn(nn.Conv1d(ch, 1, 7, 1, padding=3))
+        self._folded = None
+        self._folded_key = None
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        self._folded = None
+        return super().load_state_dict(remap_old_keys(state_dict), strict=strict)
+
+    def remove_weight_norm(self):
+        for m in self.modules():
+            if isinstance(m, (nn.Conv1d, nn.ConvTranspose1d)) and hasattr(m, "weight_g"):
+                _unwn(m)
+        self._folded = None
+
+    # ---- weights in the kernels' layout, folded once (again only when a parameter changed) --------------------
+    def _key(self):
+        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+
+    @staticmethod
+    def _fold_conv(m: nn.Module, ldw: int) -> torch.Tensor:
+        """Conv1d -> W [taps, Cout, ldw] (radmmm_rowgemm_f32 layout 0)"""
+        v, g = _conv_weight(m)
+        if g is not None:
+            return ops.weightnorm_fwd(f32c(v.detach()), f32c(g.detach()), ldw)[0]
+        Cout, Cin, taps = v.shape
+        W = torch.zeros(taps, Cout, ldw, device=v.device, dtype=torch.float32)
+        W[:, :, :Cin] = v.detach().float().permute(2, 0, 1)
+        return W
+
+    def _fold(self):
+        key = self._key()
+        if self._folded is not None and self._folded_key == key:
+            return self._folded
+        f = {"pre": (self._fold_conv(self.conv_pre, N_MEL), f32c(self.conv_pre.bias.detach()))}
+        ups = []
+        for m, u, k in zip(self.ups, self.upsample_rates, self.upsample_kernel_sizes):
+            v, g = _conv_weight(m)
+            Cin, Cout, _ = v.shape
+            if g is not None:       # weight_norm dim 0 of a [Cin, Cout, k] weight: one norm per INPUT channel
+                W = ops.weightnorm_fwd(f32c(v.detach()), f32c(g.detach()), Cout)[0]      # [k, Cin, Cout]
+                w = W.permute(1, 2, 0)
+            else:
+                w = v.detach().float()
+            Wp = pack_polyphase(w, u, (k - u) // 2).contiguous()
+            ups.append((Wp, f32c(m.bias.detach()).repeat(u)))
+        f["ups"] = ups
+        f["res"] = [[[(self._fold_conv(c, c.in_channels), f32c(c.bias.detach()), c.kernel_size[0], d, act, add)
+                      for c, d, act, add in blk.plan()] for blk in group] for group in self.resblocks]
+        C = self.conv_post.in_channels
+        ldw = ops.round_up(C, 4)
+        f["post"] = (self._fold_conv(self.conv_post, ldw).reshape(-1).contiguous(), f32c(self.conv_post.bias.detach()))
+        self._folded, self._folded_key = f, key
+        return f
+
+    @fp32_region
+    def forward(self, mel: torch.Tensor, lens=None) -> torch.Tensor:
+        if not mel.is_cuda:
+            raise RadmmmError("HiFiGANGenerator needs a GPU tensor (there is no CPU path)")
+        if mel.dim() != 3 or mel.shape[1] != N_MEL:
+            raise ValueError(f"mel must be [B, {N_MEL}, T], got {tuple(mel.shape)}")
+        dev = mel.device
+        B, _, T = mel.shape
+        lens_d, _ = _lens_arg(lens, B, T, dev)
+        return self._run(f32c(mel), lens_d)
+
+    def _run(self, mel: torch.Tensor, lens_d: torch.Tensor, events: Optional[list] = None) -> torch.Tensor:
+        """events: a list that receives a recorded device event after conv_pre, each stage and conv_post (timing)"""
+        B, _, T = mel.shape
+        mark = (lambda: events.append(torch.cuda.Event(enable_timing=True)) or events[-1].record()) if events is not None \
+            else (lambda: None)
+        mark()
+        f = self._fold()
+        R, Tc, lc = B * T, T, lens_d
+        xm = torch.empty(R, N_MEL, device=mel.device, dtype=torch.float32)
+        check(lib.radmmm_squeeze_rows(ptr(mel), ptr(xm), B, N_MEL, T, 1, N_MEL, 0, stream()), "squeeze_rows")
+        W, b = f["pre"]
+        C = W.shape[1]
+        x = torch.empty(R, C, device=mel.device, dtype=torch.float32)
+        rowgemm(A=xm, lda=N_MEL, B=W, ldb=W.shape[2], b_tap_stride=W.stride(0), C=x, ldc=C, M=R, N=C, K=N_MEL,
+                taps=W.shape[0], dil=1, T=Tc, lens=lc, a_mask_mode=1, bias=b, postmask=1)
+        mark()
+        div = 1.0
+        for i, u in enumerate(self.upsample_rates):
+            Wp, bp = f["ups"][i]
+            Cin, Cout = C, C // 2
+            a = torch.empty(R, Cin, device=mel.device, dtype=torch.float32)
+            check(lib.radmmm_voc_lrelu(ptr(x), Cin, ptr(a), Cin, R, Cin, Tc, ptr(lc), div, LRELU_SLOPE, stream()),
+                  "voc_lrelu")
+            xu = torch.empty(R * u, Cout, device=mel.device, dtype=torch.float32)
+            rowgemm(A=a, lda=Cin, B=Wp, ldb=Wp.shape[2], b_tap_stride=Wp.stride(0), C=xu, ldc=u * Cout, M=R,
+                    N=u * Cout, K=Cin, taps=Wp.shape[0], dil=1, T=Tc, lens=lc, a_mask_mode=1, bias=bp, postmask=1)
+            R, Tc, C = R * u, Tc * u, Cout
+            lc = lc * u
+            xs = torch.empty(R, C, device=mel.device, dtype=torch.float32)
+            a = torch.empty(R, C, device=mel.device, dtype=torch.float32)
+            t = torch.empty(R, C, device=mel.device, dtype=torch.float32)
+            bufs = [torch.empty(R, C, device=mel.device, dtype=torch.float32) for _ in range(2)]
+            for j, blk in enumerate(f["res"][i]):
+                xc, nxt = xu, 0
+                for n, (Wc, bc, k, d, act, add) in enumerate(blk):
+                    if add:                    # x = conv(lrelu(...)) + x  (ResBlock1's c2, ResBlock2's convs)
+                        src = t if n > 0 and blk[n - 1][4] else None
+                        if src is None:
+                            check(lib.radmmm_voc_lrelu(ptr(xc), C, ptr(a), C, R, C, Tc, ptr(lc), 1.0, LRELU_SLOPE,
+                                                       stream()), "voc_lrelu")
+                            src = a
+                        out = bufs[nxt]
+                        last = n == len(blk) - 1
+                        rowgemm(A=src, lda=C, B=Wc, ldb=Wc.shape[2], b_tap_stride=Wc.stride(0), C=out, ldc=C, M=R,
+                                N=C, K=C, taps=k, dil=d, T=Tc, lens=lc, a_mask_mode=1, bias=bc, postmask=1,
+                                add=xc, ldadd=C, C2=xs if last else None, ldc2=C, c2_accum=1 if (last and j > 0) else 0)
+                        xc, nxt = out, 1 - nxt
+                    else:                      # ResBlock1's c1: t = lrelu(c1(lrelu(x)))
+                        check(lib.radmmm_voc_lrelu(ptr(xc), C, ptr(a), C, R, C, Tc, ptr(lc), 1.0, LRELU_SLOPE,
+                                                   stream()), "voc_lrelu")
+                        rowgemm(A=a, lda=C, B=Wc, ldb=Wc.shape[2], b_tap_stride=Wc.stride(0), C=t, ldc=C, M=R, N=C,
+                                K=C, taps=k, dil=d, T=Tc, lens=lc, a_mask_mode=1, bias=bc, postmask=1)
+                        check(lib.radmmm_voc_lrelu(ptr(t), C, ptr(t), C, R, C, Tc, ptr(lc), 1.0, LRELU_SLOPE,
+                                                   stream()), "voc_lrelu")
+            x = xs
+            div = float(self.num_kernels)
+            mark()
+        Wpost, bpost = f["post"]
+        audio = torch.empty(B, Tc, device=mel.device, dtype=torch.float32)
+        check(lib.radmmm_voc_conv_post(ptr(x), C, ptr(Wpost), Wpost.numel() // 7, ptr(bpost), ptr(audio), R, C, 7, Tc,
+                                       ptr(lc), div, POST_SLOPE, stream()), "voc_conv_post")
+        mark()
+        return audio.view(B, 1, Tc)
+
+
+class Denoiser(nn.Module):
+    """Denoiser(generator, filter_length=1024, n_overlap=4, win_length=1024, mode='zeros') of
+    vocoders/hifigan_denoiser.py:25-58 on the GPU.  The bias spectrum (first STFT frame of the generator's output for a
+    zero mel (1, 80, 88)) is computed with the HIP generator at the first call.
+
+    forward(audio [B, S], strength=0.1, lens=None) -> [B, 1, (S // hop) * hop]; lens in samples (host or device), item
+    b comes back with (lens[b] // hop) * hop samples and zeros beyond.  The reference reflect-pads by filter_length/2,
+    which needs lens[b] > filter_length/2: shorter items raise."""
+
+    def __init__(self, generator: HiFiGANGenerator, filter_length=1024, n_overlap=4, win_length=1024, mode="zeros"):
+        super().__init__()
+        if mode != "zeros":
+            raise ValueError(f"Denoiser mode {mode!r} is not supported (only 'zeros')")
+        self.__dict__["generator"] = generator          # not a sub-module: the reference's state_dict has no such keys
+        self.filter_length = int(filter_length)
+        self.hop_length = int(filter_length / n_overlap)
+        self.win_length = int(win_length)
+        n_fft, hop = self.filter_length, self.hop_length
+        if n_fft % 4 or hop % 4 or (n_fft // 2) % hop or win_length != n_fft:
+            raise ValueError("Denoiser: needs filter_length % 4 == 0, hop % 4 == 0, (filter_length/2) % hop == 0 and "
+                             "win_length == filter_length")
+        self.cutoff = n_fft // 2 + 1
+        self.ldk = ops.round_up(2 * self.cutoff, 4)
+        fb = np.fft.fft(np.eye(n_fft))
+        fourier = np.vstack([np.real(fb[:self.cutoff]), np.imag(fb[:self.cutoff])])
+        win = torch.from_numpy(_hann_periodic(win_length)).float()
+        inv_basis = torch.from_numpy(np.linalg.pinv((n_fft / hop) * fourier).T).float() * win     # [2 cutoff, n_fft]
+        self.register_buffer("forward_basis", torch.from_numpy(windowed_dft_basis(n_fft, win_length)))
+        self.register_buffer("inverse_packed", pack_polyphase(inv_basis[:, None, :], hop, 0, (n_fft // 2) // hop,
+                                                              self.ldk).contiguous())
+        self.register_buffer("winsq", torch.from_numpy(_hann_periodic(win_length) ** 2))
+        self.bias_spec = None
+
+    def _bias(self, dev):
+        if self.bias_spec is None or self.bias_spec.device != dev:
+            mel0 = torch.zeros(1, N_MEL, 88, device=dev)
+            audio = self.generator(mel0)[:, 0]
+            spec = self._spectrum(audio, None, torch.ones(1, dtype=torch.int32, device=dev), 1)
+            mag = torch.empty(self.cutoff, device=dev, dtype=torch.float32)
+            check(lib.radmmm_voc_spec_bins(ptr(spec), self.ldk, 1, self.cutoff, None, 0.0, ptr(mag), stream()),
+                  "voc_spec_bins")
+            self.bias_spec = mag
+        return self.bias_spec
+
+    def _spectrum(self, audio, lens_d, frames_d, F):
+        """windowed DFT of the reflect-padded frames: spec [B*F, ldk] (re | im), frames past frames_d[b] are 0"""
+        B, S = audio.shape
+        n_fft, hop = self.filter_length, self.hop_length
+        pitch = ops.round_up(S + n_fft, 4)
+        xpad = torch.empty(B * pitch, device=audio.device, dtype=torch.float32)
+        check(lib.radmmm_voc_reflect_pad(ptr(audio), S, ptr(lens_d), ptr(xpad), B, S, n_fft // 2, pitch, stream()),
+              "voc_reflect_pad")
+        spec = torch.empty(B * F, self.ldk, device=audio.device, dtype=torch.float32)
+        fb = self.forward_basis
+        rowgemm(A=xpad, lda=hop, a_item_stride=pitch, B=fb, ldb=n_fft, b_tap_stride=0, C=spec, ldc=self.ldk, M=B * F,
+                N=2 * self.cutoff, K=n_fft, taps=1, T=F, lens=frames_d, a_mask_mode=1, postmask=1)
+        return spec
+
+    @fp32_region
+    def forward(self, audio: torch.Tensor, strength: float = 0.1, lens=None) -> torch.Tensor:
+        if not audio.is_cuda:
+            raise RadmmmError("Denoiser needs a GPU tensor (there is no CPU path)")
+        if audio.dim() == 3 and audio.shape[1] == 1:
+            audio = audio[:, 0]
+        audio = f32c(audio)
+        B, S = audio.shape
+        n_fft, hop = self.filter_length, self.hop_length
+        dev = audio.device
+        if S <= n_fft // 2:
+            raise ValueError(f"Denoiser: {S} samples cannot be reflect-padded by {n_fft // 2} (needs > {n_fft // 2})")
+        lens_d, host = _lens_arg(lens, B, S, dev)
+        if host is not None:
+            short = [int(v) for v in host if int(v) <= n_fft // 2]
+            if short:
+                raise ValueError(f"Denoiser: items of {short} samples cannot be reflect-padded by {n_fft // 2} "
+                                 f"(the reference's reflect pad needs more than {n_fft // 2} samples: >= 3 mel frames)")
+        elif bool((lens_d <= n_fft // 2).any()):       # device lengths: one synchronisation to validate them
+            raise ValueError(f"Denoiser: every item needs more than {n_fft // 2} samples (>= 3 mel frames)")
+        bias = self._bias(dev)
+        F = 1 + S // hop
+        frames_d = (_to_device(host // hop + 1, dev) if host is not None else lens_d // hop + 1).to(torch.int32)
+        spec = self._spectrum(audio, lens_d, frames_d, F)
+        check(lib.radmmm_voc_spec_bins(ptr(spec), self.ldk, B * F, self.cutoff, ptr(bias), float(strength), None,
+                                       stream()), "voc_spec_bins")
+        G = F - 1
+        Wi = self.inverse_packed
+        y = torch.empty(B, G * hop, device=dev, dtype=torch.float32)
+        rowgemm(A=spec, lda=self.ldk, a_item_stride=F * self.ldk, B=Wi, ldb=self.ldk, b_tap_stride=Wi.stride(0), C=y,
+                ldc=hop, M=B * G, N=hop, K=2 * self.cutoff, taps=Wi.shape[0], dil=1, T=G, lens=frames_d, a_mask_mode=1)
+        check(lib.radmmm_voc_istft_finish(ptr(y), B, G * hop, ptr(frames_d), ptr(self.winsq), n_fft, hop, stream()),
+              "voc_istft_finish")
+        return y.view(B, 1, G * hop)
+
+
+@fp32_region
+def vocode(generator: HiFiGANGenerator, denoiser: Optional[Denoiser], mels: torch.Tensor, out_lens,
+           strength: float = 0.001, normalize: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """mels [B, 80, T] (descaled, as the reference passes them) + lengths in frames -> (audio [B, T*hop] zero padded,
+    sample lengths [B] int64 on the host when out_lens was on the host, else on the device).  get_audio_for_mels
+    (vocoder_utils.py:35-48) for the whole batch: generator, denoiser at `strength`, and with normalize each item
+    scaled by 1 / max|audio| over its own samples."""
+    if not mels.is_cuda:
+        raise RadmmmError("vocode needs GPU tensors (there is no CPU path)")
+    B, _, T = mels.shape
+    dev = mels.device
+    lens_d, host = _lens_arg(out_lens, B, T, dev)
+    hop = generator.hop
+    audio = generator._run(f32c(mels), lens_d)[:, 0]
+    s_lens = host * hop if host is not None else lens_d.long() * hop
+    if denoiser is not None:
+        audio = denoiser(audio, strength, s_lens)[:, 0]
+    audio = audio.contiguous()
+    if normalize:
+        check(lib.radmmm_voc_normalize(ptr(audio), audio.shape[1], ptr(lens_d * hop if host is None else
+                                                                         _to_device(s_lens, dev)),
+                                       B, audio.shape[1], stream()), "voc_normalize")
+    return audio, s_lens
+
+
+def load_hifigan_vocoder(checkpoint_path: str, config_path: str, device: Union[str, torch.device] = "cuda"):
+    """load_hifigan_vocoder of vocoders/vocoder_utils.py:104-132: the config JSON + torch.load(path)['generator'];
+    the Gaussian blur stays off unless the path names it ('blur'), which this package does not support (raises).
+    Returns (generator, denoiser) on `device`, in eval mode."""
+    with open(config_path) as fh:
+        h = json.load(fh)
+    if "blur" in checkpoint_path:
+        h.setdefault("gaussian_blur", {})["p_blurring"] = 0.5
+    else:
+        h.setdefault("gaussian_blur", {})["p_blurring"] = 0.0
+    sd = torch.load(checkpoint_path, map_location="cpu")["generator"]
+    gen = HiFiGANGenerator(h)
+    gen.load_state_dict(sd)
+    gen = gen.to(device).eval()
+    den = Denoiser(gen).to(device).eval()
+    return gen, den

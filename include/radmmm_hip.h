@@ -638,6 +638,38 @@ int radmmm_voc_istft_finish(float* y, int B, int pitch, const int32_t* frames, c
                             radmmm_stream_t stream);
 int radmmm_voc_normalize(float* audio, int lda, const int32_t* lens, int B, int S, radmmm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Batched synthesis glue (TTSModel.sample_full / reconstruct_from_batch_attributes, tts_lightning_modules.py:286-437).
+ * Additive entry points of ABI 4.  No floating-point atomics: every result is bitwise repeatable.
+ *   synth_durations  per token t of utterance b (x[b*item_stride + t], fp32): d = min(max(rint(x), 1), 65536) for
+ *                    t < text_lens[b], else 0 (rint rounds half to even, as torch.round).  integer_mode != 0: d =
+ *                    min(max(x, 0), 65536) truncated, no rounding and no clamp to 1 (durations that are integers already).
+ *                    The cap of 65536 frames per token guards against non-finite or absurd predictions (NaN -> the lower
+ *                    bound); the reference has none.  Writes dur [B][Tt] and its inclusive prefix sum cum [B][Tt] (int32)
+ *                    and out_lens[b] = sum_t dur.  text_lens NULL: every token valid.  Tt <= 32767.
+ *   synth_regulate   LengthRegulator (common.py:208-237) into channels-last frame rows: rows[(b*Tmax + t)*ldc + c] =
+ *                    txt[b*item_stride + j*row_stride + c] for t < out_lens[b], c < C, j the token whose prefix-sum range
+ *                    holds t; zeros elsewhere (frames past out_lens[b], channels C..ldc).  A pure copy.  C, ldc,
+ *                    row_stride, item_stride % 4 == 0, 16-byte aligned txt / rows, Tt <= 16384.
+ *   synth_f0_stats   partials[k*nparts + i], k = count / sum / sum of squares (fp64) of f0 over the frames t < lens[b]
+ *                    with sigmoid(voiced_logit) > 0.5, workgroup i of nparts (1..1024)
+ *   synth_f0_apply   contiguous [B][T] outputs: voiced_out = (t < lens[b] && sigmoid(voiced_logit) > 0.5); f0_out = f0 *
+ *                    voiced, and with partials (from synth_f0_stats) (f0 - mu) / sigma * f0_std[b] + f0_mean[b] on the
+ *                    voiced frames (pooled mean and unbiased std of the whole batch, tts_lightning_modules.py:367-376),
+ *                    left unshifted when fewer than 2 voiced frames exist or sigma == 0; energy_out = energy masked to
+ *                    lens[b]
+ * ------------------------------------------------------------------------------------ */
+int radmmm_synth_durations(const float* x, int64_t item_stride, const int32_t* text_lens, int B, int Tt, int integer_mode,
+                           int32_t* dur, int32_t* cum, int32_t* out_lens, radmmm_stream_t stream);
+int radmmm_synth_regulate(const float* txt, int64_t item_stride, int row_stride, int Tt, int C, const int32_t* cum,
+                          const int32_t* out_lens, int B, int Tmax, float* rows, int ldc, radmmm_stream_t stream);
+int radmmm_synth_f0_stats(const float* f0, int64_t f0_stride, const float* voiced_logit, int64_t v_stride,
+                          const int32_t* lens, int B, int T, double* partials, int nparts, radmmm_stream_t stream);
+int radmmm_synth_f0_apply(const float* f0, int64_t f0_stride, const float* voiced_logit, int64_t v_stride,
+                          const float* energy, int64_t e_stride, const int32_t* lens, int B, int T, const double* partials,
+                          int nparts, const float* f0_mean, const float* f0_std, float* f0_out, float* energy_out,
+                          float* voiced_out, radmmm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -211,6 +211,10 @@ def _load() -> C.CDLL:
         "radmmm_voc_spec_bins": [p, i, i, i, p, f, p, p],
         "radmmm_voc_istft_finish": [p, i, i, p, p, i, i, p],
         "radmmm_voc_normalize": [p, i, p, i, i, p],
+        "radmmm_synth_durations": [p, i64, p, i, i, i, p, p, p, p],
+        "radmmm_synth_regulate": [p, i64, i, i, i, p, p, i, i, p, i, p],
+        "radmmm_synth_f0_stats": [p, i64, p, i64, p, i, i, p, i, p],
+        "radmmm_synth_f0_apply": [p, i64, p, i64, p, i64, p, i, i, p, i, p, p, p, p, p, p],
     }
     missing = [n for n in sig if not hasattr(lib, n)]
     if missing:

@@ -194,13 +194,14 @@ class ConvLSTMLinearDAP(AttributePredictor):
 
 
 @fp32_region
-def dap_forward_many(daps, calls):
+def dap_forward_many(daps, calls, rows=None):
     """[dap(*args, **kwargs) for dap, (args, kwargs) in zip(daps, calls)] for predictors that read the same frames (the f0 /
     energy / voiced predictors of TTSModel.training_step, tts_lightning_modules.py:688-717: three ConvLSTMLinearDAP over
     context.detach() and out_lens): their bi-LSTMs -- same shape, T dependent steps each, latency-bound -- run as ONE
     block-diagonal recurrence (lstm.MergedBiLSTMFn) instead of one after the other; conv stacks and output layers stay per
     predictor.  Same values as the separate calls (the recurrence's fp32 summation order apart); predictors whose LSTMs
-    cannot be merged (other sizes, other lengths) take their own launch."""
+    cannot be merged (other sizes, other lengths) take their own launch.  rows: _rows(context) of the context every call
+    reads, when the caller has it already (synthesis.synth_regulate writes it directly)."""
     from .lstm import can_merge, merged_bilstm
     shared = {}                                            # channels-last copy of a context several predictors read: made once
 
@@ -212,7 +213,7 @@ def dap_forward_many(daps, calls):
         if key not in shared:
             shared[key] = _rows(t)
         return shared[key]
-    pres = [d.forward_pre(*a, **k, rows=rows_of(a[1])) for d, (a, k) in zip(daps, calls)]
+    pres = [d.forward_pre(*a, **k, rows=rows_of(a[1]) if rows is None else rows) for d, (a, k) in zip(daps, calls)]
     lstms = [d.feat_pred_fn.bilstm for d in daps]
     xs = [p[1] for p in pres]
     same_lens = all(c[0][3] is calls[0][0][3] for c in calls)                 # the same SequenceLength object

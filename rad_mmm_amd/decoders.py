@@ -224,43 +224,47 @@ class RADMMMFlow(nn.Module):
                 except (ValueError, AttributeError):
                     pass
 
-    @staticmethod
-    def length_regulator(x, dur):
-        """LengthRegulator.forward (reference common.py:208-237) for the whole batch on the device:
-        x [B, T_txt, C], dur [B, T_txt] (integers) -> [B, max_b sum(dur_b), C]; text frame i is
-        repeated dur[i] times, shorter utterances are zero padded."""
-        B, Tt, C = x.shape
-        dur = dur.long().clamp_min(0)
-        cum = torch.cumsum(dur, 1)
-        total = cum[:, -1]
-        Tmax = int(total.max())
-        t = torch.arange(Tmax, device=x.device)[None, :].expand(B, -1).contiguous()
-        idx = torch.searchsorted(cum, t, right=True).clamp_max(Tt - 1)
-        out = torch.gather(x, 1, idx[:, :, None].expand(-1, -1, C))
-        return out * (t < total[:, None])[:, :, None].to(x.dtype)
-
     @torch.no_grad()
     @fp32_region
     def infer(self, spk_vec, txt_enc, sigma, dur=None, f0=None, energy_avg=None, out_lens=None, accent_vecs=None,
               residual=None):
-        """z -> mel (reference decoders.py:207-248): length-regulate the text encoding, build the
-        context, then run the flows backwards (coupling inverse, inverse 1x1 conv, early-exit
-        channels re-attached) and fold.  `residual` [B, n_mel*g, T'] optionally supplies the noise
-        (already scaled by sigma) instead of sampling it.  Spline flows run the inverse branch of the
-        piecewise-quadratic transform (splines.py:327-339) and need eval() (running batch-norm statistics)."""
-        if self.training and any(f.use_spline for f in self.flows):
-            raise RuntimeError("infer with spline flows needs eval() (masked batch-norm running statistics)")
-        g = self.n_group_size
+        """z -> mel (reference decoders.py:207-248): length-regulate the text encoding (dur [B, T_txt] integer frames per
+        token; csrc/synth.hip, a pure copy), then infer_context.  `residual` [B, n_mel*g, T'] optionally supplies the noise
+        (already scaled by sigma) instead of sampling it.  Limits of the regulation kernels: T_txt <= 16384
+        (raises beyond), and a duration is clamped to [0, 65536] frames per token."""
+        from .synthesis import synth_durations, synth_regulate, rows_as_context
         if out_lens is None:
             out_lens = dur.sum(1)
         out_lens = out_lens.to(txt_enc.device).long()
-        ctx_t = self.length_regulator(txt_enc.transpose(1, 2).float(), dur).transpose(1, 2)
-        sl = SequenceLength(out_lens)
-        cond = self.preprocess_context_cl(ctx_t, spk_vec.float(), sl, f0, energy_avg, accent_vecs)
+        x = txt_enc.transpose(1, 2)                                    # [B, T_txt, C]
+        B, _, C = x.shape
+        _, cum, total = synth_durations(dur.to(txt_enc.device).float(), None, integer_mode=True)
+        rows = synth_regulate(x, cum, total, int(total.max()))
+        return self.infer_context(spk_vec, rows_as_context(rows, B, C), out_lens, sigma, f0, energy_avg, accent_vecs,
+                                  residual)
+
+    @torch.no_grad()
+    @fp32_region
+    def infer_context(self, spk_vec, context, out_lens, sigma, f0=None, energy_avg=None, accent_vecs=None, residual=None):
+        """infer from the frame-rate context [B, C, T] (may be a strided view, e.g. of synthesis.synth_regulate's rows):
+        build the decoder's conditioning, then run the flows backwards (coupling inverse, inverse 1x1 conv, early-exit
+        channels re-attached) and fold.  out_lens: [B] frames or a SequenceLength (its host copy saves a device read).
+        Spline flows run the inverse branch of the piecewise-quadratic transform (splines.py:327-339) and need eval()
+        (running batch-norm statistics)."""
+        if self.training and any(f.use_spline for f in self.flows):
+            raise RuntimeError("infer with spline flows needs eval() (masked batch-norm running statistics)")
+        g = self.n_group_size
+        if isinstance(out_lens, SequenceLength):
+            sl = out_lens
+            out_lens = sl.lengths.to(context.device)
+        else:
+            out_lens = out_lens.to(context.device).long()
+            sl = SequenceLength(out_lens)
+        cond = self.preprocess_context_cl(context, spk_vec.float(), sl, f0, energy_avg, accent_vecs)
         B, Tg, D = cond.shape
         C0 = self.n_mel_channels * g
         if residual is None:
-            residual = torch.randn(B, C0, Tg, device=txt_enc.device) * sigma
+            residual = torch.randn(B, C0, Tg, device=context.device) * sigma
         r = residual.float().transpose(1, 2).reshape(B * Tg, C0)
         cond2 = cond.reshape(B * Tg, D)
         lens32 = torch.div(out_lens, g, rounding_mode="floor").to(torch.int32)

@@ -64,6 +64,11 @@ class TTSTrainingStep(nn.Module):
     def mel_scale(mel):
         return (mel + 5) / 2
 
+    @staticmethod
+    def mel_descale(mel):
+        """tts_lightning_modules.py:547-549"""
+        return mel * 2 - 5
+
     def encode_speaker(self, spk_ids):
         return self.speaker_embeddings(spk_ids)
 
@@ -247,3 +252,15 @@ class TTSTrainingStep(nn.Module):
         audio = audio.cpu().numpy()
         s_lens = s_lens.cpu().tolist()
         return [audio[b, :s_lens[b]].copy() for b in range(len(s_lens))]
+
+    # ---- synthesis (tts_lightning_modules.py:286-437): rad_mmm_amd/synthesis.py -----------------------------------------
+    def sample_full(self, text, text_lengths, speaker_ids, **kwargs):
+        """token ids [B, L] -> mel and waveforms for the whole batch (synthesis.sample_full)"""
+        from .synthesis import sample_full
+        return sample_full(self, text, text_lengths, speaker_ids, **kwargs)
+
+    def reconstruct_from_batch_attributes(self, batch, durations=None, vocode=True, residual=None):
+        """the batch's mel rebuilt from its text, speaker, f0, energy and alignment durations
+        (synthesis.reconstruct_from_batch_attributes)"""
+        from .synthesis import reconstruct_from_batch_attributes
+        return reconstruct_from_batch_attributes(self, batch, durations=durations, vocode=vocode, residual=residual)

@@ -670,6 +670,44 @@ int radmmm_synth_f0_apply(const float* f0, int64_t f0_stride, const float* voice
                           int nparts, const float* f0_mean, const float* f0_std, float* f0_out, float* energy_out,
                           float* voiced_out, radmmm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Training batches built on the device (data.py:419-610 AudioDataset.__getitem__ after the file reads, :616-790
+ * DataCollate): ragged utterances packed back to back in one staging buffer -> the padded tensors of a batch.
+ * offsets are int64 DEVICE arrays [B] in elements of the packed array, lens / frames / in_lens int32 device arrays [B].
+ *   collate_scratch_floats  size of `scratch` (the layout of radmmm_stft_mel at S = Smax; the reflect-padded rows
+ *                    xpad [B][pitch], pitch = roundup4(Smax + n_fft), sit at its start)
+ *   collate_unpack_pad  xpad[b][p] = src[offsets[b] + reflect(p - n_fft/2)] * scale inside [0, lens[b]) for
+ *                    p < lens[b] + n_fft, 0 beyond.  src: int16 (src_int16 != 0) or fp32 samples.  audio != NULL:
+ *                    audio[b][j] = src[offsets[b] + j] * scale for j < lens[b], 0 for lens[b] <= j < Smax, in the same
+ *                    pass.  Caller guarantees n_fft/2 < lens[b] <= Smax.  Offsets that are multiples of 4 let the
+ *                    interior go through 8 / 16-byte loads.
+ *   collate_mel      the two row GEMMs of radmmm_stft_mel over B*Tmax rows (Tmax = 1 + Smax/hop) of the xpad that
+ *                    collate_unpack_pad left in `scratch`, then mel[b][c][t] = log(max(., clip)) for t < frames[b], 0
+ *                    beyond, and (energy != NULL) energy[b][t] = mean_c mel[b][c][t], (x + 20) / 20 when scaled, 0 beyond
+ *                    -- the sums in the order of radmmm_energy_average.  mel [B][n_mel][Tmax], energy [B][Tmax].
+ *   collate_tracks   one workgroup per utterance: f0[b][t] = f0_normalize(f0_packed[frame_offsets[b] + t])
+ *                    (use_log_f0: x >= f0_min ? log(x) : 0, data.py:321-327) and, with distance_tx, minus max(log d, 0),
+ *                    d the distance in frames to the nearest frame of the utterance with f0 > 0 (data.py:527-532: the 1-D
+ *                    scipy.ndimage.distance_transform_edt(f0 <= 0); without any such frame d = t + 1, as scipy returns); log
+ *                    and subtraction in double, rounded once.  p_voiced / voiced_mask copied; all three zero for frames[b]
+ *                    <= t < Tmax.  text[b][l] = ids_packed[token_offsets[b] + l] for l < in_lens[b], else 0 (int64
+ *                    [B][Lmax]).  meta_dst[0..n_meta) = meta_src[0..n_meta) (8-byte words: the per-item scalars of the
+ *                    batch).  Any of the three tracks, text and meta may be NULL / 0.  scan: int32 [B][Tmax] scratch,
+ *                    needed with f0 and distance_tx.  No cap on Tmax.
+ * ------------------------------------------------------------------------------------ */
+int64_t radmmm_collate_scratch_floats(int B, int Smax, int n_fft, int hop, int n_mel);
+int radmmm_collate_unpack_pad(const void* src, int src_int16, const int64_t* offsets, const int32_t* lens,
+                              float* scratch, float* audio, int B, int Smax, int n_fft, float scale,
+                              radmmm_stream_t stream);
+int radmmm_collate_mel(const float* basis, const float* mel_basis, const int32_t* frames, float* mel, float* energy,
+                       float* scratch, int B, int Smax, int n_fft, int hop, int n_mel, float clip, int scaled,
+                       radmmm_stream_t stream);
+int radmmm_collate_tracks(const float* f0_packed, const float* p_voiced_packed, const float* voiced_mask_packed,
+                          const int32_t* ids_packed, const int64_t* frame_offsets, const int64_t* token_offsets,
+                          const int32_t* frames, const int32_t* in_lens, float* f0, float* p_voiced, float* voiced_mask,
+                          int64_t* text, int32_t* scan, const int64_t* meta_src, int64_t* meta_dst, int n_meta, int B,
+                          int Tmax, int Lmax, float f0_min, int use_log_f0, int distance_tx, radmmm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -215,6 +215,9 @@ def _load() -> C.CDLL:
         "radmmm_synth_regulate": [p, i64, i, i, i, p, p, i, i, p, i, p],
         "radmmm_synth_f0_stats": [p, i64, p, i64, p, i, i, p, i, p],
         "radmmm_synth_f0_apply": [p, i64, p, i64, p, i64, p, i, i, p, i, p, p, p, p, p, p],
+        "radmmm_collate_unpack_pad": [p, i, p, p, p, p, i, i, i, f, p],
+        "radmmm_collate_mel": [p, p, p, p, p, p, i, i, i, i, i, f, i, p],
+        "radmmm_collate_tracks": [p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, f, i, i, p],
     }
     missing = [n for n in sig if not hasattr(lib, n)]
     if missing:
@@ -228,6 +231,7 @@ def _load() -> C.CDLL:
                        "radmmm_mas_scratch_bytes": [i, i, i], "radmmm_ctc_monotonic_scratch_floats": [i, i, i],
                        "radmmm_film_bwd_scratch_floats": [i, i],
                        "radmmm_stft_mel_scratch_floats": [i, i, i, i, i],
+                       "radmmm_collate_scratch_floats": [i, i, i, i, i],
                        "radmmm_lstm_scratch_bytes": [i, i, i], "radmmm_lstm_hseq_bytes": [i, i, i],
                        "radmmm_sumsq_scratch_floats": []}.items():
         fn = getattr(lib, name)

@@ -14,7 +14,7 @@ import torch
 from torch import nn
 
 from . import ops
-from ._lib import fp32_region
+from ._lib import fp32_region, lib, check, ptr, stream
 
 
 def _hann_periodic(n: int) -> np.ndarray:
@@ -91,3 +91,57 @@ class TacotronSTFT(nn.Module):
         assert float(y.min()) >= -1 and float(y.max()) <= 1
         s = self.stft_fn
         return ops.stft_mel(y.float(), s.forward_basis, self.mel_basis, s.filter_length, s.hop_length, 1e-5)
+
+    @fp32_region
+    def mel_spectrogram_ragged(self, y: torch.Tensor, lens, out: torch.Tensor = None, *, lens_device: torch.Tensor = None,
+                               frames_device: torch.Tensor = None, offsets: torch.Tensor = None, scale: float = 1.0,
+                               energy: torch.Tensor = None, scaled_energy: bool = True, audio_out: torch.Tensor = None,
+                               scratch: torch.Tensor = None) -> torch.Tensor:
+        """Log-mel of utterances of different lengths in one call: [B, n_mel, Tmax], Tmax = 1 + max(lens) // hop, row b
+        holding the 1 + lens[b] // hop frames `mel_spectrogram` gives for that utterance alone (each reflect-padded at its
+        own two ends) and exact zeros after them.  No range assert and no synchronisation.
+
+        y: [B, Smax] float in [-1, 1] on the device; or, with `offsets` (int64 device tensor [B], first sample of each item),
+        a packed 1-D int16 / float32 buffer, multiplied by `scale`.  lens: HOST sample counts (sequence or CPU tensor), each
+        > filter_length // 2; lens_device / frames_device: the same counts and 1 + lens // hop as int32 device tensors when the
+        caller has them (else they are uploaded through pinned memory).  energy [B, Tmax], audio_out [B, 1, Smax]: filled
+        in the same pass when given (data.get_energy_average of the rows; the scaled, zero-padded samples).  scratch: fp32
+        device buffer of radmmm_collate_scratch_floats elements to reuse."""
+        if not y.is_cuda:
+            raise RuntimeError("rad_mmm_amd.audio_processing runs on an MI355X only (no CPU path)")
+        s = self.stft_fn
+        n_fft, hop, n_mel = s.filter_length, s.hop_length, self.n_mel_channels
+        lens_host = torch.as_tensor(lens, dtype=torch.int64, device="cpu")
+        B = int(lens_host.numel())
+        Smax = int(lens_host.max())
+        if int(lens_host.min()) <= n_fft // 2:
+            raise ValueError(f"mel_spectrogram_ragged: every utterance needs more than filter_length // 2 = {n_fft // 2} samples")
+        if offsets is None:
+            if y.dim() != 2 or y.shape[0] != B or y.shape[1] < Smax:
+                raise ValueError("mel_spectrogram_ragged: y must be [B, S] with S >= max(lens) (or packed, with offsets)")
+            y = y.float().contiguous()
+            offsets = torch.arange(B, device=y.device, dtype=torch.int64) * y.shape[1]
+        elif y.dim() != 1 or y.dtype not in (torch.int16, torch.float32) or not y.is_contiguous():
+            raise ValueError("mel_spectrogram_ragged: a packed buffer is 1-D contiguous int16 or float32")
+        if lens_device is None:
+            lens_device = lens_host.to(torch.int32).pin_memory().to(y.device, non_blocking=True)
+        if frames_device is None:
+            frames_device = torch.div(lens_device, hop, rounding_mode="floor").to(torch.int32) + 1
+        Tmax = 1 + Smax // hop
+        if out is None:
+            out = torch.empty(B, n_mel, Tmax, device=y.device, dtype=torch.float32)
+        elif tuple(out.shape) != (B, n_mel, Tmax) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"mel_spectrogram_ragged: out must be contiguous fp32 [{B}, {n_mel}, {Tmax}]")
+        for name, t, shape in (("energy", energy, (B, Tmax)), ("audio_out", audio_out, (B, 1, Smax))):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError(f"mel_spectrogram_ragged: {name} must be contiguous fp32 {list(shape)}")
+        need = int(lib.radmmm_collate_scratch_floats(B, Smax, n_fft, hop, n_mel))
+        if scratch is None or scratch.numel() < need:
+            scratch = torch.empty(need, device=y.device, dtype=torch.float32)
+        check(lib.radmmm_collate_unpack_pad(ptr(y), 1 if y.dtype == torch.int16 else 0, ptr(offsets), ptr(lens_device),
+                                            ptr(scratch), ptr(audio_out), B, Smax, n_fft, float(scale), stream()),
+              "collate_unpack_pad")
+        check(lib.radmmm_collate_mel(ptr(s.forward_basis), ptr(self.mel_basis), ptr(frames_device), ptr(out), ptr(energy),
+                                     ptr(scratch), B, Smax, n_fft, hop, n_mel, 1e-5, 1 if scaled_energy else 0, stream()),
+              "collate_mel")
+        return out

@@ -338,6 +338,9 @@ int radmmm_pq_spline_bwd(const float* x, int ldx, const float* q, int ldq, const
  * mean/invstd are the caller's masked statistics (radmmm_colsum with square = 0/1).
  * backward: gout -> gh2, gc1 [rows, 2C], gx1r, and dL/dw, dL/db of the batch-norm affine;
  * n_valid = number of unmasked frames; scratch: radmmm_film_bwd_scratch_floats(rows, C).
+ * radmmm_film_bwd's use_bn: 0 = no batch-norm, 1 = mean/invstd are the masked statistics of this h2 (training mode: gh2
+ * carries their derivatives), 2 = mean/invstd are constants (eval mode, running statistics: gh2 = invstd * w * g_y;
+ * dL/dw, dL/db are the same column sums in both).
  * ------------------------------------------------------------------------------------ */
 int radmmm_film_fwd(const float* h2, int ldh, const float* c1, int ldc, const float* x1r, int ldx,
                     const float* mean, const float* invstd, const float* w, const float* b,

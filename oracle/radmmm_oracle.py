@@ -332,39 +332,46 @@ def masked_batchnorm1d(p: Params, prefix: str, x: Tensor, mask: Tensor, training
 
 
 def film_stack_forward(p: Params, prefix: str, x: Tensor, ctx: Tensor, mask: Tensor, n_layers: int,
-                       use_bn: bool, training: bool = True, record: Optional[Dict] = None) -> Tensor:
+                       use_bn: bool, training: bool = True, record: Optional[Dict] = None,
+                       gates: Optional[Dict] = None) -> Tensor:
     """FiLMStack / FiLMResBlock.  common.py:706-773.  record (test accounting): "leaky_near_zero" / "leaky_total" count the
     leaky-ReLU pre-activations (valid frames) within 2e-5 of their tensor's rms of the kink at 0 -- another implementation's
-    rounding may put those on the other side, which changes the slope its gradient sees from 1 to 0.01."""
-    def count(pre):
+    rounding may put those on the other side, which changes the slope its gradient sees from 1 to 0.01.  A record that holds
+    the key "pre" (a dict) also receives there the two pre-activations of block i, [B, C, T], under (i, "x1") and (i, "t")
+    (opt-in: 2 x n_layers activation-sized tensors); `gates` (same keys, bool; not reference behaviour) overrides the
+    decision pre > 0 of that leaky ReLU and of its derivative, as dap_forward's `gates` does."""
+    def leaky(pre, key):
         if record is not None:
             with torch.no_grad():
                 v = mask.expand_as(pre) > 0
                 rms = float(pre[v].pow(2).mean().sqrt())
                 record["leaky_near_zero"] = record.get("leaky_near_zero", 0) + int(((pre.abs() < 2e-5 * rms) & v).sum())
                 record["leaky_total"] = record.get("leaky_total", 0) + int(v.sum())
+                if "pre" in record:
+                    record["pre"][key] = pre.detach()
+        return F.leaky_relu(pre) if gates is None else torch.where(gates[key], pre, 0.01 * pre)
     for i in range(n_layers):
         q = f"{prefix}in_layers.{i}."
         x1 = conv_norm(p, q + "input_conv.", x, mask, 1)
         c1 = conv_norm(p, q + "cond_conv.", ctx, mask, 1)
         n_out = x1.shape[1]
         scale, bias = c1[:, :n_out] + 1, c1[:, n_out:]
-        count(x1)
-        x1r = F.leaky_relu(x1)
+        x1r = leaky(x1, (i, "x1"))
         x2 = conv_norm(p, q + "hidden_conv.", x1r, mask, 2 ** i)
         if use_bn:
             x2 = masked_batchnorm1d(p, q + "bn.", x2, mask, training)
-        count(x2 * scale + bias)
-        x2 = F.leaky_relu(x2 * scale + bias)
+        x2 = leaky(x2 * scale + bias, (i, "t"))
         x = 0.5 * (x2 + x1r)
     return F.conv1d(x, p[prefix + "end.weight"], p[prefix + "end.bias"])
 
 
 def spline_coupling_forward(p: Params, prefix: str, z: Tensor, ctx: Tensor, mask: Tensor,
                             n_layers: int, n_bins: int = 32, bound: float = 3.0,
-                            use_bn: bool = True, training: bool = True, record: Optional[Dict] = None) -> Tuple[Tensor, Tensor]:
+                            use_bn: bool = True, training: bool = True, record: Optional[Dict] = None,
+                            gates: Optional[Dict] = None) -> Tuple[Tensor, Tensor]:
     """SplineTransformationLayer.forward, use_quadratic=True.  common.py:1040-1090
     (left=bottom=-bound, right=top=bound as wired by decoders.py:51-61).
+    gates (test accounting): film_stack_forward's; a record with "ulps" or "pre" is handed to it as well.
     record (test accounting, not reference behaviour): receives "x" [B*T, h] (the transform's argument in [0, 1)) and
     "edges" [B*T, h, K] (the bin edges the search runs on) -- an element within an ulp of an edge may take the
     neighbouring bin in another implementation; the transform is continuous there, its parameter gradient is not."""
@@ -373,7 +380,7 @@ def spline_coupling_forward(p: Params, prefix: str, z: Tensor, ctx: Tensor, mask
     z0, z1 = z[:, :h], z[:, h:]
     z1n = (z1 + bound) / (2 * bound)
     q = film_stack_forward(p, prefix + "param_predictor.", z0, ctx, mask, n_layers, use_bn, training,
-                           record if (record is not None and "ulps" in record) else None)
+                           record if (record is not None and ("ulps" in record or "pre" in record)) else None, gates)
     nb = 2 * n_bins + 1
     x = z1n.permute(0, 2, 1).reshape(B * T, h)
     qt = q.permute(0, 2, 1).reshape(B * T, h, nb)

@@ -6,6 +6,9 @@
 // and its gradient.  HBM-bound elementwise work on [rows, C] fp32 matrices; the two column
 // reductions the batch-norm gradient needs (sum g_y, sum g_y * xhat) are produced by a partial
 // kernel (float4 columns, 64-row chunks) + a final add, deterministic.
+// use_bn of the backward: 1 = mean / invstd are the masked statistics of THIS h2 (training mode: the gradient carries
+// their derivatives, the -(S1 + xhat * S2) / n terms), 2 = they are constants (eval mode, running statistics,
+// maskedbatchnorm1d.py:110-118: dL/dh = invstd * w * g_y; dL/dw, dL/db are the same sums either way).
 #include "common.h"
 
 extern "C" int radmmm_colsum_final(const float* part, float* out, int nparts, int cols, radmmm_stream_t stream);
@@ -16,6 +19,17 @@ constexpr int FR = 64;  // rows per reduction block
 
 __device__ __forceinline__ float leaky(float x) { return x > 0.f ? x : 0.01f * x; }
 
+// y and the pre-activation t of one element, in ONE fixed sequence of roundings.  The forward kernel, the reduce kernel
+// and the apply kernel each decide t > 0 for themselves; spelled as plain expressions the compiler contracted them
+// differently per kernel, and an element within rounding of the kink got slope 1 in one kernel and 0.01 in another (the
+// column sums S, dL/dw, dL/db then belonged to other decisions than gh2 / gc1: tests/test_hip_film.py).
+__device__ __forceinline__ float film_t(float h, float ca, float cb, float mean, float invstd, float w, float b,
+                                        int use_bn, float& xhat, float& y) {
+  xhat = use_bn ? __fmul_rn(__fsub_rn(h, mean), invstd) : h;
+  y = use_bn ? __fmaf_rn(xhat, w, b) : h;
+  return __fmaf_rn(y, __fadd_rn(ca, 1.f), cb);
+}
+
 __global__ __launch_bounds__(256) void film_fwd_kernel(
     const float* __restrict__ h2, int ldh, const float* __restrict__ c1, int ldc, const float* __restrict__ x1r,
     int ldx, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ w,
@@ -24,9 +38,11 @@ __global__ __launch_bounds__(256) void film_fwd_kernel(
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
        i += (long long)gridDim.x * blockDim.x) {
     const int r = (int)(i / C), c = (int)(i - (long long)r * C);
-    float y = h2[(long long)r * ldh + c];
-    if (use_bn) y = (y - mean[c]) * invstd[c] * w[c] + b[c];
-    const float t = y * (c1[(long long)r * ldc + c] + 1.f) + c1[(long long)r * ldc + C + c];
+    const float m = use_bn ? mean[c] : 0.f, is = use_bn ? invstd[c] : 1.f;
+    const float ww = use_bn ? w[c] : 1.f, bb = use_bn ? b[c] : 0.f;
+    float xhat, y;
+    const float t = film_t(h2[(long long)r * ldh + c], c1[(long long)r * ldc + c], c1[(long long)r * ldc + C + c], m, is, ww,
+                           bb, use_bn, xhat, y);
     out[(long long)r * ldo + c] = 0.5f * (leaky(t) + x1r[(long long)r * ldx + c]);
   }
 }
@@ -34,11 +50,9 @@ __global__ __launch_bounds__(256) void film_fwd_kernel(
 // g_y for one element (and xhat / y as by-products)
 __device__ __forceinline__ float film_gy(float h, float ca, float cb, float go, float mean, float invstd,
                                          float w, float b, int use_bn, float& xhat, float& y, float& gt) {
-  xhat = use_bn ? (h - mean) * invstd : h;
-  y = use_bn ? xhat * w + b : h;
-  const float t = y * (ca + 1.f) + cb;
+  const float t = film_t(h, ca, cb, mean, invstd, w, b, use_bn, xhat, y);
   gt = 0.5f * go * (t > 0.f ? 1.f : 0.01f);
-  return gt * (ca + 1.f);
+  return __fmul_rn(gt, __fadd_rn(ca, 1.f));
 }
 
 __global__ __launch_bounds__(256) void film_bwd_reduce_kernel(
@@ -84,11 +98,13 @@ __global__ __launch_bounds__(256) void film_bwd_apply_kernel(
     gc1[(long long)r * ldgc + C + c] = gt;
     gx1r[(long long)r * ldgx + c] = 0.5f * go;
     float g = gy;
-    if (use_bn) {
+    if (use_bn == 1) {
       // dL/dh = invstd * w * gy + mask/n * ( -invstd * w * S1 - invstd * w * xhat * S2 )
       const int bi = r / T, t = r - bi * T;
       const float mk = t < (lens ? lens[bi] : T) ? 1.f : 0.f;
       g = is * ww * (gy - mk * inv_n * (S[c] + xhat * S[C + c]));
+    } else if (use_bn) {
+      g = is * ww * gy;  // constant statistics
     }
     gh2[(long long)r * ldgh + c] = g;
   }
@@ -169,8 +185,8 @@ extern "C" int radmmm_film_bwd(const float* h2, int ldh, const float* c1, int ld
   RADMMM_REQUIRE(h2 && c1 && gout && gh2 && gc1 && gx1r && scratch, "film_bwd: null pointer");
   RADMMM_REQUIRE(!use_bn || (mean && invstd && w && b && gw && gb && n_valid > 0 && T > 0 && rows % T == 0),
                  "film_bwd: batch-norm operands missing");
-  RADMMM_REQUIRE(rows > 0 && C > 0 && ldh >= C && ldc >= 2 * C && ldg >= C && ldgh >= C && ldgc >= 2 * C && ldgx >= C,
-                 "film_bwd: bad dims");
+  RADMMM_REQUIRE(rows > 0 && C > 0 && ldh >= C && ldc >= 2 * C && ldg >= C && ldgh >= C && ldgc >= 2 * C && ldgx >= C &&
+                     use_bn >= 0 && use_bn <= 2, "film_bwd: bad dims");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nparts = (rows + FR - 1) / FR;
   float* S = scratch + (long long)nparts * 2 * C;
@@ -188,7 +204,7 @@ extern "C" int radmmm_film_bwd(const float* h2, int ldh, const float* c1, int ld
     }
   }
   hipLaunchKernelGGL(film_bwd_apply_kernel, dim3(grid_for((long long)rows * C)), dim3(256), 0, s, h2, ldh, c1, ldc,
-                     gout, ldg, mean, invstd, w, b, S, use_bn ? 1.f / n_valid : 0.f, T > 0 ? T : 1, lens, gh2, ldgh, gc1,
+                     gout, ldg, mean, invstd, w, b, S, use_bn == 1 ? 1.f / n_valid : 0.f, T > 0 ? T : 1, lens, gh2, ldgh, gc1,
                      ldgc, gx1r, ldgx, rows, C, use_bn);
   return radmmm::check_launch("film_bwd");
 }

@@ -57,9 +57,11 @@ class FiLMPostFn(torch.autograd.Function):
 
     @staticmethod
     @amp_fwd
-    def forward(ctx, h2, c1, x1r, bn_w, bn_b, mean, invstd, lens, T, n_valid, use_bn, sync_group=False):
+    def forward(ctx, h2, c1, x1r, bn_w, bn_b, mean, invstd, lens, T, n_valid, use_bn, sync_group=False, batch_stats=True):
         """sync_group: False = local statistics; None or a process group = synchronised statistics (mean / invstd /
-        n_valid are then the GLOBAL ones and backward all-reduces its two gradient sums over that group)."""
+        n_valid are then the GLOBAL ones and backward all-reduces its two gradient sums over that group).
+        batch_stats: mean / invstd are the masked statistics of this h2 (training mode), so the gradient of h2 carries their
+        derivatives; False = they are constants (running statistics in eval mode, maskedbatchnorm1d.py:110-118)."""
         rows, C = h2.shape[0], x1r.shape[1]
         out = torch.empty(rows, C, device=h2.device, dtype=torch.float32)
         check(lib.radmmm_film_fwd(ptr(h2), h2.shape[1], ptr(c1), c1.shape[1], ptr(x1r), x1r.shape[1], ptr(mean),
@@ -67,7 +69,7 @@ class FiLMPostFn(torch.autograd.Function):
                                   stream()), "film_fwd")
         ctx.save_for_backward(h2, c1, bn_w if use_bn else h2, bn_b if use_bn else h2, mean if use_bn else h2,
                               invstd if use_bn else h2, lens if lens is not None else h2)
-        ctx.meta = (T, float(n_valid), use_bn, lens is not None, C)
+        ctx.meta = (T, float(n_valid), (1 if batch_stats else 2) if use_bn else 0, lens is not None, C)
         ctx.sync_group = sync_group
         return out
 
@@ -85,7 +87,7 @@ class FiLMPostFn(torch.autograd.Function):
         gb = torch.empty(C, device=h2.device) if use_bn else None
         nscr = int(lib.radmmm_film_bwd_scratch_floats(rows, C))
         scratch = torch.empty(nscr, device=h2.device)
-        if use_bn and ctx.sync_group is not False:
+        if use_bn == 1 and ctx.sync_group is not False:
             import torch.distributed as dist
             check(lib.radmmm_film_bwd_sums(ptr(h2), h2.shape[1], ptr(c1), c1.shape[1], ptr(gout), gout.shape[1], ptr(mean),
                                            ptr(invstd), ptr(bn_w), ptr(bn_b), ptr(gw), ptr(gb), ptr(scratch), rows, C,
@@ -95,14 +97,13 @@ class FiLMPostFn(torch.autograd.Function):
                                             ptr(invstd), ptr(bn_w), ptr(bn_b), n_valid, T, ptr(lens) if has_lens else None,
                                             ptr(gh2), gh2.shape[1], ptr(gc1), gc1.shape[1], ptr(gx1r), C, ptr(scratch), rows,
                                             C, stream()), "film_bwd_apply")
-            return gh2, gc1, gx1r, gw, gb, None, None, None, None, None, None, None
+            return gh2, gc1, gx1r, gw, gb, None, None, None, None, None, None, None, None
         check(lib.radmmm_film_bwd(ptr(h2), h2.shape[1], ptr(c1), c1.shape[1], ptr(gout), gout.shape[1],
                                   ptr(mean) if use_bn else None, ptr(invstd) if use_bn else None,
                                   ptr(bn_w) if use_bn else None, ptr(bn_b) if use_bn else None, n_valid, T,
                                   ptr(lens) if has_lens else None, ptr(gh2), gh2.shape[1], ptr(gc1), gc1.shape[1],
-                                  ptr(gx1r), C, ptr(gw), ptr(gb), ptr(scratch), rows, C, 1 if use_bn else 0,
-                                  stream()), "film_bwd")
-        return gh2, gc1, gx1r, gw, gb, None, None, None, None, None, None, None
+                                  ptr(gx1r), C, ptr(gw), ptr(gb), ptr(scratch), rows, C, use_bn, stream()), "film_bwd")
+        return gh2, gc1, gx1r, gw, gb, None, None, None, None, None, None, None, None
 
 
 class FiLMResBlock(nn.Module):
@@ -128,9 +129,10 @@ class FiLMResBlock(nn.Module):
         C = self.out_channels
         mean = invstd = None
         sync_group = False
+        batch_stats = bool(self.use_bn and self.training and n_valid > 1)
         if self.use_bn:
             bn = self.bn
-            if self.training and n_valid > 1:
+            if batch_stats:
                 with torch.no_grad():
                     s1 = ops.colsum(h2, C, 1, T, lens32)
                     s2 = ops.colsum(h2, C, 1, T, lens32, square=True)
@@ -151,12 +153,12 @@ class FiLMResBlock(nn.Module):
                     bn.running_var.mul_(1 - f).add_(f * var * n_valid / (n_valid - 1))
             else:
                 # eval mode (maskedbatchnorm1d.py:110-118): running statistics, no update; the fused kernel
-                # takes mean / invstd as inputs, so only their source changes (inference path: no autograd
-                # through the statistics is needed)
+                # takes mean / invstd as inputs, so only their source changes -- and, in backward, that they are
+                # constants (a frozen decoder under a training predictor still passes gradients through here)
                 mean = bn.running_mean
                 invstd = torch.rsqrt(bn.running_var + bn.eps)
         return FiLMPostFn.apply(h2, c1, x1r, bn.weight if self.use_bn else None, bn.bias if self.use_bn else None,
-                                mean, invstd, lens32, T, n_valid, self.use_bn, sync_group)
+                                mean, invstd, lens32, T, n_valid, self.use_bn, sync_group, batch_stats)
 
 
 class FiLMStack(nn.Module):

@@ -553,7 +553,9 @@ int radmmm_wgrad_rm8(const void* GYh, const void* GYx, int ldg, int g8_exp, cons
  *   which = 0 wsplit, 1 hsplit (fwd), 2 wtpack, 3 P, 4 dcbuf (bwd).
  * radmmm_lstm_bwd overwrites G with the pre-activation gradients dG; the input / weight / bias
  * gradients are plain GEMMs of dG (dW_ih = dG^T x, dx = dG W_ih, db = colsum dG, dW_hh[d] = dG_d^T h_prev).
- * gscale: device scalar, power of two bringing dG into fp16 range (e.g. 2^floor(log2(64 / max|dy|))).
+ * gscale: ignored, may be NULL.  (Until this revision of ABI 4 it was a device scalar that brought dG into fp16 range;
+ * the kernel now gives every batch row of its fp16 operand its own power-of-two scale per step, so no gradient range or
+ * growth along the recurrence is clamped.  The parameter stays so that existing callers keep working.)
  * All T steps run in ONE launch when the grid (ceil(H/8) x 2 x ceil(B/32) workgroups) fits one workgroup per CU: the
  * workgroups hand h / the partial recurrent gradients from step to step through memory, the data being its own ready
  * flag (csrc/lstm.hip).  The forward pass then needs hseq, radmmm_lstm_hseq_bytes(B, T, H) bytes of scratch (one operand
@@ -564,6 +566,10 @@ int radmmm_lstm_fwd(float* G, const float* W_hh, float* y, float* c, const int32
                     void* hseq, int B, int T, int H, radmmm_stream_t stream);
 int radmmm_lstm_bwd(float* G, const float* c, const float* dy, const float* W_hh, const int32_t* lens, void* wtpack,
                     float* P, float* dcbuf, int B, int T, int H, const float* gscale, radmmm_stream_t stream);
+/* Additive entry point of ABI 4, read-only: the form the calling thread's last radmmm_lstm_fwd (which = 0) /
+ * radmmm_lstm_bwd (which = 1) ran in -- 1 = one launch per step, 2 = single cooperative launch, 0 = no call yet.  It is
+ * recorded where the launch decision is made, including a refused cooperative launch that falls through to per-step. */
+int radmmm_lstm_last_path(int which);
 
 /* Channel-mix matrix of the LUS invertible 1x1 conv (common.py:507-548, Invertible1x1ConvLUS.forward's
  * W = P (L U) with L = tril(lower,-1) + diag(lower_diag), U = triu(upper,1) + diag(upper_diag), and

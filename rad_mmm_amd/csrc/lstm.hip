@@ -57,7 +57,6 @@ struct LstmArgs {
   float* P;                     // [2 dirs][2 ping-pong][Bp/32][Hp/8 consumer slices][NS producer slices][32][8] partial recurrent gradients
   float* dcbuf;                 // [2][Bp][H] carried cell gradient
   int Hp, NS;                   // Hp = H rounded up to 32, NS = ceil(H / 8)
-  const float* gscale;          // device scalar: power-of-two scale applied to dG before the fp16 split
   int probe;                    // persistent kernels: poll ONE word until it is written before loading (and checking) everything
 };
 
@@ -158,6 +157,17 @@ __device__ __forceinline__ void spin_wait(unsigned& spins, unsigned long long& t
 }
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// max over the 8 lanes that hold one batch row's units of a slice (lanes 8r .. 8r + 7): two quad permutes and a mirror of
+// the half row, no LDS
+template <int CTRL>
+__device__ __forceinline__ float dpp_max(float v) {
+  return fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false)));
+}
+__device__ __forceinline__ float max8(float v) {
+  v = dpp_max<0xB1>(v);          // quad_perm [1, 0, 3, 2]
+  v = dpp_max<0x4E>(v);          // quad_perm [2, 3, 0, 1]
+  return dpp_max<0x141>(v);      // row_half_mirror: lane i <-> 7 - i of every 8
+}
 __device__ __forceinline__ unsigned is_fill(const f16x8& f) {
   const u32x4 v = __builtin_bit_cast(u32x4, f);
   return (unsigned)(v.x == FILL) | (unsigned)(v.y == FILL) | (unsigned)(v.z == FILL) | (unsigned)(v.w == FILL);
@@ -331,6 +341,7 @@ template <bool PERSIST, int NSC, int NT>
 __global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmArgs a, const int s0) {
   // [batch][k' (32) + pad]; two copies in the persistent kernel (a fast wave may be one step ahead)
   __shared__ __attribute__((aligned(16))) _Float16 sAh2[PERSIST ? 2 : 1][32][40], sAl2[PERSIST ? 2 : 1][32][40];
+  __shared__ float sInv2[PERSIST ? 2 : 1][32];                   // 1 / (this step's scale of batch row b), see below
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = blockIdx.x, d = blockIdx.y, bz = blockIdx.z, bb = bz * 32;
@@ -359,8 +370,6 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmArgs a, const i
       }
     }
   }
-  const float gsc = a.gscale[0];
-  const float inv = 1.f / gsc;
   // partial recurrent gradients [dir][ping-pong][batch block] x [consumer slice][producer slice][32][8]
   const long long slot_floats = (long long)NS * 32 * Hp;
   const float* Pg = a.P + ((long long)d * 2 * nbz + bz) * slot_floats;    // slot 0 of this group; slot 1 is nbz slots further
@@ -457,7 +466,19 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmArgs a, const i
       }
       dc_carry = dc_prev;
     }
+    // The fp16 split needs its operand in fp16's range.  The gate gradients grow along the recurrence (a forget gate near
+    // 1 carries dc over hundreds of frames), so no scale derived from max|dy| before the launch bounds them.  Each batch
+    // row of this workgroup's [32 x 32] operand gets its OWN power of two per step, from the row's largest magnitude: the
+    // products of row b scale with it and the partial sums of row b are divided by it again -- exact, and nothing is
+    // clamped whatever the range of dy across items or the growth over time.  max * scale is in [2^14, 2^15); rows below
+    // 2^-99 (and all-zero rows) take the largest scale, 2^113.
+    const float rmax = max8(fmaxf(fmaxf(fabsf(dG[0]), fabsf(dG[1])), fmaxf(fabsf(dG[2]), fabsf(dG[3]))));
+    const unsigned rex = (__builtin_bit_cast(unsigned, rmax) >> 23) & 0xffu;
+    const unsigned rfs = 268u - rex < 240u ? 268u - rex : 240u;  // biased exponent of the scale, 13 .. 240
+    const float gsc = __builtin_bit_cast(float, rfs << 23);
     _Float16 (*sAh)[40] = sAh2[PERSIST ? (s & 1) : 0], (*sAl)[40] = sAl2[PERSIST ? (s & 1) : 0];
+    float* sInv = sInv2[PERSIST ? (s & 1) : 0];
+    if (ju == 0) sInv[bl_] = __builtin_bit_cast(float, (254u - rfs) << 23);
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       _Float16 h, l;
@@ -467,7 +488,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmArgs a, const i
     }
     __syncthreads();
 
-    // P[j][b][u'] = (1/gscale) * sum_k' A[b][k'] * Wt[d][j][u'][k']
+    // P[j][b][u'] = (1/scale[b]) * sum_k' A[b][k'] * Wt[d][j][u'][k']
     f16x8 ah[2], al[2];
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
@@ -476,6 +497,13 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmArgs a, const i
     }
     const unsigned otag = (unsigned)(s >> 1) & 1u;
     const bool oodd = s & 1;
+    float invr[PERSIST ? 1 : 16];                                // per output row of this lane (see the two MFMA layouts)
+    if (PERSIST) {
+      invr[0] = sInv[lane & 31];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) invr[e] = sInv[(e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)];
+    }
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
       const int tile = wave + 4 * i;
@@ -496,7 +524,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmArgs a, const i
         for (int q = 0; q < 4; ++q) {
           u32x4 o;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (__builtin_bit_cast(unsigned, acc[4 * q + e] * inv) & ~1u) | otag;
+          for (int e = 0; e < 4; ++e) o[e] = (__builtin_bit_cast(unsigned, acc[4 * q + e] * invr[0]) & ~1u) | otag;
           const int po = tok ? ((tile * 4 + q) * NS + j) * 1024 + (lane & 31) * 32 + (lane >> 5) * 16 : OOB;
           __builtin_amdgcn_raw_buffer_store_b128(o, oodd ? rp1 : rp0, po, 0, AUX_SC1);
         }
@@ -510,7 +538,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmArgs a, const i
 #pragma unroll
         for (int e = 0; e < 16; ++e) {                           // P[consumer slice][producer slice j][row][unit & 7]
           const int po = tok ? (((tile * 4 + ((lane & 31) >> 3)) * NS + j) * 256 + ((e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)) * 8 + (lane & 7)) * 4 : OOB;
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, acc[e] * inv), oodd ? rp1 : rp0, po, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, acc[e] * invr[PERSIST ? 0 : e]), oodd ? rp1 : rp0, po, 0, 0);
         }
       }
     }
@@ -569,6 +597,9 @@ int lstm_probe(int bit) {
   return ((e ? atoi(e) : 1) >> bit) & 1;
 }
 
+// which form the calling thread's last forward / backward recurrence ran in (radmmm_lstm_last_path)
+thread_local int g_last_path[2] = {0, 0};
+
 struct Dims {
   int64_t ldk, Bp, Hp, NS;
   Dims(int B, int H) : ldk((H + 15) / 16 * 16), Bp((B + 31) / 32 * 32), Hp((H + 31) / 32 * 32), NS((H + UPW - 1) / UPW) {}
@@ -599,6 +630,10 @@ extern "C" int64_t radmmm_lstm_hseq_bytes(int B, int T, int H) {
   if (one >= (1LL << 31) || !use_persistent(dim3((unsigned)q.NS, 2, (unsigned)(q.Bp / 32)))) return 0;
   return 2 * one;
 }
+
+// 1: the calling thread's last radmmm_lstm_fwd (which = 0) / radmmm_lstm_bwd (which = 1) ran one launch per step, 2: as a
+// single cooperative launch, 0: no such call yet (or `which` out of range).  Set where the launch decision is made.
+extern "C" int radmmm_lstm_last_path(int which) { return which == 0 || which == 1 ? g_last_path[which] : 0; }
 
 // Forward recurrence of both directions.  G [B*T][8H] holds x W_ih^T + b_ih + b_hh (direction d in
 // columns d*4H .., gate order i, f, g, o) and is overwritten by the gate activations; W_hh [2][4H][H];
@@ -638,29 +673,34 @@ extern "C" int radmmm_lstm_fwd(float* G, const float* W_hh, float* y, float* c, 
       radmmm::set_error("lstm_fwd: hipMemsetAsync failed");
       return -2;
     }
-    if (launch_fwd<true>(a, grid, st, 0) == hipSuccess) return radmmm::check_launch("lstm_fwd");
+    if (launch_fwd<true>(a, grid, st, 0) == hipSuccess) {
+      g_last_path[0] = 2;
+      return radmmm::check_launch("lstm_fwd");
+    }
     // the cooperative launch was refused (the grid cannot be co-resident right now): per-step launches on the ping-pong
     // operand buffers (hsplit, zeroed above)
   }
+  g_last_path[0] = 1;
   for (int s = 0; s < T; ++s) launch_fwd<false>(a, grid, st, s);
   return radmmm::check_launch("lstm_fwd");
 }
 
 // Backward recurrence.  G holds the saved gate activations and is overwritten by the pre-activation
 // gradients dG [B*T][8H] (the caller forms dW_ih = dG^T x, dx = dG W_ih, db = colsum(dG),
-// dW_hh[d] = dG_d^T h_prev with plain GEMMs).  gscale: DEVICE scalar, a power of two that brings dG
-// into fp16 range (the caller derives it from max|dy| without a host sync).
+// dW_hh[d] = dG_d^T h_prev with plain GEMMs).  gscale: ignored, may be null (the kernel scales every batch row of
+// its fp16 operand by its own power of two per step; the parameter is kept so that callers of ABI 4 still link).
 extern "C" int radmmm_lstm_bwd(float* G, const float* c, const float* dy, const float* W_hh, const int32_t* lens,
                                void* wtpack, float* P, float* dcbuf, int B, int T, int H, const float* gscale,
                                radmmm_stream_t stream) {
-  RADMMM_REQUIRE(G && c && dy && W_hh && wtpack && P && dcbuf && gscale, "lstm_bwd: null pointer");
+  RADMMM_REQUIRE(G && c && dy && W_hh && wtpack && P && dcbuf, "lstm_bwd: null pointer");
+  (void)gscale;
   RADMMM_REQUIRE(B > 0 && T > 0 && H > 0 && H <= 4 * MAXT * 32, "lstm_bwd: bad dims (H <= %d)", 4 * MAXT * 32);
   RADMMM_REQUIRE(radmmm_lstm_scratch_bytes(B, H, 3) < (1LL << 31), "lstm_bwd: batch too large for one call (partials >= 2 GiB)");
   hipStream_t st = static_cast<hipStream_t>(stream);
   LstmArgs a = {};
   a.G = G; a.c = const_cast<float*>(c); a.dy = dy; a.lens = lens; a.B = B; a.T = T; a.H = H;
   a.ldk = (H + 15) / 16 * 16; a.Bp = (B + 31) / 32 * 32; a.Hp = (H + 31) / 32 * 32; a.NS = (H + UPW - 1) / UPW;
-  a.P = P; a.dcbuf = dcbuf; a.gscale = gscale; a.probe = lstm_probe(1);
+  a.P = P; a.dcbuf = dcbuf; a.probe = lstm_probe(1);
   const long long tn = 2LL * a.NS * a.Hp * 32;
   _Float16* Wth = static_cast<_Float16*>(wtpack);
   _Float16* Wtl = Wth + tn;
@@ -673,8 +713,12 @@ extern "C" int radmmm_lstm_bwd(float* G, const float* c, const float* dy, const 
       radmmm::set_error("lstm_bwd: hipMemsetAsync failed");
       return -2;
     }
-    if (launch_bwd<true>(a, grid, st, 0) == hipSuccess) return radmmm::check_launch("lstm_bwd");
+    if (launch_bwd<true>(a, grid, st, 0) == hipSuccess) {
+      g_last_path[1] = 2;
+      return radmmm::check_launch("lstm_bwd");
+    }
   }
+  g_last_path[1] = 1;
   for (int s = 0; s < T; ++s) launch_bwd<false>(a, grid, st, s);
   return radmmm::check_launch("lstm_bwd");
 }

@@ -16,6 +16,12 @@ from ._lib import lib, check, ptr, stream, amp_fwd, amp_bwd, rowgemm_h3, debug_e
 from ._trace import traced
 
 
+# What the most recent forward ([0]) / backward ([1]) recurrence of this process ran as: 1 = one launch per step, 2 = single
+# cooperative launch (radmmm_lstm_last_path, which is per calling thread -- autograd runs backward on a thread of its own,
+# so it is read right after the call, on that thread).  For tests and diagnostics; nothing here depends on it.
+last_path = [0, 0]
+
+
 def _scratch(B, H, which, like):
     n = int(lib.radmmm_lstm_scratch_bytes(B, H, which))
     return torch.empty((n + 3) // 4, device=like.device, dtype=torch.float32)
@@ -58,6 +64,7 @@ class BiLSTMFn(torch.autograd.Function):
         hseq = torch.empty(nq // 4, device=x.device, dtype=torch.float32) if nq else None
         check(lib.radmmm_lstm_fwd(ptr(G), ptr(W_hh), ptr(y), ptr(c), ptr(lens), ptr(wsplit), ptr(hsplit), ptr(hseq), B, T, H,
                                   stream()), "lstm_fwd")
+        last_path[0] = int(lib.radmmm_lstm_last_path(0))
         ctx.dims = (B, T, I, H)
         ctx.save_for_backward(x2, G, c, y, W_ih, W_hh, lens if lens is not None else torch.empty(0, device=x.device), *xpair)
         ctx.has_lens = lens is not None
@@ -77,13 +84,12 @@ class BiLSTMFn(torch.autograd.Function):
         xpair = tuple(ctx.saved_tensors[7:9]) if ctx.has_xpair else None
         lens = lens if ctx.has_lens else None
         dy2 = dy.contiguous().view(B * T, 2 * H)
-        amax = dy2.abs().amax().clamp_min(1e-30)
-        gscale = torch.exp2(torch.floor(torch.log2(64.0 / amax))).reshape(1).float().contiguous()
         wtpack = _scratch(B, H, 2, dy2)
         P = _scratch(B, H, 3, dy2)
         dcbuf = _scratch(B, H, 4, dy2)
         check(lib.radmmm_lstm_bwd(ptr(G), ptr(c), ptr(dy2), ptr(W_hh), ptr(lens), ptr(wtpack), ptr(P), ptr(dcbuf), B, T, H,
-                                  ptr(gscale), stream()), "lstm_bwd")
+                                  None, stream()), "lstm_bwd")            # (the kernel scales its fp16 operand itself, per row and step)
+        last_path[1] = int(lib.radmmm_lstm_last_path(1))
         dG = G                                                   # now the pre-activation gradients
         y3 = y.view(B, T, 2 * H)
         hp = torch.zeros(B, T, 2 * H, device=dy.device, dtype=torch.float32)
@@ -233,6 +239,7 @@ class MergedBiLSTMFn(torch.autograd.Function):
         hseq = torch.empty(nq // 4, device=dev, dtype=torch.float32) if nq else None
         check(lib.radmmm_lstm_fwd(ptr(G), ptr(W_hh), ptr(y), ptr(c), ptr(lens), ptr(wsplit), ptr(hsplit), ptr(hseq), B, T, HP,
                                   stream()), "lstm_fwd")
+        last_path[0] = int(lib.radmmm_lstm_last_path(0))
         ctx.dims = (B, T, H, P)
         ctx.has_lens = lens is not None
         ctx.n_x2 = len(x2s)
@@ -259,11 +266,10 @@ class MergedBiLSTMFn(torch.autograd.Function):
             if dys[p] is not None:
                 dy[:, :, :, p, :] = dys[p].reshape(B, T, 2, H)
         dy2 = dy.view(B * T, 2 * HP)
-        amax = dy2.abs().amax().clamp_min(1e-30)
-        gscale = torch.exp2(torch.floor(torch.log2(64.0 / amax))).reshape(1).float().contiguous()
         wtpack, Pbuf, dcbuf = _scratch(B, HP, 2, dy2), _scratch(B, HP, 3, dy2), _scratch(B, HP, 4, dy2)
         check(lib.radmmm_lstm_bwd(ptr(G), ptr(c), ptr(dy2), ptr(W_hh), ptr(lens), ptr(wtpack), ptr(Pbuf), ptr(dcbuf), B, T, HP,
-                                  ptr(gscale), stream()), "lstm_bwd")
+                                  None, stream()), "lstm_bwd")
+        last_path[1] = int(lib.radmmm_lstm_last_path(1))
         grads = [None] * (3 + P + 8 * P)
         if ctx.split:
             # the merged tensors as they are: dG' [B*T, 8 HP] is the row-major operand of all four gradient GEMMs (BiLSTMFn.backward)

@@ -46,6 +46,32 @@ def test_argument_validation_without_gpu():
     assert lib.radmmm_wgrad_f32(None, None) == -1
 
 
+def test_lstm_entry_points_validate_without_gpu():
+    """radmmm_lstm_fwd / radmmm_lstm_bwd refuse null pointers and H = 769 (one past the largest size class) with -1 before
+    any HIP call: the null check comes first, so the dims case passes dummy non-null addresses, which that path never
+    dereferences.  The path query reports 0 on a thread that has not run a recurrence."""
+    lib = ctypes.CDLL(LIB)
+    lib.radmmm_last_error.restype = ctypes.c_char_p
+    p, i = ctypes.c_void_p, ctypes.c_int
+    lib.radmmm_lstm_fwd.argtypes = [p] * 8 + [i, i, i, p]
+    lib.radmmm_lstm_bwd.argtypes = [p] * 8 + [i, i, i, p, p]
+    lib.radmmm_lstm_last_path.argtypes = [i]
+    d = 0x1000                                                   # never dereferenced
+    assert lib.radmmm_lstm_fwd(None, d, d, d, None, d, d, None, 2, 3, 8, None) == -1
+    assert b"lstm_fwd: null pointer" in lib.radmmm_last_error()
+    assert lib.radmmm_lstm_bwd(d, d, None, d, None, d, d, d, 2, 3, 8, None, None) == -1
+    assert b"lstm_bwd: null pointer" in lib.radmmm_last_error()
+    for H in (769, 0, -8):
+        assert lib.radmmm_lstm_fwd(d, d, d, d, None, d, d, None, 2, 3, H, None) == -1
+        assert b"lstm_fwd: bad dims" in lib.radmmm_last_error()
+        assert lib.radmmm_lstm_bwd(d, d, d, d, None, d, d, d, 2, 3, H, None, None) == -1
+        assert b"lstm_bwd: bad dims" in lib.radmmm_last_error()
+    for B, T in ((0, 3), (2, 0)):
+        assert lib.radmmm_lstm_fwd(d, d, d, d, None, d, d, None, B, T, 8, None) == -1
+        assert lib.radmmm_lstm_bwd(d, d, d, d, None, d, d, d, B, T, 8, None, None) == -1
+    assert [lib.radmmm_lstm_last_path(w) for w in (0, 1, 2, -1)] == [0, 0, 0, 0]
+
+
 def test_python_binding_matches_struct_layout():
     import rad_mmm_amd._lib as L
     # field order/size of the ctypes mirrors == the C structs (checked via a tiny C probe is not

@@ -46,11 +46,18 @@ def test_bilstm_matches_torch(B, T, I, H, lens, persistent, monkeypatch):
     xd = x.detach().to(DEV).requires_grad_(True)
     lens_d = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
     y = bilstm(dl, xd, lens_d)
+    from _lstm_ref import expected_lstm_path
+    from rad_mmm_amd import lstm as lstm_mod
+    from rad_mmm_amd._lib import lib
+    want = expected_lstm_path(lib, B, T, H)                      # the kernel this parametrisation means to test did run
+    assert want == (1 if persistent == "0" else want) and lib.radmmm_lstm_last_path(0) == want == lstm_mod.last_path[0]
     assert rel_err(y.detach().cpu(), y_ref.detach()) < 2e-5
     if lens is not None:
         for b, n in enumerate(lens):
             assert torch.all(y[b, n:] == 0)
+    lstm_mod.last_path[1] = 0
     (y * gy.to(DEV)).sum().backward()
+    assert lstm_mod.last_path[1] == want                         # (read on autograd's thread, right after the call)
     assert rel_err(xd.grad.cpu(), gx_ref) < 5e-5
     for n, p in dl.named_parameters():
         assert rel_err(p.grad.cpu(), ref_grads[n]) < 5e-5, n

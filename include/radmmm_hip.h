@@ -648,6 +648,49 @@ int radmmm_voc_istft_finish(float* y, int B, int pitch, const int32_t* frames, c
 int radmmm_voc_normalize(float* audio, int lda, const int32_t* lens, int B, int S, radmmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * WaveGlow inference (vocoders/waveglow_for_LIMMITS23/glow.py:105-175 WN.forward, :251-293 WaveGlow.infer).  The wide
+ * convolutions are radmmm_rowgemm_f32 launches (the ConvTranspose1d(n_mel, n_mel, 1024, 256) upsample as ONE polyphase
+ * row GEMM, cond_layer once per flow for all layers, the 3-tap dilated in_layers with taps/dil, the 1x1 res_skip
+ * layers).  These entry points are what surrounds them.  Rows are GROUP steps: row r = b*Tg + g holds samples
+ * g*n_group .. g*n_group + n_group - 1 of item b, Tg = T*hop/n_group.  `lens` are int32 device arrays [B] of valid
+ * group steps (NULL: all rows valid); rows at or past an item's length are written as 0.  The flow variable X keeps its
+ * c live channels in columns [col0, col0 + c) of an [rows][ldx] array, col0 = n_group - c, so an early re-attachment
+ * writes the n_early_size columns in front of them and the final X is the waveform.  Additive entry points of ABI 4.
+ *   wg_group_cond    rows[(b*Tg + g)*ldr + m*n_group + j] = up[b*up_item_stride + (g*n_group + j)*n_mel + m] (glow.py:257-258:
+ *                    unfold + permute, channel order mel*n_group + j), 0 in columns n_mel*n_group .. ldr.  up is the
+ *                    channels-last upsampled mel; up_item_stride >= Tg*n_group*n_mel floats (the samples a longer
+ *                    transposed-convolution tail would hold past Tg*n_group are never read: the reference's trim)
+ *   wg_noise_rows    X[(b*Tg + g)*ldx + col0 + c] = sigma * z[(b*ch + c)*Tg + g], z in the reference's [B][ch][Tg] layout:
+ *                    the initial sigma * z and cat(sigma * z, audio) of an early re-attachment (glow.py:269, 290)
+ *   wg_start         H[r, c] = bias[c] + sum_{i < n_half} W[c*n_half + i] * X[r*ldx + col0 + i]  (WN.start, n_half <= 8)
+ *   wg_gate          y[r, c] = tanh(a[r, c] + cond[r, cond_off + c]) * sigmoid(a[r, C + c] + cond[r, cond_off + C + c]),
+ *                    c < C: fused_add_tanh_sigmoid_multiply on layer i's slice cond_off = 2*C*i of the conditioning, in place
+ *   wg_res_skip      last == 0: H[r, c] += rs[r, c], S[r, c] = (first ? 0 : S[r, c]) + rs[r, C + c];
+ *                    last != 0: S[r, c] = (first ? 0 : S[r, c]) + rs[r, c] (rs has C columns, H is not touched)
+ *   wg_end_coupling  o = Wend S[r] + bend (Wend [2 n_half][C]); z = [X0, (X1 - o[:n_half]) * exp(-o[n_half:])] with
+ *                    X0 / X1 the two halves of X[r, col0 : col0 + 2 n_half]; X[r, col0 + i] = sum_j Winv[i*2 n_half + j]
+ *                    * z[j] (the inverse 1x1 mix, Winv inverted by the caller), in place.  n_half <= 4,
+ *                    2 n_half * (C + 2 n_half + 1) <= 8192
+ *   wg_ungroup       audio[b*lda + g*n_group + j] = X[(b*Tg + g)*ldx + col0 + j], 0 for g >= lens[b]
+ * C, lda, ldcond, cond_off, ldy, ldrs, ldh, lds % 4 == 0 and 16-byte aligned a / cond / y / rs / H / S / Wend.
+ * ------------------------------------------------------------------------------------ */
+int radmmm_wg_group_cond(const float* up, int64_t up_item_stride, float* rows, int ldr, const int32_t* lens, int B, int Tg,
+                         int n_mel, int n_group, radmmm_stream_t stream);
+int radmmm_wg_noise_rows(const float* z, float sigma, float* X, int ldx, int col0, int ch, const int32_t* lens, int B,
+                         int Tg, radmmm_stream_t stream);
+int radmmm_wg_start(const float* X, int ldx, int col0, int n_half, const float* W, const float* bias, float* H, int ldh,
+                    int C, const int32_t* lens, int rows, int T, radmmm_stream_t stream);
+int radmmm_wg_gate(const float* a, int lda, const float* cond, int ldcond, int cond_off, float* y, int ldy, int C,
+                   const int32_t* lens, int rows, int T, radmmm_stream_t stream);
+int radmmm_wg_res_skip(const float* rs, int ldrs, float* H, int ldh, float* S, int lds, int C, int first, int last,
+                       const int32_t* lens, int rows, int T, radmmm_stream_t stream);
+int radmmm_wg_end_coupling(const float* S, int lds, const float* Wend, const float* bend, const float* Winv, float* X,
+                           int ldx, int col0, int n_half, int C, const int32_t* lens, int rows, int T,
+                           radmmm_stream_t stream);
+int radmmm_wg_ungroup(const float* X, int ldx, int col0, int n_group, float* audio, int64_t lda, const int32_t* lens,
+                      int B, int Tg, radmmm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Batched synthesis glue (TTSModel.sample_full / reconstruct_from_batch_attributes, tts_lightning_modules.py:286-437).
  * Additive entry points of ABI 4.  No floating-point atomics: every result is bitwise repeatable.
  *   synth_durations  per token t of utterance b (x[b*item_stride + t], fp32): d = min(max(rint(x), 1), 65536) for

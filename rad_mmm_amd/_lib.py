@@ -212,6 +212,13 @@ def _load() -> C.CDLL:
         "radmmm_voc_spec_bins": [p, i, i, i, p, f, p, p],
         "radmmm_voc_istft_finish": [p, i, i, p, p, i, i, p],
         "radmmm_voc_normalize": [p, i, p, i, i, p],
+        "radmmm_wg_group_cond": [p, i64, p, i, p, i, i, i, i, p],
+        "radmmm_wg_noise_rows": [p, f, p, i, i, i, p, i, i, p],
+        "radmmm_wg_start": [p, i, i, i, p, p, p, i, i, p, i, i, p],
+        "radmmm_wg_gate": [p, i, p, i, i, p, i, i, p, i, i, p],
+        "radmmm_wg_res_skip": [p, i, p, i, p, i, i, i, i, p, i, i, p],
+        "radmmm_wg_end_coupling": [p, i, p, p, p, p, i, i, i, i, p, i, i, p],
+        "radmmm_wg_ungroup": [p, i, i, i, p, i64, p, i, i, p],
         "radmmm_synth_durations": [p, i64, p, i, i, i, p, p, p, p],
         "radmmm_synth_regulate": [p, i64, i, i, i, p, p, i, i, p, i, p],
         "radmmm_synth_f0_stats": [p, i64, p, i64, p, i, i, p, i, p],

@@ -1,0 +1,356 @@
+// WaveGlow inference support kernels (vocoders/waveglow_for_LIMMITS23/glow.py:105-175 WN.forward, :251-293
+// WaveGlow.infer) on gfx950.
+//
+// The wide convolutions (the polyphase upsample, cond_layer, the dilated in_layers and the 1x1 res_skip layers) are
+// row GEMMs of radmmm_rowgemm_f32; what lives here is everything around them, on channels-last rows of GROUP steps
+// ([B*Tg rows][ld] fp32, row r = b*Tg + g, Tg = T*hop/n_group) with the same per-item length masking as the HiFi-GAN
+// path (rows at or past lens[b] are written as zeros, so no layer ever sees what bias and gating would leave there):
+//   radmmm_wg_group_cond    upsampled mel [B][Tg*n_group][n_mel] -> conditioning rows [B*Tg][n_mel*n_group]
+//   radmmm_wg_noise_rows    sigma * z (reference layout [B][ch][Tg]) into `ch` columns of the audio rows: the initial
+//                           draw and every early re-attachment (the audio rows are kept RIGHT aligned in n_group
+//                           columns, so cat(sigma*z, audio) is a write beside the live columns and nothing moves)
+//   radmmm_wg_start         WN.start: n_half (<= 8) -> C channels, K far below a GEMM tile
+//   radmmm_wg_gate          tanh(a[:, :C] + cond[:, off:off+C]) * sigmoid(a[:, C:] + cond[:, off+C:off+2C])
+//   radmmm_wg_res_skip      audio += rs[:, :C]; skip (+)= rs[:, C:]   (last layer: skip += rs[:, :C] only)
+//   radmmm_wg_end_coupling  WN.end (C -> 2 n_half) + audio_1 = (audio_1 - b) * exp(-s) + the inverse 1x1 mix, in place
+//   radmmm_wg_ungroup       audio rows -> [B][Tg*n_group] samples, zeros past each length
+// All of them are bound by memory traffic (each reads or writes [rows][C] or [rows][2C] once); none uses atomics and
+// every output element is summed in an order that depends on its own row alone, so an item in a batch is bit-identical
+// to the item alone as far as these kernels go.
+#include "common.h"
+
+namespace {
+
+inline hipStream_t ST(radmmm_stream_t s) { return static_cast<hipStream_t>(s); }
+
+inline int grid_for(long long total, int block) {
+  long long g = (total + block - 1) / block;
+  if (g > 16384) g = 16384;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
+// rows[(b*Tg + g)*ldr + m*ng + j] = up[b*item_stride + (g*ng + j)*n_mel + m] for g < lens[b]; 0 in the rows past the
+// item's length and in the padding columns n_mel*ng <= c < ldr.  One thread per output element: a group step's source
+// (ng x n_mel floats) and destination (n_mel x ng) are the same contiguous 4*n_mel*ng bytes transposed, so both sides
+// stay inside a few cache lines per wavefront.
+__global__ __launch_bounds__(256) void group_cond_kernel(const float* __restrict__ up, long long item_stride,
+                                                         float* __restrict__ rows, int ldr,
+                                                         const int32_t* __restrict__ lens, long long R, int Tg,
+                                                         int n_mel, int ng) {
+  const long long total = R * ldr;
+  const int cols = n_mel * ng;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / ldr;
+    const int c = (int)(i - r * ldr);
+    const int b = (int)(r / Tg), g = (int)(r - (long long)b * Tg);
+    float v = 0.f;
+    if (c < cols && (!lens || g < lens[b])) {
+      const int m = c / ng, j = c - m * ng;
+      v = up[b * item_stride + ((long long)g * ng + j) * n_mel + m];
+    }
+    rows[i] = v;
+  }
+}
+
+// X[(b*Tg + g)*ldx + col0 + c] = sigma * z[(b*ch + c)*Tg + g] for g < lens[b], else 0
+__global__ __launch_bounds__(256) void noise_rows_kernel(const float* __restrict__ z, float sigma,
+                                                         float* __restrict__ X, int ldx, int col0, int ch,
+                                                         const int32_t* __restrict__ lens, int B, int Tg) {
+  const long long total = (long long)B * ch * Tg;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long bc = i / Tg;
+    const int g = (int)(i - bc * Tg);
+    const int b = (int)(bc / ch), c = (int)(bc - (long long)b * ch);
+    const bool valid = !lens || g < lens[b];
+    X[((long long)b * Tg + g) * ldx + col0 + c] = valid ? sigma * z[i] : 0.f;
+  }
+}
+
+// H[r, c] = bias[c] + sum_{i < nh} W[c*nh + i] * X[r*ldx + col0 + i] for t < lens[b], else 0.  One float4 of H per
+// thread; the nh <= 8 inputs of the row are re-read by the C/4 threads of the row (L1 hits).
+constexpr int START_MAX_NH = 8;
+__global__ __launch_bounds__(256) void start_kernel(const float* __restrict__ X, int ldx, int col0, int nh,
+                                                    const float* __restrict__ W, const float* __restrict__ bias,
+                                                    float* __restrict__ H, int ldh, int C,
+                                                    const int32_t* __restrict__ lens, long long rows, int T) {
+  const int q = C >> 2;
+  const long long total = rows * q;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / q;
+    const int c = (int)(i - r * q) * 4;
+    const int b = (int)(r / T), t = (int)(r - (long long)b * T);
+    float o[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!lens || t < lens[b]) {
+      const float* xr = X + r * ldx + col0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float acc = bias ? bias[c + e] : 0.f;
+        const float* w = W + (long long)(c + e) * nh;
+        for (int k = 0; k < nh; ++k) acc = fmaf(w[k], xr[k], acc);
+        o[e] = acc;
+      }
+    }
+    *reinterpret_cast<float4*>(H + r * ldh + c) = make_float4(o[0], o[1], o[2], o[3]);
+  }
+}
+
+__device__ __forceinline__ float gate1(float ta, float tc, float sa, float sc) {
+  // libm tanhf / expf (not the 1-ulp hardware exp2 forms): the kernel is bound by its 5 C floats of traffic per row
+  return tanhf(ta + tc) * (1.f / (1.f + expf(-(sa + sc))));
+}
+
+// y[r, c] = tanh(a[r, c] + cond[r, off + c]) * sigmoid(a[r, C + c] + cond[r, off + C + c]) for t < lens[b], else 0
+__global__ __launch_bounds__(256) void gate_kernel(const float* __restrict__ a, int lda, const float* __restrict__ cond,
+                                                   int ldcond, int off, float* __restrict__ y, int ldy, int C,
+                                                   const int32_t* __restrict__ lens, long long rows, int T) {
+  const int q = C >> 2;
+  const long long total = rows * q;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / q;
+    const int c = (int)(i - r * q) * 4;
+    const int b = (int)(r / T), t = (int)(r - (long long)b * T);
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!lens || t < lens[b]) {
+      const float* ar = a + r * lda + c;
+      const float* cr = cond + r * ldcond + off + c;
+      const float4 ta = *reinterpret_cast<const float4*>(ar), sa = *reinterpret_cast<const float4*>(ar + C);
+      const float4 tc = *reinterpret_cast<const float4*>(cr), sc = *reinterpret_cast<const float4*>(cr + C);
+      o.x = gate1(ta.x, tc.x, sa.x, sc.x);
+      o.y = gate1(ta.y, tc.y, sa.y, sc.y);
+      o.z = gate1(ta.z, tc.z, sa.z, sc.z);
+      o.w = gate1(ta.w, tc.w, sa.w, sc.w);
+    }
+    *reinterpret_cast<float4*>(y + r * ldy + c) = o;
+  }
+}
+
+__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// not last: H[r, c] += rs[r, c]; S[r, c] = (first ? 0 : S[r, c]) + rs[r, C + c].  last: S[r, c] = (first ? 0 : S[r, c])
+// + rs[r, c], H untouched.  Rows past the item's length are written as zeros in everything that is written.
+__global__ __launch_bounds__(256) void res_skip_kernel(const float* __restrict__ rs, int ldrs, float* __restrict__ H,
+                                                       int ldh, float* __restrict__ S, int lds, int C, int first,
+                                                       int last, const int32_t* __restrict__ lens, long long rows,
+                                                       int T) {
+  const int q = C >> 2;
+  const long long total = rows * q;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / q;
+    const int c = (int)(i - r * q) * 4;
+    const int b = (int)(r / T), t = (int)(r - (long long)b * T);
+    const bool valid = !lens || t < lens[b];
+    float4 h = make_float4(0.f, 0.f, 0.f, 0.f), s = h;
+    float4* hp = last ? nullptr : reinterpret_cast<float4*>(H + r * ldh + c);   // H may be NULL with last
+    float4* sp = reinterpret_cast<float4*>(S + r * lds + c);
+    if (valid) {
+      const float* rr = rs + r * ldrs + c;
+      if (!first) s = *sp;
+      if (last) {
+        s = add4(s, *reinterpret_cast<const float4*>(rr));
+      } else {
+        h = add4(*hp, *reinterpret_cast<const float4*>(rr));
+        s = add4(s, *reinterpret_cast<const float4*>(rr + C));
+      }
+    }
+    if (!last) *hp = h;
+    *sp = s;
+  }
+}
+
+// out = Wend S[r] + bend (NO = 2 n_half outputs: b = out[:n_half], s = out[n_half:]), z = [X0, (X1 - b) * exp(-s)],
+// X[r, col0 : col0 + NO] = Winv z; zeros past the item's length.  16 lanes share a row (a float4 of S per lane and 64
+// columns, xor-butterfly over the 16 lanes: every row is summed in the same order wherever it sits), 16 rows per
+// workgroup pass, Wend / Winv / bend in LDS.
+template <int NO>
+__global__ __launch_bounds__(256) void end_coupling_kernel(const float* __restrict__ S, int lds,
+                                                           const float* __restrict__ Wend,
+                                                           const float* __restrict__ bend,
+                                                           const float* __restrict__ Winv, float* __restrict__ X,
+                                                           int ldx, int col0, int C,
+                                                           const int32_t* __restrict__ lens, long long rows, int T) {
+  extern __shared__ __align__(16) float sh[];   // float4 reads of Wend rows below
+  float* w = sh;                    // [NO][C]
+  float* wi = sh + NO * C;          // [NO][NO]
+  float* be = wi + NO * NO;         // [NO]
+  for (int i = threadIdx.x; i < NO * C; i += blockDim.x) w[i] = Wend[i];
+  for (int i = threadIdx.x; i < NO * NO; i += blockDim.x) wi[i] = Winv[i];
+  for (int i = threadIdx.x; i < NO; i += blockDim.x) be[i] = bend ? bend[i] : 0.f;
+  __syncthreads();
+  constexpr int NH = NO / 2;
+  const int sub = threadIdx.x & 15, rloc = threadIdx.x >> 4;
+  for (long long r0 = blockIdx.x * 16LL; r0 < rows; r0 += gridDim.x * 16LL) {
+    const long long r = r0 + rloc;
+    bool valid = r < rows;
+    if (valid && lens) {
+      const int b = (int)(r / T), t = (int)(r - (long long)b * T);
+      valid = t < lens[b];
+    }
+    float acc[NO];
+#pragma unroll
+    for (int o = 0; o < NO; ++o) acc[o] = 0.f;
+    if (valid) {
+      const float* sr = S + r * lds;
+      for (int c = sub * 4; c < C; c += 64) {
+        const float4 v = *reinterpret_cast<const float4*>(sr + c);
+#pragma unroll
+        for (int o = 0; o < NO; ++o) {
+          const float4 ww = *reinterpret_cast<const float4*>(w + o * C + c);
+          acc[o] = fmaf(v.w, ww.w, fmaf(v.z, ww.z, fmaf(v.y, ww.y, fmaf(v.x, ww.x, acc[o]))));
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+#pragma unroll
+      for (int m = 8; m > 0; m >>= 1) acc[o] += __shfl_xor(acc[o], m, 16);
+    }
+    if (sub == 0 && r < rows) {
+      float* xr = X + r * ldx + col0;
+      float z[NO];
+      if (valid) {
+#pragma unroll
+        for (int k = 0; k < NH; ++k) {
+          z[k] = xr[k];
+          z[NH + k] = (xr[NH + k] - (acc[k] + be[k])) * expf(-(acc[NH + k] + be[NH + k]));
+        }
+#pragma unroll
+        for (int o = 0; o < NO; ++o) {
+          float v = 0.f;
+#pragma unroll
+          for (int k = 0; k < NO; ++k) v = fmaf(wi[o * NO + k], z[k], v);
+          xr[o] = v;
+        }
+      } else {
+#pragma unroll
+        for (int o = 0; o < NO; ++o) xr[o] = 0.f;
+      }
+    }
+  }
+}
+
+// audio[b*lda + g*ng + j] = X[(b*Tg + g)*ldx + col0 + j] for g < lens[b], else 0 (every sample of [0, Tg*ng) written)
+__global__ __launch_bounds__(256) void ungroup_kernel(const float* __restrict__ X, int ldx, int col0, int ng,
+                                                      float* __restrict__ audio, long long lda,
+                                                      const int32_t* __restrict__ lens, int B, int Tg) {
+  const long long per = (long long)Tg * ng;
+  const long long total = (long long)B * per;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / per);
+    const long long n = i - (long long)b * per;
+    const int g = (int)(n / ng), j = (int)(n - (long long)g * ng);
+    const bool valid = !lens || g < lens[b];
+    audio[b * lda + n] = valid ? X[((long long)b * Tg + g) * ldx + col0 + j] : 0.f;
+  }
+}
+
+}  // namespace
+
+extern "C" int radmmm_wg_group_cond(const float* up, int64_t up_item_stride, float* rows, int ldr, const int32_t* lens,
+                                    int B, int Tg, int n_mel, int n_group, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(up && rows, "wg_group_cond: null pointer");
+  RADMMM_REQUIRE(B > 0 && Tg > 0 && n_mel > 0 && n_group > 0 && ldr >= n_mel * n_group &&
+                     up_item_stride >= (int64_t)Tg * n_group * n_mel && (int64_t)B * Tg <= 0x7fffffffLL,
+                 "wg_group_cond: bad dims (B=%d Tg=%d n_mel=%d n_group=%d ldr=%d item_stride=%lld)", B, Tg, n_mel,
+                 n_group, ldr, (long long)up_item_stride);
+  const long long R = (long long)B * Tg;
+  hipLaunchKernelGGL(group_cond_kernel, dim3(grid_for(R * ldr, 256)), dim3(256), 0, ST(stream), up,
+                     (long long)up_item_stride, rows, ldr, lens, R, Tg, n_mel, n_group);
+  return radmmm::check_launch("wg_group_cond");
+}
+
+extern "C" int radmmm_wg_noise_rows(const float* z, float sigma, float* X, int ldx, int col0, int ch,
+                                    const int32_t* lens, int B, int Tg, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(z && X, "wg_noise_rows: null pointer");
+  RADMMM_REQUIRE(B > 0 && Tg > 0 && ch > 0 && col0 >= 0 && col0 + ch <= ldx,
+                 "wg_noise_rows: bad dims (B=%d Tg=%d ch=%d col0=%d ldx=%d)", B, Tg, ch, col0, ldx);
+  hipLaunchKernelGGL(noise_rows_kernel, dim3(grid_for((long long)B * ch * Tg, 256)), dim3(256), 0, ST(stream), z, sigma,
+                     X, ldx, col0, ch, lens, B, Tg);
+  return radmmm::check_launch("wg_noise_rows");
+}
+
+extern "C" int radmmm_wg_start(const float* X, int ldx, int col0, int n_half, const float* W, const float* bias,
+                               float* H, int ldh, int C, const int32_t* lens, int rows, int T,
+                               radmmm_stream_t stream) {
+  RADMMM_REQUIRE(X && W && H, "wg_start: null pointer");
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && C > 0 && C % 4 == 0 && ldh % 4 == 0 && ldh >= C && n_half >= 1 &&
+                     n_half <= START_MAX_NH && col0 >= 0 && col0 + n_half <= ldx,
+                 "wg_start: bad dims (rows=%d T=%d C=%d ldh=%d n_half=%d col0=%d ldx=%d)", rows, T, C, ldh, n_half, col0,
+                 ldx);
+  RADMMM_REQUIRE(radmmm::aligned16(H), "wg_start: H must be 16B aligned");
+  hipLaunchKernelGGL(start_kernel, dim3(grid_for((long long)rows * (C / 4), 256)), dim3(256), 0, ST(stream), X, ldx,
+                     col0, n_half, W, bias, H, ldh, C, lens, (long long)rows, T);
+  return radmmm::check_launch("wg_start");
+}
+
+extern "C" int radmmm_wg_gate(const float* a, int lda, const float* cond, int ldcond, int cond_off, float* y, int ldy,
+                              int C, const int32_t* lens, int rows, int T, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(a && cond && y, "wg_gate: null pointer");
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && C > 0 && C % 4 == 0 && lda % 4 == 0 && lda >= 2 * C &&
+                     ldcond % 4 == 0 && cond_off >= 0 && cond_off % 4 == 0 && cond_off + 2 * C <= ldcond &&
+                     ldy % 4 == 0 && ldy >= C,
+                 "wg_gate: bad dims (rows=%d T=%d C=%d lda=%d ldcond=%d cond_off=%d ldy=%d)", rows, T, C, lda, ldcond,
+                 cond_off, ldy);
+  RADMMM_REQUIRE(radmmm::aligned16(a) && radmmm::aligned16(cond) && radmmm::aligned16(y),
+                 "wg_gate: a / cond / y must be 16B aligned");
+  hipLaunchKernelGGL(gate_kernel, dim3(grid_for((long long)rows * (C / 4), 256)), dim3(256), 0, ST(stream), a, lda, cond,
+                     ldcond, cond_off, y, ldy, C, lens, (long long)rows, T);
+  return radmmm::check_launch("wg_gate");
+}
+
+extern "C" int radmmm_wg_res_skip(const float* rs, int ldrs, float* H, int ldh, float* S, int lds, int C, int first,
+                                  int last, const int32_t* lens, int rows, int T, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(rs && S && (H || last), "wg_res_skip: null pointer");
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && C > 0 && C % 4 == 0 && ldrs % 4 == 0 &&
+                     ldrs >= (last ? C : 2 * C) && lds % 4 == 0 && lds >= C && (last || (ldh % 4 == 0 && ldh >= C)),
+                 "wg_res_skip: bad dims (rows=%d T=%d C=%d ldrs=%d ldh=%d lds=%d last=%d)", rows, T, C, ldrs, ldh, lds,
+                 last);
+  RADMMM_REQUIRE(radmmm::aligned16(rs) && radmmm::aligned16(S) && (last || radmmm::aligned16(H)),
+                 "wg_res_skip: rs / H / S must be 16B aligned");
+  hipLaunchKernelGGL(res_skip_kernel, dim3(grid_for((long long)rows * (C / 4), 256)), dim3(256), 0, ST(stream), rs, ldrs,
+                     H, ldh, S, lds, C, first, last, lens, (long long)rows, T);
+  return radmmm::check_launch("wg_res_skip");
+}
+
+extern "C" int radmmm_wg_end_coupling(const float* S, int lds, const float* Wend, const float* bend, const float* Winv,
+                                      float* X, int ldx, int col0, int n_half, int C, const int32_t* lens, int rows,
+                                      int T, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(S && Wend && Winv && X, "wg_end_coupling: null pointer");
+  const int NO = 2 * n_half;
+  const long long smem = ((long long)NO * C + NO * NO + NO) * 4;
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && C > 0 && C % 4 == 0 && lds % 4 == 0 && lds >= C && n_half >= 1 &&
+                     n_half <= 4 && col0 >= 0 && col0 + NO <= ldx && smem <= 32768,
+                 "wg_end_coupling: bad dims (rows=%d T=%d C=%d lds=%d n_half=%d col0=%d ldx=%d; n_half <= 4, "
+                 "(2 n_half)(C + 2 n_half + 1) <= 8192)", rows, T, C, lds, n_half, col0, ldx);
+  RADMMM_REQUIRE(radmmm::aligned16(S) && radmmm::aligned16(Wend), "wg_end_coupling: S / Wend must be 16B aligned");
+  const dim3 grid(grid_for(((long long)rows + 15) / 16, 1)), block(256);
+#define WG_END(NOV)                                                                                                  \
+  hipLaunchKernelGGL(end_coupling_kernel<NOV>, grid, block, (size_t)smem, ST(stream), S, lds, Wend, bend, Winv, X, ldx, \
+                     col0, C, lens, (long long)rows, T)
+  switch (NO) {
+    case 2: WG_END(2); break;
+    case 4: WG_END(4); break;
+    case 6: WG_END(6); break;
+    default: WG_END(8); break;
+  }
+#undef WG_END
+  return radmmm::check_launch("wg_end_coupling");
+}
+
+extern "C" int radmmm_wg_ungroup(const float* X, int ldx, int col0, int n_group, float* audio, int64_t lda,
+                                 const int32_t* lens, int B, int Tg, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(X && audio, "wg_ungroup: null pointer");
+  RADMMM_REQUIRE(B > 0 && Tg > 0 && n_group > 0 && col0 >= 0 && col0 + n_group <= ldx &&
+                     lda >= (int64_t)Tg * n_group,
+                 "wg_ungroup: bad dims (B=%d Tg=%d n_group=%d col0=%d ldx=%d lda=%lld)", B, Tg, n_group, col0, ldx,
+                 (long long)lda);
+  hipLaunchKernelGGL(ungroup_kernel, dim3(grid_for((long long)B * Tg * n_group, 256)), dim3(256), 0, ST(stream), X, ldx,
+                     col0, n_group, audio, (long long)lda, lens, B, Tg);
+  return radmmm::check_launch("wg_ungroup");
+}

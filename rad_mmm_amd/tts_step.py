@@ -244,11 +244,16 @@ class TTSTrainingStep(nn.Module):
         passes `mels` rather than `current_mel` to get_audio_for_mels (tts_lightning_modules.py:572-573, which vocodes
         mels[0]) and so returns utterance 0 B times; this returns each utterance at its own length."""
         from .vocoder import vocode
+        from .waveglow import WaveGlow, vocode_waveglow
         if self.synth_vocoder is None:
-            raise RuntimeError("vocode_mels: attach a vocoder first (step.synth_vocoder = load_hifigan_vocoder(...))")
+            raise RuntimeError("vocode_mels: attach a vocoder first (step.synth_vocoder = load_hifigan_vocoder(...) or "
+                               "load_waveglow_vocoder(...))")
         generator, denoiser = self.synth_vocoder
         lens = out_lens.lengths_host if isinstance(out_lens, SequenceLength) else out_lens
-        audio, s_lens = vocode(generator, denoiser, mels, lens, strength=strength, normalize=normalize)
+        if isinstance(generator, WaveGlow):      # a (WaveGlow, WaveGlowDenoiser) pair of load_waveglow_vocoder
+            audio, s_lens = vocode_waveglow(generator, denoiser, mels, lens, strength=strength, normalize=normalize)
+        else:
+            audio, s_lens = vocode(generator, denoiser, mels, lens, strength=strength, normalize=normalize)
         audio = audio.cpu().numpy()
         s_lens = s_lens.cpu().tolist()
         return [audio[b, :s_lens[b]].copy() for b in range(len(s_lens))]

@@ -1,0 +1,429 @@
+"""WaveGlow vocoder + its STFT denoiser, batched on the GPU: mel -> waveform (reference
+vocoders/waveglow_for_LIMMITS23/glow.py:62-311, denoiser.py, tacotron2/stft.py, vocoders/vocoder_utils.py:49-58, 134-143).
+
+The reference's `infer` takes one utterance, knows no lengths and draws its noise inside the call.  Here a batch
+[B, n_mel, T] with per-item lengths goes through one launch sequence, the noise can be handed in, item b equals a call
+with item b alone at T = lens[b] given the same noise columns, and everything past lens[b] * hop is exactly 0.
+
+Layout: channels-last rows of GROUP steps.  Row r = b*Tg + g (Tg = T * hop / n_group) holds the n_group consecutive
+samples g*n_group .. of item b, as the reference's unfold does, and every layer treats rows at or past lens[b] * hop /
+n_group as zeros (the reference's convolutions zero-pad at an utterance's end).  The flow variable X is an [R, n_group]
+array whose c live channels sit RIGHT aligned in columns [n_group - c, n_group): an early re-attachment
+cat(sigma * z, audio) writes n_early_size columns in front of them and nothing moves, and the final X is the waveform.
+
+The wide convolutions are radmmm_rowgemm_f32 launches (exact fp32 MFMA): the ConvTranspose1d(n_mel, n_mel, 1024,
+stride 256) as ONE polyphase row GEMM (pack_polyphase; output row group g takes input frames g - 3 .. g, and writing
+exactly `stride` samples per frame is the reference's trim of kernel - stride samples), cond_layer once per flow for all
+layers, the 3-tap in_layers with dilation 2^i, the 1x1 res_skip layers.  Everything else (grouping the conditioning,
+start, the gate on a conditioning slice, the residual / skip update, end + inverse coupling + inverse 1x1 mix, the
+noise columns, un-grouping) is a kernel of csrc/waveglow.hip.
+"""
+from __future__ import annotations
+
+import json
+import pickle
+from typing import Optional, Sequence, Tuple, Union
+
+import torch
+from torch import nn
+
+from . import ops
+from ._lib import RadmmmError, check, f32c, fp32_region, lib, ptr, rowgemm, stream
+from .vocoder import Denoiser, _lens_arg, _to_device, fold_weight_norm, pack_polyphase
+
+UPSAMPLE_KERNEL = 1024     # glow.py:183-186: hard-coded in the reference
+HOP = 256
+_A_OPERAND_BYTES = 2 ** 31 - 2 ** 16     # the row GEMM's 16-row fast path needs A operands below 2 GiB
+_COND_BYTES = 8 << 30                    # cap of the per-flow conditioning buffer [rows, 2 * n_channels * n_layers]
+
+
+class _WN(nn.Module):
+    """parameter holder with the reference WN's names (glow.py:105-151), weight norm already folded"""
+
+    def __init__(self, n_in_channels, n_mel_channels, n_layers, n_channels, kernel_size):
+        super().__init__()
+        if kernel_size % 2 != 1:
+            raise ValueError(f"WN kernel_size {kernel_size}: only odd kernels keep the length")
+        if n_channels % 4:
+            raise ValueError(f"WN n_channels {n_channels} must be a multiple of 4")
+        self.n_layers, self.n_channels, self.kernel_size = int(n_layers), int(n_channels), int(kernel_size)
+        self.start = nn.Conv1d(n_in_channels, n_channels, 1)
+        self.end = nn.Conv1d(n_channels, 2 * n_in_channels, 1)
+        nn.init.zeros_(self.end.weight)
+        nn.init.zeros_(self.end.bias)
+        self.cond_layer = nn.Conv1d(n_mel_channels, 2 * n_channels * n_layers, 1)
+        self.in_layers = nn.ModuleList()
+        self.res_skip_layers = nn.ModuleList()
+        for i in range(n_layers):
+            d = 2 ** i
+            self.in_layers.append(nn.Conv1d(n_channels, 2 * n_channels, kernel_size, dilation=d,
+                                            padding=(kernel_size * d - d) // 2))
+            self.res_skip_layers.append(nn.Conv1d(n_channels, 2 * n_channels if i < n_layers - 1 else n_channels, 1))
+
+
+class _Invertible1x1Conv(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.conv = nn.Conv1d(c, c, 1, bias=False)
+        W = torch.linalg.qr(torch.randn(c, c))[0]
+        if torch.det(W) < 0:
+            W[:, 0] = -W[:, 0]
+        self.conv.weight.data = W.reshape(c, c, 1).contiguous()
+
+
+def fold_weight_norm_keys(state_dict: dict) -> dict:
+    """<name>.weight_g / <name>.weight_v (torch.nn.utils.weight_norm) or <name>.parametrizations.weight.original0 /
+    original1 (its parametrization form) -> <name>.weight; every other key unchanged"""
+    out = {}
+    for k, v in state_dict.items():
+        if k.endswith(".weight_g") or k.endswith(".parametrizations.weight.original0"):
+            continue
+        if k.endswith(".weight_v"):
+            base = k[:-len(".weight_v")]
+            out[base + ".weight"] = fold_weight_norm(v.float(), state_dict[base + ".weight_g"].float())
+        elif k.endswith(".parametrizations.weight.original1"):
+            base = k[:-len(".parametrizations.weight.original1")]
+            out[base + ".weight"] = fold_weight_norm(v.float(),
+                                                     state_dict[base + ".parametrizations.weight.original0"].float())
+        else:
+            out[k] = v
+    return out
+
+
+class WaveGlow(nn.Module):
+    """WaveGlow(n_mel_channels, n_flows, n_group, n_early_every, n_early_size, WN_config) of glow.py:178-205, inference
+    only.  state_dict keys are those of a reference model after remove_weightnorm (upsample.weight / .bias,
+    WN.{k}.start / in_layers.{i} / cond_layer / res_skip_layers.{i} / end .weight / .bias, convinv.{k}.conv.weight);
+    load_state_dict also takes the weight-normed keys (.weight_g / .weight_v) and folds them.
+
+    infer(mel [B, n_mel, T], lens=None, sigma=1.0, noise=None) -> audio [B, T * 256], exactly 0 at and past
+    lens[b] * 256.  lens: lengths in mel frames, a host list / CPU tensor (no device -> host synchronisation) or a
+    device int32 tensor.
+
+    noise: None (drawn on the device) or the tuple of the reference's draws in the reference's order, each in the
+    reference's layout [B, channels, Tg] with Tg = T * 256 / n_group group steps:
+        noise[0]    [B, n_remaining_channels, Tg]   the initial draw (glow.py:265-267)
+        noise[1 + j] [B, n_early_size, Tg]          one per early re-attachment, taken while k runs DOWN from
+                                                    n_flows - 1 (glow.py:285-290: at every k > 0 with k % n_early_every
+                                                    == 0), so noise[1] belongs to the largest such k
+    Column g of every draw belongs to samples g*n_group .. g*n_group + n_group - 1; columns at or past an item's length
+    are ignored.  Item b alone at T = lens[b] with noise[:][b:b+1, :, :lens[b] * 256 / n_group] gives the same audio."""
+
+    def __init__(self, n_mel_channels, n_flows, n_group, n_early_every, n_early_size, WN_config):
+        super().__init__()
+        if n_group % 2 or HOP % n_group:
+            raise ValueError(f"n_group {n_group} must be even and divide the hop {HOP}")
+        if n_group > 8:
+            raise ValueError(f"n_group {n_group}: the coupling kernel holds at most 8 channels")
+        if n_early_size % 2:
+            raise ValueError(f"n_early_size {n_early_size} must be even")
+        self.n_mel_channels, self.n_flows, self.n_group = int(n_mel_channels), int(n_flows), int(n_group)
+        self.n_early_every, self.n_early_size = int(n_early_every), int(n_early_size)
+        self.hop = HOP
+        self.upsample = nn.ConvTranspose1d(n_mel_channels, n_mel_channels, UPSAMPLE_KERNEL, stride=HOP)
+        self.WN = nn.ModuleList()
+        self.convinv = nn.ModuleList()
+        n_half, n_rem = n_group // 2, n_group
+        for k in range(n_flows):
+            if k % n_early_every == 0 and k > 0:
+                n_half -= n_early_size // 2
+                n_rem -= n_early_size
+            if n_rem < 2:
+                raise ValueError("n_early_size / n_early_every leave no channels for the last flows")
+            self.convinv.append(_Invertible1x1Conv(n_rem))
+            self.WN.append(_WN(n_half, n_mel_channels * n_group, **WN_config))
+        self.n_remaining_channels = n_rem
+        self._folded = None
+        self._folded_key = None
+
+    @property
+    def noise_shapes(self):
+        """channel counts of the draws of `noise`, in order"""
+        early = [k for k in reversed(range(self.n_flows)) if k % self.n_early_every == 0 and k > 0]
+        return [self.n_remaining_channels] + [self.n_early_size] * len(early)
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        self._folded = None
+        return super().load_state_dict(fold_weight_norm_keys(state_dict), strict=strict, assign=assign)
+
+    # ---- weights in the kernels' layout, folded once (again only when a parameter changed) -------------------------
+    def _key(self):
+        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+
+    @staticmethod
+    def _gemm_weight(w: torch.Tensor, ldk: Optional[int] = None) -> torch.Tensor:
+        """Conv1d weight [Cout, Cin, taps] -> [taps, Cout, ldk] (radmmm_rowgemm_f32 layout 0), zero padded to ldk"""
+        Cout, Cin, taps = w.shape
+        ldk = ldk or Cin
+        W = torch.zeros(taps, Cout, ldk, device=w.device, dtype=torch.float32)
+        W[:, :, :Cin] = w.detach().float().permute(2, 0, 1)
+        return W
+
+    def _fold(self):
+        key = self._key()
+        if self._folded is not None and self._folded_key == key:
+            return self._folded
+        n_mel, ng = self.n_mel_channels, self.n_group
+        ldm = ops.round_up(n_mel, 4)
+        f = {"ldm": ldm, "ldk": ops.round_up(n_mel * ng, 4)}
+        f["up"] = (pack_polyphase(self.upsample.weight.detach().float(), HOP, 0, 0, ldm).contiguous(),
+                   f32c(self.upsample.bias.detach()).repeat(HOP))
+        flows = []
+        for wn, inv in zip(self.WN, self.convinv):
+            c = inv.conv.weight.shape[0]
+            Winv = torch.linalg.inv(inv.conv.weight.detach()[:, :, 0].double().cpu()).float().to(inv.conv.weight.device)
+            flows.append({
+                "c": c,
+                "start": (f32c(wn.start.weight.detach()[:, :, 0]), f32c(wn.start.bias.detach())),
+                "cond": (self._gemm_weight(wn.cond_layer.weight, f["ldk"]), f32c(wn.cond_layer.bias.detach())),
+                "in": [(self._gemm_weight(m.weight), f32c(m.bias.detach())) for m in wn.in_layers],
+                "rs": [(self._gemm_weight(m.weight), f32c(m.bias.detach())) for m in wn.res_skip_layers],
+                "end": (f32c(wn.end.weight.detach()[:, :, 0]), f32c(wn.end.bias.detach())),
+                "inv": Winv.contiguous(),
+            })
+        f["flows"] = flows
+        self._folded, self._folded_key = f, key
+        return f
+
+    def _noise_arg(self, noise, B: int, Tg: int, dev) -> Optional[list]:
+        if noise is None:
+            return None
+        shapes = self.noise_shapes
+        if len(noise) != len(shapes):
+            raise ValueError(f"noise must hold {len(shapes)} draws (channels {shapes}), got {len(noise)}")
+        out = []
+        for z, ch in zip(noise, shapes):
+            if tuple(z.shape) != (B, ch, Tg):
+                raise ValueError(f"noise draw of shape {tuple(z.shape)}, expected {(B, ch, Tg)}")
+            out.append(f32c(z.to(dev)))
+        return out
+
+    @fp32_region
+    def infer(self, mel: torch.Tensor, lens=None, sigma: float = 1.0, noise: Optional[Sequence[torch.Tensor]] = None
+              ) -> torch.Tensor:
+        if not mel.is_cuda:
+            raise RadmmmError("WaveGlow needs a GPU tensor (there is no CPU path)")
+        if mel.dim() != 3 or mel.shape[1] != self.n_mel_channels:
+            raise ValueError(f"mel must be [B, {self.n_mel_channels}, T], got {tuple(mel.shape)}")
+        B, _, T = mel.shape
+        lens_d, _ = _lens_arg(lens, B, T, mel.device)
+        return self._run(f32c(mel), lens_d, float(sigma), noise)
+
+    def _run(self, mel: torch.Tensor, lens_d: torch.Tensor, sigma: float, noise=None,
+             events: Optional[dict] = None) -> torch.Tensor:
+        """mel [B, n_mel, T] fp32 on the device, lens_d int32 [B] on the device (frames).  Items are processed in chunks
+        that keep every GEMM operand below 2 GiB (items are independent, so the chunking changes no value).
+        events: a dict that receives (start, end) device events per launch family of the LAST chunk, and its row count
+        under "rows" (timing)."""
+        B, _, T = mel.shape
+        dev = mel.device
+        per = HOP // self.n_group
+        Tg = T * per
+        noise = self._noise_arg(noise, B, Tg, dev)
+        f = self._fold()
+        wn = self.WN[0]
+        rows_cap = min(_A_OPERAND_BYTES // (4 * max(f["ldk"], wn.n_channels)),
+                       _COND_BYTES // (8 * wn.n_channels * wn.n_layers))
+        Bc = max(1, rows_cap // Tg)
+        audio = torch.empty(B, T * HOP, device=dev, dtype=torch.float32)
+        for b0 in range(0, B, Bc):
+            b1 = min(B, b0 + Bc)
+            self._run_chunk(f, mel[b0:b1], lens_d[b0:b1], sigma, None if noise is None else [z[b0:b1] for z in noise],
+                            audio[b0:b1], events if b1 == B else None)
+        return audio
+
+    def _run_chunk(self, f, mel, lens_d, sigma, noise, audio, events) -> None:
+        B, n_mel, T = mel.shape
+        dev = mel.device
+        ng = self.n_group
+        per = HOP // ng
+        Tg, R = T * per, B * T * per
+        wn0 = self.WN[0]
+        C, L, ksz = wn0.n_channels, wn0.n_layers, wn0.kernel_size
+        lens_g = lens_d * per
+        s = stream()
+        if events is not None:
+            events["rows"] = R
+
+        def timed(name):
+            if events is None:
+                return lambda: None
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            events.setdefault(name, []).append((e0, e1))
+            e0.record()
+            return e1.record
+
+        def empty(*shape):
+            return torch.empty(*shape, device=dev, dtype=torch.float32)
+
+        # upsample: one polyphase row GEMM over the mel frames, [B*T, HOP*n_mel] = channels-last [B*T*HOP, n_mel]
+        done = timed("upsample")
+        ldm, ldk = f["ldm"], f["ldk"]
+        xm = empty(B * T, ldm) if ldm == n_mel else torch.zeros(B * T, ldm, device=dev, dtype=torch.float32)
+        check(lib.radmmm_squeeze_rows(ptr(mel), ptr(xm), B, n_mel, T, 1, ldm, 0, s), "squeeze_rows")
+        Wp, bp = f["up"]
+        up = empty(B * T, HOP * n_mel)
+        rowgemm(A=xm, lda=ldm, B=Wp, ldb=Wp.shape[2], b_tap_stride=Wp.stride(0), C=up, ldc=HOP * n_mel, M=B * T,
+                N=HOP * n_mel, K=n_mel, taps=Wp.shape[0], dil=1, T=T, lens=lens_d, a_mask_mode=1, bias=bp, postmask=1)
+        ci = empty(R, ldk)
+        check(lib.radmmm_wg_group_cond(ptr(up), T * HOP * n_mel, ptr(ci), ldk, ptr(lens_g), B, Tg, n_mel, ng, s),
+              "wg_group_cond")
+        del up, xm
+        done()
+
+        X = empty(R, ng)
+        c = self.n_remaining_channels
+        zi = 0
+
+        def attach(ch, col0):
+            nonlocal zi
+            z = noise[zi] if noise is not None else torch.randn(B, ch, Tg, device=dev, dtype=torch.float32)
+            zi += 1
+            check(lib.radmmm_wg_noise_rows(ptr(z), sigma, ptr(X), ng, col0, ch, ptr(lens_g), B, Tg, s), "wg_noise_rows")
+
+        attach(c, ng - c)
+        cond = empty(R, 2 * C * L)
+        H, S, acts = empty(R, C), empty(R, C), empty(R, C)
+        A, rs = empty(R, 2 * C), empty(R, 2 * C)
+        for k in reversed(range(self.n_flows)):
+            fk = f["flows"][k]
+            assert fk["c"] == c
+            nh, col0 = c // 2, ng - c
+            Ws, bs = fk["start"]
+            done = timed("start")
+            check(lib.radmmm_wg_start(ptr(X), ng, col0, nh, ptr(Ws), ptr(bs), ptr(H), C, C, ptr(lens_g), R, Tg, s),
+                  "wg_start")
+            done()
+            Wc, bc = fk["cond"]
+            done = timed("cond_layer")
+            rowgemm(A=ci, lda=ldk, B=Wc, ldb=ldk, b_tap_stride=0, C=cond, ldc=2 * C * L, M=R, N=2 * C * L, K=n_mel * ng,
+                    taps=1, T=Tg, lens=lens_g, bias=bc)
+            done()
+            for i in range(L):
+                Wi, bi = fk["in"][i]
+                done = timed("in_layers")
+                rowgemm(A=H, lda=C, B=Wi, ldb=C, b_tap_stride=Wi.stride(0), C=A, ldc=2 * C, M=R, N=2 * C, K=C, taps=ksz,
+                        dil=2 ** i, T=Tg, lens=lens_g, a_mask_mode=1, bias=bi)
+                done()
+                done = timed("gate")
+                check(lib.radmmm_wg_gate(ptr(A), 2 * C, ptr(cond), 2 * C * L, 2 * C * i, ptr(acts), C, C, ptr(lens_g), R,
+                                         Tg, s), "wg_gate")
+                done()
+                last = i == L - 1
+                Wr, br = fk["rs"][i]
+                done = timed("res_skip_gemm")
+                rowgemm(A=acts, lda=C, B=Wr, ldb=C, b_tap_stride=0, C=rs, ldc=2 * C, M=R, N=C if last else 2 * C, K=C,
+                        taps=1, T=Tg, lens=lens_g, bias=br)
+                done()
+                done = timed("res_skip_update")
+                check(lib.radmmm_wg_res_skip(ptr(rs), 2 * C, ptr(H), C, ptr(S), C, C, int(i == 0), int(last),
+                                             ptr(lens_g), R, Tg, s), "wg_res_skip")
+                done()
+            We, be = fk["end"]
+            done = timed("end_coupling")
+            check(lib.radmmm_wg_end_coupling(ptr(S), C, ptr(We), ptr(be), ptr(fk["inv"]), ptr(X), ng, col0, nh, C,
+                                             ptr(lens_g), R, Tg, s), "wg_end_coupling")
+            done()
+            if k % self.n_early_every == 0 and k > 0:
+                attach(self.n_early_size, col0 - self.n_early_size)
+                c += self.n_early_size
+        assert c == ng
+        done = timed("ungroup")
+        check(lib.radmmm_wg_ungroup(ptr(X), ng, 0, ng, ptr(audio), audio.stride(0), ptr(lens_g), B, Tg, s), "wg_ungroup")
+        done()
+
+
+class WaveGlowDenoiser(Denoiser):
+    """Denoiser(waveglow, filter_length=1024, n_overlap=4, win_length=1024, mode='zeros') of
+    vocoders/waveglow_for_LIMMITS23/denoiser.py on the GPU: the bias spectrum is the magnitude of frame 0 of the STFT of
+    waveglow.infer(zeros(1, n_mel, 88), sigma=0), computed with the HIP path at the first call; forward is STFT ->
+    clamp(mag - bias * strength, 0) -> inverse STFT with the original phase.  The reference's tacotron2/stft.py and the
+    audio_processing.py the HiFi-GAN denoiser uses are the same transform (reflect pad, window-sum-square division,
+    filter_length / 2 trimmed at both ends), so everything but the bias is vocoder.Denoiser's.
+
+    forward(audio [B, S], strength=0.1, lens=None) -> [B, 1, (S // hop) * hop]; lens in samples."""
+
+    def __init__(self, waveglow: WaveGlow, filter_length=1024, n_overlap=4, win_length=1024, mode="zeros"):
+        super().__init__(waveglow, filter_length, n_overlap, win_length, mode)
+
+    def _bias(self, dev):
+        if self.bias_spec is None or self.bias_spec.device != dev:
+            wg = self.generator
+            audio = wg.infer(torch.zeros(1, wg.n_mel_channels, 88, device=dev), sigma=0.0)
+            spec = self._spectrum(audio, None, torch.ones(1, dtype=torch.int32, device=dev), 1)
+            mag = torch.empty(self.cutoff, device=dev, dtype=torch.float32)
+            check(lib.radmmm_voc_spec_bins(ptr(spec), self.ldk, 1, self.cutoff, None, 0.0, ptr(mag), stream()),
+                  "voc_spec_bins")
+            self.bias_spec = mag
+        return self.bias_spec
+
+
+@fp32_region
+def vocode_waveglow(model: WaveGlow, denoiser: Optional[WaveGlowDenoiser], mels: torch.Tensor, out_lens,
+                    sigma: float = 0.667, strength: float = 0.001, normalize: bool = True
+                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """mels [B, n_mel, T] + lengths in frames -> (audio [B, T*256] zero padded, sample lengths [B] int64 on the host
+    when out_lens was on the host, else on the device).  The waveglow branch of get_audio_for_mels
+    (vocoder_utils.py:49-58) for a whole batch: infer at `sigma`, denoiser at `strength`, and with normalize each item
+    divided by max|audio| over its own samples."""
+    if not mels.is_cuda:
+        raise RadmmmError("vocode_waveglow needs GPU tensors (there is no CPU path)")
+    B, _, T = mels.shape
+    dev = mels.device
+    lens_d, host = _lens_arg(out_lens, B, T, dev)
+    audio = model._run(f32c(mels), lens_d, float(sigma))
+    s_lens = host * HOP if host is not None else lens_d.long() * HOP
+    if denoiser is not None:
+        audio = denoiser(audio, strength, s_lens)[:, 0]
+    audio = audio.contiguous()
+    if normalize:
+        sl = lens_d * HOP if host is None else _to_device(s_lens, dev)
+        check(lib.radmmm_voc_normalize(ptr(audio), audio.shape[1], ptr(sl), B, audio.shape[1], stream()), "voc_normalize")
+    return audio, s_lens
+
+
+def config_of_module(m) -> dict:
+    """the constructor arguments of an unpickled reference WaveGlow module, read from its attributes"""
+    wn = m.WN[0]
+    return {"n_mel_channels": int(m.upsample.weight.shape[0]), "n_flows": int(m.n_flows), "n_group": int(m.n_group),
+            "n_early_every": int(m.n_early_every), "n_early_size": int(m.n_early_size),
+            "WN_config": {"n_layers": int(wn.n_layers), "n_channels": int(wn.n_channels),
+                          "kernel_size": int(wn.in_layers[0].kernel_size[0])}}
+
+
+def load_waveglow_vocoder(checkpoint_path: str, config_path: Optional[str] = None,
+                          device: Union[str, torch.device] = "cuda", allow_pickled_module: bool = False):
+    """load_waveglow_vocoder of vocoders/vocoder_utils.py:134-143.  Two checkpoint formats:
+      * a plain file {'state_dict': ..., 'waveglow_config': {...}} (see INTEGRATION.md for the one-line conversion);
+        without 'waveglow_config' the config JSON's "waveglow_config" section is used;
+      * the reference's own {'model': <pickled WaveGlow module>}: only with allow_pickled_module=True, because
+        unpickling a module runs whatever code the file names (load such files from sources you trust only) and needs
+        the reference's glow.py on sys.path (this package never imports it); its state_dict and attributes are
+        copied out.
+    The file is read with torch's restricted unpickler first; a file that this refuses is fully unpickled only when the
+    caller opted in.  Returns (waveglow, denoiser) on `device`, in eval mode."""
+    try:
+        ck = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
+    except pickle.UnpicklingError as e:
+        if not allow_pickled_module:
+            raise ValueError(f"{checkpoint_path} is not a plain {{'state_dict', 'waveglow_config'}} file ({e}); a "
+                             "reference checkpoint holding a pickled module loads with allow_pickled_module=True, or "
+                             "convert it once (INTEGRATION.md)") from e
+        ck = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
+    if "state_dict" in ck:
+        sd, cfg = ck["state_dict"], ck.get("waveglow_config")
+    elif "model" in ck:
+        sd, cfg = ck["model"].state_dict(), config_of_module(ck["model"])
+    else:
+        raise ValueError(f"{checkpoint_path}: neither 'state_dict' nor 'model' in the checkpoint")
+    if cfg is None:
+        if config_path is None:
+            raise ValueError("load_waveglow_vocoder: the checkpoint carries no 'waveglow_config' and no config_path given")
+        with open(config_path) as fh:
+            cfg = json.load(fh)
+        cfg = cfg.get("waveglow_config", cfg)
+    model = WaveGlow(**cfg)
+    model.load_state_dict(sd)
+    model = model.to(device).eval()
+    den = WaveGlowDenoiser(model).to(device).eval()
+    return model, den

@@ -1,0 +1,101 @@
+#!/usr/bin/env python3
+"""Batched WaveGlow benchmark (rad_mmm_amd/waveglow.py, csrc/waveglow.hip): one JSON line.
+
+    python tools/waveglow_bench.py [--batch 32] [--frames 800] [--iters 3] [--warmup 1]
+
+The shipped config (12 flows, 8 layers, 256 channels, n_group 8, 80 mels), random weights from a seed, every item at
+full length: device milliseconds of WaveGlow.infer (device events around the whole call, median after warm-up), audio
+seconds per second at 22050 Hz, the time of each launch family (events around every launch of one extra call; the last
+chunk of items only), and the in_layers row GEMMs' fraction of the fp32-MFMA peak (157.3 TFLOPS on
+paper, MI355X)."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+FP32_MFMA_PEAK = 157.3e12
+SHIPPED = dict(n_mel_channels=80, n_flows=12, n_group=8, n_early_every=4, n_early_size=2,
+               WN_config=dict(n_layers=8, n_channels=256, kernel_size=3))
+
+
+def seeded_state(model, seed):
+    """weights ~ N(0, 1 / fan_in) so that activations stay O(1) through 12 flows, biases ~ N(0, 0.1), end ~ N(0, 0.02)
+    (the reference's zero end layers would skip the coupling's arithmetic), convinv orthogonal"""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for k, v in model.state_dict().items():
+        if k.startswith("convinv"):
+            sd[k] = torch.linalg.qr(torch.randn(v.shape[0], v.shape[0], generator=g))[0].reshape(v.shape).contiguous()
+        elif k.endswith("bias"):
+            sd[k] = 0.1 * torch.randn(v.shape, generator=g)
+        elif ".end." in k:
+            sd[k] = 0.02 * torch.randn(v.shape, generator=g)
+        elif k == "upsample.weight":
+            sd[k] = torch.randn(v.shape, generator=g) / (4 * v.shape[0]) ** 0.5
+        else:
+            sd[k] = torch.randn(v.shape, generator=g) / (v.shape[1] * v.shape[2]) ** 0.5
+    return sd
+
+
+@torch.no_grad()
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--frames", type=int, default=800)
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--once", action="store_true", help="one untimed call only (for a kernel trace)")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("waveglow_bench needs an MI355X")
+    from rad_mmm_amd.waveglow import HOP, WaveGlow
+    dev = torch.device("cuda:0")
+    model = WaveGlow(**SHIPPED)
+    model.load_state_dict(seeded_state(model, 5))
+    model = model.to(dev).eval()
+    B, T = args.batch, args.frames
+    mel = (torch.randn(B, 80, T, generator=torch.Generator().manual_seed(6)) - 2.0).to(dev)
+    lens = [T] * B
+    if args.once:
+        model.infer(mel, lens, sigma=0.667)
+        torch.cuda.synchronize()
+        return
+    for _ in range(args.warmup):
+        model.infer(mel, lens, sigma=0.667)
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(args.iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        model.infer(mel, lens, sigma=0.667)
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    ms = float(np.median(ts))
+    events = {}
+    lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
+    model._run(mel, lens_d, 0.667, None, events)
+    torch.cuda.synchronize()
+    rows_chunk = events.pop("rows")
+    fam = {k: sum(a.elapsed_time(b) for a, b in v) for k, v in events.items()}
+    n_in = len(events["in_layers"])
+    wn = SHIPPED["WN_config"]
+    C = wn["n_channels"]
+    flop_in = 2.0 * 3 * C * 2 * C                       # per row and launch
+    in_tflops = flop_in * n_in * rows_chunk / (fam["in_layers"] * 1e-3) / 1e12 if fam["in_layers"] else 0.0
+    audio_s = B * T * HOP / 22050.0
+    out = {"metric": "waveglow_infer_ms", "batch": B, "frames": T, "device_ms": ms, "all_ms": ts,
+           "audio_seconds": audio_s, "audio_seconds_per_second": audio_s / (ms * 1e-3),
+           "last_chunk_family_ms": fam, "last_chunk_rows": rows_chunk, "rows": B * T * HOP // 8,
+           "in_layers_tflops": in_tflops, "in_layers_frac_of_fp32_mfma_peak": in_tflops * 1e12 / FP32_MFMA_PEAK}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -690,6 +690,30 @@ int radmmm_wg_end_coupling(const float* S, int lds, const float* Wend, const flo
 int radmmm_wg_ungroup(const float* X, int ldx, int col0, int n_group, float* audio, int64_t lda, const int32_t* lens,
                       int B, int Tg, radmmm_stream_t stream);
 
+/* The other direction of the same flow (glow.py:207-249 WaveGlow.forward: audio -> latent z and the terms of its
+ * likelihood), same conventions; the WN between the mix and the coupling is the launch sequence of the inverse
+ * direction (wg_start reads the mixed values).  Additive entry points of ABI 4.
+ *   wg_group_audio       X[(b*Tg + g)*ldx + j] = audio[b*lda + g*n_group + j], j < n_group, 0 for g >= lens[b] (the inverse
+ *                        of wg_ungroup; samples past an item's length are never read, so a NaN there cannot reach X)
+ *   wg_mix_fwd           X[r, col0 + i] = sum_j W[i*c + j] * X[r, col0 + j] in place, W = convinv.conv.weight itself,
+ *                        c even, 2 <= c <= 8
+ *   wg_end_coupling_fwd  o = Wend S[r] + bend; b = o[:n_half], log_s = o[n_half:]; X1 = exp(log_s) * X1 + b in place (X1 the
+ *                        second half of X[r, col0 : col0 + 2 n_half], the first half is not touched);
+ *                        ls[r] = (first ? 0 : ls[r]) + sum_i log_s[i]; log_s != NULL: log_s[r*n_half + i] = log_s[i].
+ *                        The limits of wg_end_coupling: n_half <= 4, 2 n_half * (C + 2 n_half + 1) <= 8192
+ *   wg_nll_parts         parts[b][0] = sum of X[r, j]^2 over the valid rows of item b and j < n_group, parts[b][1] = sum
+ *                        of ls[r] over the same rows; float64 sums in a fixed order, one workgroup per item, no
+ *                        atomics: bitwise repeatable, and an item's sums do not depend on the rest of the batch */
+int radmmm_wg_group_audio(const float* audio, int64_t lda, float* X, int ldx, int n_group, const int32_t* lens, int B,
+                          int Tg, radmmm_stream_t stream);
+int radmmm_wg_mix_fwd(float* X, int ldx, int col0, int c, const float* W, const int32_t* lens, int rows, int T,
+                      radmmm_stream_t stream);
+int radmmm_wg_end_coupling_fwd(const float* S, int lds, const float* Wend, const float* bend, float* X, int ldx, int col0,
+                               int n_half, int C, float* ls, int first, float* log_s, const int32_t* lens, int rows,
+                               int T, radmmm_stream_t stream);
+int radmmm_wg_nll_parts(const float* X, int ldx, int n_group, const float* ls, const int32_t* lens, int B, int Tg,
+                        double* parts, radmmm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Batched synthesis glue (TTSModel.sample_full / reconstruct_from_batch_attributes, tts_lightning_modules.py:286-437).
  * Additive entry points of ABI 4.  No floating-point atomics: every result is bitwise repeatable.

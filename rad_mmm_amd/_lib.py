@@ -219,6 +219,10 @@ def _load() -> C.CDLL:
         "radmmm_wg_res_skip": [p, i, p, i, p, i, i, i, i, p, i, i, p],
         "radmmm_wg_end_coupling": [p, i, p, p, p, p, i, i, i, i, p, i, i, p],
         "radmmm_wg_ungroup": [p, i, i, i, p, i64, p, i, i, p],
+        "radmmm_wg_group_audio": [p, i64, p, i, i, p, i, i, p],
+        "radmmm_wg_mix_fwd": [p, i, i, i, p, p, i, i, p],
+        "radmmm_wg_end_coupling_fwd": [p, i, p, p, p, i, i, i, i, p, i, p, p, i, i, p],
+        "radmmm_wg_nll_parts": [p, i, i, p, p, i, i, p, p],
         "radmmm_synth_durations": [p, i64, p, i, i, i, p, p, p, p],
         "radmmm_synth_regulate": [p, i64, i, i, i, p, p, i, i, p, i, p],
         "radmmm_synth_f0_stats": [p, i64, p, i64, p, i, i, p, i, p],

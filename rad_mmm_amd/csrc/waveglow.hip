@@ -14,9 +14,15 @@
 //   radmmm_wg_res_skip      audio += rs[:, :C]; skip (+)= rs[:, C:]   (last layer: skip += rs[:, :C] only)
 //   radmmm_wg_end_coupling  WN.end (C -> 2 n_half) + audio_1 = (audio_1 - b) * exp(-s) + the inverse 1x1 mix, in place
 //   radmmm_wg_ungroup       audio rows -> [B][Tg*n_group] samples, zeros past each length
+// and the other direction (glow.py:207-249 WaveGlow.forward: audio -> latent, with the terms of its likelihood), which
+// runs the same WN launches on the untouched half:
+//   radmmm_wg_group_audio       [B][Tg*n_group] samples -> audio rows (the inverse of wg_ungroup)
+//   radmmm_wg_mix_fwd           the forward 1x1 mix W on the live columns, in place
+//   radmmm_wg_end_coupling_fwd  WN.end + audio_1 = exp(log_s) * audio_1 + b, in place, + the row's sum of log_s
+//   radmmm_wg_nll_parts         per item: sum of z^2 and sum of the rows' log_s sums over its valid rows, in float64
 // All of them are bound by memory traffic (each reads or writes [rows][C] or [rows][2C] once); none uses atomics and
 // every output element is summed in an order that depends on its own row alone, so an item in a batch is bit-identical
-// to the item alone as far as these kernels go.
+// to the item alone as far as these kernels go (wg_nll_parts: on the item's own rows alone, in a fixed order).
 #include "common.h"
 
 namespace {
@@ -163,10 +169,41 @@ __global__ __launch_bounds__(256) void res_skip_kernel(const float* __restrict__
   }
 }
 
+// The part the two coupling kernels share: o = Wend S[r] (NO = 2 n_half outputs, bend is added by the caller).  16 lanes
+// share a row (a float4 of S per lane and 64 columns, xor-butterfly over the 16 lanes: every row is summed in the same
+// order wherever it sits), 16 rows per workgroup pass, Wend [NO][C] in LDS at w.
+template <int NO>
+__device__ __forceinline__ void end_dot(const float* __restrict__ S, int lds, const float* w, int C, long long r,
+                                        bool valid, int sub, float (&acc)[NO]) {
+#pragma unroll
+  for (int o = 0; o < NO; ++o) acc[o] = 0.f;
+  if (valid) {
+    const float* sr = S + r * lds;
+    for (int c = sub * 4; c < C; c += 64) {
+      const float4 v = *reinterpret_cast<const float4*>(sr + c);
+#pragma unroll
+      for (int o = 0; o < NO; ++o) {
+        const float4 ww = *reinterpret_cast<const float4*>(w + o * C + c);
+        acc[o] = fmaf(v.w, ww.w, fmaf(v.z, ww.z, fmaf(v.y, ww.y, fmaf(v.x, ww.x, acc[o]))));
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 0; o < NO; ++o) {
+#pragma unroll
+    for (int m = 8; m > 0; m >>= 1) acc[o] += __shfl_xor(acc[o], m, 16);
+  }
+}
+
+__device__ __forceinline__ bool row_valid(long long r, long long rows, const int32_t* lens, int T) {
+  if (r >= rows) return false;
+  if (!lens) return true;
+  const int b = (int)(r / T), t = (int)(r - (long long)b * T);
+  return t < lens[b];
+}
+
 // out = Wend S[r] + bend (NO = 2 n_half outputs: b = out[:n_half], s = out[n_half:]), z = [X0, (X1 - b) * exp(-s)],
-// X[r, col0 : col0 + NO] = Winv z; zeros past the item's length.  16 lanes share a row (a float4 of S per lane and 64
-// columns, xor-butterfly over the 16 lanes: every row is summed in the same order wherever it sits), 16 rows per
-// workgroup pass, Wend / Winv / bend in LDS.
+// X[r, col0 : col0 + NO] = Winv z; zeros past the item's length.  Wend / Winv / bend in LDS, the sum as end_dot.
 template <int NO>
 __global__ __launch_bounds__(256) void end_coupling_kernel(const float* __restrict__ S, int lds,
                                                            const float* __restrict__ Wend,
@@ -174,7 +211,7 @@ __global__ __launch_bounds__(256) void end_coupling_kernel(const float* __restri
                                                            const float* __restrict__ Winv, float* __restrict__ X,
                                                            int ldx, int col0, int C,
                                                            const int32_t* __restrict__ lens, long long rows, int T) {
-  extern __shared__ __align__(16) float sh[];   // float4 reads of Wend rows below
+  extern __shared__ __align__(16) float sh[];   // float4 reads of Wend rows in end_dot
   float* w = sh;                    // [NO][C]
   float* wi = sh + NO * C;          // [NO][NO]
   float* be = wi + NO * NO;         // [NO]
@@ -186,30 +223,9 @@ __global__ __launch_bounds__(256) void end_coupling_kernel(const float* __restri
   const int sub = threadIdx.x & 15, rloc = threadIdx.x >> 4;
   for (long long r0 = blockIdx.x * 16LL; r0 < rows; r0 += gridDim.x * 16LL) {
     const long long r = r0 + rloc;
-    bool valid = r < rows;
-    if (valid && lens) {
-      const int b = (int)(r / T), t = (int)(r - (long long)b * T);
-      valid = t < lens[b];
-    }
+    const bool valid = row_valid(r, rows, lens, T);
     float acc[NO];
-#pragma unroll
-    for (int o = 0; o < NO; ++o) acc[o] = 0.f;
-    if (valid) {
-      const float* sr = S + r * lds;
-      for (int c = sub * 4; c < C; c += 64) {
-        const float4 v = *reinterpret_cast<const float4*>(sr + c);
-#pragma unroll
-        for (int o = 0; o < NO; ++o) {
-          const float4 ww = *reinterpret_cast<const float4*>(w + o * C + c);
-          acc[o] = fmaf(v.w, ww.w, fmaf(v.z, ww.z, fmaf(v.y, ww.y, fmaf(v.x, ww.x, acc[o]))));
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 0; o < NO; ++o) {
-#pragma unroll
-      for (int m = 8; m > 0; m >>= 1) acc[o] += __shfl_xor(acc[o], m, 16);
-    }
+    end_dot<NO>(S, lds, w, C, r, valid, sub, acc);
     if (sub == 0 && r < rows) {
       float* xr = X + r * ldx + col0;
       float z[NO];
@@ -231,6 +247,163 @@ __global__ __launch_bounds__(256) void end_coupling_kernel(const float* __restri
         for (int o = 0; o < NO; ++o) xr[o] = 0.f;
       }
     }
+  }
+}
+
+// The forward counterpart: o = Wend S[r] + bend, b = o[:n_half], log_s = o[n_half:]; X1 = exp(log_s) * X1 + b in place
+// (X0 is not touched), ls[r] = (first ? 0 : ls[r]) + sum_i log_s[i], and with logs != NULL logs[r*n_half + i] =
+// log_s[i].  Rows past the item's length: X1, ls[r] and logs are written as 0.
+template <int NO>
+__global__ __launch_bounds__(256) void end_coupling_fwd_kernel(const float* __restrict__ S, int lds,
+                                                               const float* __restrict__ Wend,
+                                                               const float* __restrict__ bend, float* __restrict__ X,
+                                                               int ldx, int col0, int C, float* __restrict__ ls,
+                                                               int first, float* __restrict__ logs,
+                                                               const int32_t* __restrict__ lens, long long rows,
+                                                               int T) {
+  extern __shared__ __align__(16) float sh[];
+  float* w = sh;                    // [NO][C]
+  float* be = sh + NO * C;          // [NO]
+  for (int i = threadIdx.x; i < NO * C; i += blockDim.x) w[i] = Wend[i];
+  for (int i = threadIdx.x; i < NO; i += blockDim.x) be[i] = bend ? bend[i] : 0.f;
+  __syncthreads();
+  constexpr int NH = NO / 2;
+  const int sub = threadIdx.x & 15, rloc = threadIdx.x >> 4;
+  for (long long r0 = blockIdx.x * 16LL; r0 < rows; r0 += gridDim.x * 16LL) {
+    const long long r = r0 + rloc;
+    const bool valid = row_valid(r, rows, lens, T);
+    float acc[NO];
+    end_dot<NO>(S, lds, w, C, r, valid, sub, acc);
+    if (sub == 0 && r < rows) {
+      float* x1 = X + r * ldx + col0 + NH;
+      float sum = 0.f;
+#pragma unroll
+      for (int k = 0; k < NH; ++k) {
+        float v = 0.f, l = 0.f;
+        if (valid) {
+          l = acc[NH + k] + be[NH + k];
+          v = fmaf(expf(l), x1[k], acc[k] + be[k]);
+          sum += l;
+        }
+        x1[k] = v;
+        if (logs) logs[r * NH + k] = l;
+      }
+      ls[r] = (valid && !first) ? ls[r] + sum : sum;
+    }
+  }
+}
+
+template <int V> struct vec_of;
+template <> struct vec_of<1> { using type = float; };
+template <> struct vec_of<2> { using type = float2; };
+template <> struct vec_of<4> { using type = float4; };
+
+// X[r, col0 + i] = sum_j W[i*CC + j] * X[r, col0 + j] in place, one row per thread; V floats per access (4 where col0,
+// CC and ldx are multiples of 4 and X is 16-byte aligned, else 2, else 1).  Rows past the item's length are written as 0.
+template <int CC, int V>
+__global__ __launch_bounds__(256) void mix_fwd_kernel(float* __restrict__ X, int ldx, int col0,
+                                                      const float* __restrict__ W,
+                                                      const int32_t* __restrict__ lens, long long rows, int T) {
+  using vec = typename vec_of<V>::type;
+  __shared__ float w[CC * CC];
+  for (int i = threadIdx.x; i < CC * CC; i += blockDim.x) w[i] = W[i];
+  __syncthreads();
+  for (long long r = blockIdx.x * (long long)blockDim.x + threadIdx.x; r < rows;
+       r += (long long)gridDim.x * blockDim.x) {
+    float* xr = X + r * ldx + col0;
+    union { vec v[CC / V]; float f[CC]; } in, out;
+    if (row_valid(r, rows, lens, T)) {
+#pragma unroll
+      for (int q = 0; q < CC / V; ++q) in.v[q] = reinterpret_cast<const vec*>(xr)[q];
+#pragma unroll
+      for (int i = 0; i < CC; ++i) {
+        float a = 0.f;
+#pragma unroll
+        for (int j = 0; j < CC; ++j) a = fmaf(w[i * CC + j], in.f[j], a);
+        out.f[i] = a;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < CC; ++i) out.f[i] = 0.f;
+    }
+#pragma unroll
+    for (int q = 0; q < CC / V; ++q) reinterpret_cast<vec*>(xr)[q] = out.v[q];
+  }
+}
+
+// X[(b*Tg + g)*ldx + j] = audio[b*lda + g*ng + j] for g < lens[b], else 0 (a select: the samples past an item's length
+// are never read).  V floats per thread and access: 4 where ng, ldx and lda are multiples of 4 and both arrays aligned.
+template <int V>
+__global__ __launch_bounds__(256) void group_audio_kernel(const float* __restrict__ audio, long long lda,
+                                                          float* __restrict__ X, int ldx, int ng,
+                                                          const int32_t* __restrict__ lens, int B, int Tg) {
+  using vec = typename vec_of<V>::type;
+  const int q = ng / V;
+  const long long per = (long long)Tg * q;
+  const long long total = (long long)B * per;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / per);
+    const long long n = i - (long long)b * per;
+    const int g = (int)(n / q), j = (int)(n - (long long)g * q) * V;
+    vec v = vec();
+    if (!lens || g < lens[b]) v = *reinterpret_cast<const vec*>(audio + b * lda + (long long)g * ng + j);
+    *reinterpret_cast<vec*>(X + ((long long)b * Tg + g) * ldx + j) = v;
+  }
+}
+
+// parts[b][0] = sum over the valid rows g < lens[b] of item b and the columns j < ng of X[(b*Tg + g)*ldx + j]^2,
+// parts[b][1] = sum over the same rows of ls[b*Tg + g]; float64.  One workgroup per item and a fixed order: thread t sums
+// rows t, t + 1024, .. in that order, the 64 lanes of a wave combine in an xor butterfly, thread 0 adds the 16 waves'
+// sums in wave order.  No atomics, so two runs give the same bits and an item's sums do not depend on its neighbours.
+constexpr int NLL_THREADS = 1024;
+template <bool VEC>
+__global__ __launch_bounds__(NLL_THREADS) void nll_parts_kernel(const float* __restrict__ X, int ldx, int ng,
+                                                                const float* __restrict__ ls,
+                                                                const int32_t* __restrict__ lens, int Tg,
+                                                                double* __restrict__ parts) {
+  __shared__ double sh[2][NLL_THREADS / 64];
+  const int b = blockIdx.x;
+  int len = lens ? lens[b] : Tg;
+  len = len < 0 ? 0 : (len > Tg ? Tg : len);
+  double sq = 0.0, sl = 0.0;
+  for (int g = threadIdx.x; g < len; g += NLL_THREADS) {
+    const long long r = (long long)b * Tg + g;
+    const float* xr = X + r * ldx;
+    double a = 0.0;
+    if (VEC) {
+      for (int j = 0; j < ng; j += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(xr + j);
+        a += (double)v.x * v.x;
+        a += (double)v.y * v.y;
+        a += (double)v.z * v.z;
+        a += (double)v.w * v.w;
+      }
+    } else {
+      for (int j = 0; j < ng; ++j) a += (double)xr[j] * xr[j];
+    }
+    sq += a;
+    sl += (double)ls[r];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sq += __shfl_xor(sq, o, 64);
+    sl += __shfl_xor(sl, o, 64);
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) {
+    sh[0][wv] = sq;
+    sh[1][wv] = sl;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tq = 0.0, tl = 0.0;
+    for (int i = 0; i < NLL_THREADS / 64; ++i) {
+      tq += sh[0][i];
+      tl += sh[1][i];
+    }
+    parts[2 * b] = tq;
+    parts[2 * b + 1] = tl;
   }
 }
 
@@ -353,4 +526,98 @@ extern "C" int radmmm_wg_ungroup(const float* X, int ldx, int col0, int n_group,
   hipLaunchKernelGGL(ungroup_kernel, dim3(grid_for((long long)B * Tg * n_group, 256)), dim3(256), 0, ST(stream), X, ldx,
                      col0, n_group, audio, (long long)lda, lens, B, Tg);
   return radmmm::check_launch("wg_ungroup");
+}
+
+extern "C" int radmmm_wg_group_audio(const float* audio, int64_t lda, float* X, int ldx, int n_group,
+                                     const int32_t* lens, int B, int Tg, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(audio && X, "wg_group_audio: null pointer");
+  RADMMM_REQUIRE(B > 0 && Tg > 0 && n_group > 0 && ldx >= n_group && lda >= (int64_t)Tg * n_group &&
+                     (int64_t)B * Tg <= 0x7fffffffLL,
+                 "wg_group_audio: bad dims (B=%d Tg=%d n_group=%d ldx=%d lda=%lld)", B, Tg, n_group, ldx,
+                 (long long)lda);
+  const bool v4 = n_group % 4 == 0 && ldx % 4 == 0 && lda % 4 == 0 && radmmm::aligned16(audio) && radmmm::aligned16(X);
+  const long long total = (long long)B * Tg * (v4 ? n_group / 4 : n_group);
+  if (v4)
+    hipLaunchKernelGGL(group_audio_kernel<4>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), audio,
+                       (long long)lda, X, ldx, n_group, lens, B, Tg);
+  else
+    hipLaunchKernelGGL(group_audio_kernel<1>, dim3(grid_for(total, 256)), dim3(256), 0, ST(stream), audio,
+                       (long long)lda, X, ldx, n_group, lens, B, Tg);
+  return radmmm::check_launch("wg_group_audio");
+}
+
+extern "C" int radmmm_wg_mix_fwd(float* X, int ldx, int col0, int c, const float* W, const int32_t* lens, int rows,
+                                 int T, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(X && W, "wg_mix_fwd: null pointer");
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && c >= 2 && c <= 8 && c % 2 == 0 && col0 >= 0 && col0 + c <= ldx,
+                 "wg_mix_fwd: bad dims (rows=%d T=%d c=%d col0=%d ldx=%d; c even, 2 <= c <= 8)", rows, T, c, col0, ldx);
+  const bool a16 = radmmm::aligned16(X);
+  const int V = (a16 && ldx % 4 == 0 && col0 % 4 == 0 && c % 4 == 0)                                      ? 4
+                : ((reinterpret_cast<uintptr_t>(X) & 7) == 0 && ldx % 2 == 0 && col0 % 2 == 0) ? 2
+                                                                                                : 1;
+  const dim3 grid(grid_for(rows, 256)), block(256);
+#define WG_MIX(CV, VV) \
+  hipLaunchKernelGGL((mix_fwd_kernel<CV, VV>), grid, block, 0, ST(stream), X, ldx, col0, W, lens, (long long)rows, T)
+#define WG_MIX_V(CV)            \
+  do {                          \
+    if (V == 2) WG_MIX(CV, 2);  \
+    else WG_MIX(CV, 1);         \
+  } while (0)
+  switch (c) {
+    case 2: WG_MIX_V(2); break;
+    case 4:
+      if (V == 4) WG_MIX(4, 4);
+      else WG_MIX_V(4);
+      break;
+    case 6: WG_MIX_V(6); break;
+    default:
+      if (V == 4) WG_MIX(8, 4);
+      else WG_MIX_V(8);
+      break;
+  }
+#undef WG_MIX_V
+#undef WG_MIX
+  return radmmm::check_launch("wg_mix_fwd");
+}
+
+extern "C" int radmmm_wg_end_coupling_fwd(const float* S, int lds, const float* Wend, const float* bend, float* X, int ldx,
+                                          int col0, int n_half, int C, float* ls, int first, float* log_s,
+                                          const int32_t* lens, int rows, int T, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(S && Wend && X && ls, "wg_end_coupling_fwd: null pointer");
+  const int NO = 2 * n_half;
+  // the limit of wg_end_coupling, whose LDS also holds Winv: a model that runs one direction runs the other
+  const long long smem_twin = ((long long)NO * C + NO * NO + NO) * 4;
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && C > 0 && C % 4 == 0 && lds % 4 == 0 && lds >= C && n_half >= 1 &&
+                     n_half <= 4 && col0 >= 0 && col0 + NO <= ldx && smem_twin <= 32768,
+                 "wg_end_coupling_fwd: bad dims (rows=%d T=%d C=%d lds=%d n_half=%d col0=%d ldx=%d; n_half <= 4, "
+                 "(2 n_half)(C + 2 n_half + 1) <= 8192)", rows, T, C, lds, n_half, col0, ldx);
+  RADMMM_REQUIRE(radmmm::aligned16(S) && radmmm::aligned16(Wend), "wg_end_coupling_fwd: S / Wend must be 16B aligned");
+  const size_t smem = ((size_t)NO * C + NO) * 4;
+  const dim3 grid(grid_for(((long long)rows + 15) / 16, 1)), block(256);
+#define WG_END_FWD(NOV)                                                                                               \
+  hipLaunchKernelGGL(end_coupling_fwd_kernel<NOV>, grid, block, smem, ST(stream), S, lds, Wend, bend, X, ldx, col0, C, \
+                     ls, first, log_s, lens, (long long)rows, T)
+  switch (NO) {
+    case 2: WG_END_FWD(2); break;
+    case 4: WG_END_FWD(4); break;
+    case 6: WG_END_FWD(6); break;
+    default: WG_END_FWD(8); break;
+  }
+#undef WG_END_FWD
+  return radmmm::check_launch("wg_end_coupling_fwd");
+}
+
+extern "C" int radmmm_wg_nll_parts(const float* X, int ldx, int n_group, const float* ls, const int32_t* lens, int B,
+                                   int Tg, double* parts, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(X && ls && parts, "wg_nll_parts: null pointer");
+  RADMMM_REQUIRE(B > 0 && Tg > 0 && n_group > 0 && ldx >= n_group && (int64_t)B * Tg <= 0x7fffffffLL,
+                 "wg_nll_parts: bad dims (B=%d Tg=%d n_group=%d ldx=%d)", B, Tg, n_group, ldx);
+  RADMMM_REQUIRE((reinterpret_cast<uintptr_t>(parts) & 7) == 0, "wg_nll_parts: parts must be 8B aligned");
+  if (n_group % 4 == 0 && ldx % 4 == 0 && radmmm::aligned16(X))
+    hipLaunchKernelGGL(nll_parts_kernel<true>, dim3(B), dim3(NLL_THREADS), 0, ST(stream), X, ldx, n_group, ls, lens, Tg,
+                       parts);
+  else
+    hipLaunchKernelGGL(nll_parts_kernel<false>, dim3(B), dim3(NLL_THREADS), 0, ST(stream), X, ldx, n_group, ls, lens,
+                       Tg, parts);
+  return radmmm::check_launch("wg_nll_parts");
 }

@@ -17,6 +17,12 @@ exactly `stride` samples per frame is the reference's trim of kernel - stride sa
 layers, the 3-tap in_layers with dilation 2^i, the 1x1 res_skip layers.  Everything else (grouping the conditioning,
 start, the gate on a conditioning slice, the residual / skip update, end + inverse coupling + inverse 1x1 mix, the
 noise columns, un-grouping) is a kernel of csrc/waveglow.hip.
+
+The other direction, audio -> latent (glow.py:207-249 WaveGlow.forward, :43-59 WaveGlowLoss), runs the same WN launches
+on the untouched half: the audio enters the rows with all n_group columns live (wg_group_audio), each flow is the forward
+1x1 mix (wg_mix_fwd), the WN, and the forward coupling with the row's sum of log_s (wg_end_coupling_fwd); an early
+output is n_early_size columns that simply stop being live, so the final X IS z in the reference's channel order; the
+likelihood's two ragged sums are wg_nll_parts.  No backward pass: this evaluates a model, it does not train one.
 """
 from __future__ import annotations
 
@@ -107,7 +113,23 @@ class WaveGlow(nn.Module):
                                                     n_flows - 1 (glow.py:285-290: at every k > 0 with k % n_early_every
                                                     == 0), so noise[1] belongs to the largest such k
     Column g of every draw belongs to samples g*n_group .. g*n_group + n_group - 1; columns at or past an item's length
-    are ignored.  Item b alone at T = lens[b] with noise[:][b:b+1, :, :lens[b] * 256 / n_group] gives the same audio."""
+    are ignored.  Item b alone at T = lens[b] with noise[:][b:b+1, :, :lens[b] * 256 / n_group] gives the same audio.
+
+    analyze(mel [B, n_mel, T], audio [B, T * 256], lens=None, sigma=1.0) -> dict, everything on the device:
+        z          [B, n_group, Tg] fp32   the reference's layout (early outputs first), exactly 0 past each length
+        log_s_sum  [B] float64             sum of every coupling's log_s over the item's valid group steps
+        log_det_W  [n_flows] float64       log|det W_k|, per group step (not multiplied by the batch)
+        n_groups   [B] int64               valid group steps, lens[b] * 256 / n_group
+        nll        [B] float64             (sum z^2 / (2 sigma^2) - log_s_sum[b] - n_groups[b] * sum_k log_det_W[k])
+                                           / (n_groups[b] * n_group): nats per sample of item b
+        loss       [] float64              the same expression over the batch's sums and sum_b n_groups[b] * n_group
+    forward((mel, audio)) -> (z, log_s_list, log_det_W_list) as glow.py:207-249 (full lengths; log_det_W_list[k] =
+    B * Tg * log|det W_k|, glow.py:100) for WaveGlowLoss; noise_from_z(z) -> the tuple `noise` of infer, so that
+    infer(mel, lens, sigma=1.0, noise=noise_from_z(z)) returns the analysed audio.
+
+    Deliberate differences from the reference's forward: log|det W| where torch.logdet is NaN for a negative
+    determinant; with ragged lengths every sum and the normalisation run over an item's own valid samples (the
+    reference knows no lengths; with equal lengths `loss` equals WaveGlowLoss); lengths are given in mel frames."""
 
     def __init__(self, n_mel_channels, n_flows, n_group, n_early_every, n_early_size, WN_config):
         super().__init__()
@@ -168,10 +190,12 @@ class WaveGlow(nn.Module):
         f = {"ldm": ldm, "ldk": ops.round_up(n_mel * ng, 4)}
         f["up"] = (pack_polyphase(self.upsample.weight.detach().float(), HOP, 0, 0, ldm).contiguous(),
                    f32c(self.upsample.bias.detach()).repeat(HOP))
-        flows = []
+        flows, logdets = [], []
         for wn, inv in zip(self.WN, self.convinv):
             c = inv.conv.weight.shape[0]
-            Winv = torch.linalg.inv(inv.conv.weight.detach()[:, :, 0].double().cpu()).float().to(inv.conv.weight.device)
+            W64 = inv.conv.weight.detach()[:, :, 0].double().cpu()
+            Winv = torch.linalg.inv(W64).float().to(inv.conv.weight.device)
+            logdets.append(float(torch.linalg.slogdet(W64)[1]))
             flows.append({
                 "c": c,
                 "start": (f32c(wn.start.weight.detach()[:, :, 0]), f32c(wn.start.bias.detach())),
@@ -180,8 +204,10 @@ class WaveGlow(nn.Module):
                 "rs": [(self._gemm_weight(m.weight), f32c(m.bias.detach())) for m in wn.res_skip_layers],
                 "end": (f32c(wn.end.weight.detach()[:, :, 0]), f32c(wn.end.bias.detach())),
                 "inv": Winv.contiguous(),
+                "mix": f32c(inv.conv.weight.detach()[:, :, 0]),
             })
         f["flows"] = flows
+        f["logdet"] = torch.tensor(logdets, dtype=torch.float64).to(self.upsample.weight.device)
         self._folded, self._folded_key = f, key
         return f
 
@@ -209,6 +235,14 @@ class WaveGlow(nn.Module):
         lens_d, _ = _lens_arg(lens, B, T, mel.device)
         return self._run(f32c(mel), lens_d, float(sigma), noise)
 
+    def _chunk_items(self, f, Tg: int) -> int:
+        """items per chunk: every GEMM A operand stays below 2 GiB and the conditioning buffer below its cap (items
+        are independent, so the chunking changes no value)"""
+        wn = self.WN[0]
+        rows_cap = min(_A_OPERAND_BYTES // (4 * max(f["ldk"], wn.n_channels)),
+                       _COND_BYTES // (8 * wn.n_channels * wn.n_layers))
+        return max(1, rows_cap // Tg)
+
     def _run(self, mel: torch.Tensor, lens_d: torch.Tensor, sigma: float, noise=None,
              events: Optional[dict] = None) -> torch.Tensor:
         """mel [B, n_mel, T] fp32 on the device, lens_d int32 [B] on the device (frames).  Items are processed in chunks
@@ -221,10 +255,7 @@ class WaveGlow(nn.Module):
         Tg = T * per
         noise = self._noise_arg(noise, B, Tg, dev)
         f = self._fold()
-        wn = self.WN[0]
-        rows_cap = min(_A_OPERAND_BYTES // (4 * max(f["ldk"], wn.n_channels)),
-                       _COND_BYTES // (8 * wn.n_channels * wn.n_layers))
-        Bc = max(1, rows_cap // Tg)
+        Bc = self._chunk_items(f, Tg)
         audio = torch.empty(B, T * HOP, device=dev, dtype=torch.float32)
         for b0 in range(0, B, Bc):
             b1 = min(B, b0 + Bc)
@@ -232,16 +263,8 @@ class WaveGlow(nn.Module):
                             audio[b0:b1], events if b1 == B else None)
         return audio
 
-    def _run_chunk(self, f, mel, lens_d, sigma, noise, audio, events) -> None:
-        B, n_mel, T = mel.shape
-        dev = mel.device
-        ng = self.n_group
-        per = HOP // ng
-        Tg, R = T * per, B * T * per
-        wn0 = self.WN[0]
-        C, L, ksz = wn0.n_channels, wn0.n_layers, wn0.kernel_size
-        lens_g = lens_d * per
-        s = stream()
+    @staticmethod
+    def _timer(events: Optional[dict], R: int):
         if events is not None:
             events["rows"] = R
 
@@ -252,26 +275,94 @@ class WaveGlow(nn.Module):
             events.setdefault(name, []).append((e0, e1))
             e0.record()
             return e1.record
+        return timed
 
-        def empty(*shape):
-            return torch.empty(*shape, device=dev, dtype=torch.float32)
-
-        # upsample: one polyphase row GEMM over the mel frames, [B*T, HOP*n_mel] = channels-last [B*T*HOP, n_mel]
+    def _conditioning(self, f, mel, lens_d, lens_g, timed) -> torch.Tensor:
+        """upsample: one polyphase row GEMM over the mel frames, [B*T, HOP*n_mel] = channels-last [B*T*HOP, n_mel],
+        then grouped into the conditioning rows [R, ldk]"""
+        B, n_mel, T = mel.shape
+        dev = mel.device
+        ng = self.n_group
+        Tg = T * (HOP // ng)
+        s = stream()
         done = timed("upsample")
         ldm, ldk = f["ldm"], f["ldk"]
-        xm = empty(B * T, ldm) if ldm == n_mel else torch.zeros(B * T, ldm, device=dev, dtype=torch.float32)
+        xm = (torch.empty if ldm == n_mel else torch.zeros)(B * T, ldm, device=dev, dtype=torch.float32)
         check(lib.radmmm_squeeze_rows(ptr(mel), ptr(xm), B, n_mel, T, 1, ldm, 0, s), "squeeze_rows")
         Wp, bp = f["up"]
-        up = empty(B * T, HOP * n_mel)
+        up = torch.empty(B * T, HOP * n_mel, device=dev, dtype=torch.float32)
         rowgemm(A=xm, lda=ldm, B=Wp, ldb=Wp.shape[2], b_tap_stride=Wp.stride(0), C=up, ldc=HOP * n_mel, M=B * T,
                 N=HOP * n_mel, K=n_mel, taps=Wp.shape[0], dil=1, T=T, lens=lens_d, a_mask_mode=1, bias=bp, postmask=1)
-        ci = empty(R, ldk)
+        ci = torch.empty(B * Tg, ldk, device=dev, dtype=torch.float32)
         check(lib.radmmm_wg_group_cond(ptr(up), T * HOP * n_mel, ptr(ci), ldk, ptr(lens_g), B, Tg, n_mel, ng, s),
               "wg_group_cond")
         del up, xm
         done()
+        return ci
 
-        X = empty(R, ng)
+    def _wn_buffers(self, R: int, dev):
+        wn0 = self.WN[0]
+        C, L = wn0.n_channels, wn0.n_layers
+
+        def empty(*shape):
+            return torch.empty(*shape, device=dev, dtype=torch.float32)
+        return {"cond": empty(R, 2 * C * L), "H": empty(R, C), "S": empty(R, C), "acts": empty(R, C),
+                "A": empty(R, 2 * C), "rs": empty(R, 2 * C)}
+
+    def _wn(self, f, fk, X, col0: int, nh: int, ci, bufs, lens_g, R: int, Tg: int, timed) -> torch.Tensor:
+        """the WN of one flow on the untouched half X[:, col0 : col0 + nh], the same launches in both directions: start,
+        cond_layer for all layers, then per layer the dilated in_layer GEMM, the gate, the res_skip GEMM and the
+        residual / skip update.  Returns the skip sum S [R, C], the input of `end`."""
+        wn0 = self.WN[0]
+        C, L, ksz = wn0.n_channels, wn0.n_layers, wn0.kernel_size
+        ng, ldk = self.n_group, f["ldk"]
+        cond, H, S, acts, A, rs = (bufs[n] for n in ("cond", "H", "S", "acts", "A", "rs"))
+        s = stream()
+        Ws, bs = fk["start"]
+        done = timed("start")
+        check(lib.radmmm_wg_start(ptr(X), ng, col0, nh, ptr(Ws), ptr(bs), ptr(H), C, C, ptr(lens_g), R, Tg, s),
+              "wg_start")
+        done()
+        Wc, bc = fk["cond"]
+        done = timed("cond_layer")
+        rowgemm(A=ci, lda=ldk, B=Wc, ldb=ldk, b_tap_stride=0, C=cond, ldc=2 * C * L, M=R, N=2 * C * L,
+                K=self.n_mel_channels * ng, taps=1, T=Tg, lens=lens_g, bias=bc)
+        done()
+        for i in range(L):
+            Wi, bi = fk["in"][i]
+            done = timed("in_layers")
+            rowgemm(A=H, lda=C, B=Wi, ldb=C, b_tap_stride=Wi.stride(0), C=A, ldc=2 * C, M=R, N=2 * C, K=C, taps=ksz,
+                    dil=2 ** i, T=Tg, lens=lens_g, a_mask_mode=1, bias=bi)
+            done()
+            done = timed("gate")
+            check(lib.radmmm_wg_gate(ptr(A), 2 * C, ptr(cond), 2 * C * L, 2 * C * i, ptr(acts), C, C, ptr(lens_g), R,
+                                     Tg, s), "wg_gate")
+            done()
+            last = i == L - 1
+            Wr, br = fk["rs"][i]
+            done = timed("res_skip_gemm")
+            rowgemm(A=acts, lda=C, B=Wr, ldb=C, b_tap_stride=0, C=rs, ldc=2 * C, M=R, N=C if last else 2 * C, K=C,
+                    taps=1, T=Tg, lens=lens_g, bias=br)
+            done()
+            done = timed("res_skip_update")
+            check(lib.radmmm_wg_res_skip(ptr(rs), 2 * C, ptr(H), C, ptr(S), C, C, int(i == 0), int(last),
+                                         ptr(lens_g), R, Tg, s), "wg_res_skip")
+            done()
+        return S
+
+    def _run_chunk(self, f, mel, lens_d, sigma, noise, audio, events) -> None:
+        B, n_mel, T = mel.shape
+        dev = mel.device
+        ng = self.n_group
+        per = HOP // ng
+        Tg, R = T * per, B * T * per
+        C = self.WN[0].n_channels
+        lens_g = lens_d * per
+        s = stream()
+        timed = self._timer(events, R)
+        ci = self._conditioning(f, mel, lens_d, lens_g, timed)
+
+        X = torch.empty(R, ng, device=dev, dtype=torch.float32)
         c = self.n_remaining_channels
         zi = 0
 
@@ -282,43 +373,12 @@ class WaveGlow(nn.Module):
             check(lib.radmmm_wg_noise_rows(ptr(z), sigma, ptr(X), ng, col0, ch, ptr(lens_g), B, Tg, s), "wg_noise_rows")
 
         attach(c, ng - c)
-        cond = empty(R, 2 * C * L)
-        H, S, acts = empty(R, C), empty(R, C), empty(R, C)
-        A, rs = empty(R, 2 * C), empty(R, 2 * C)
+        bufs = self._wn_buffers(R, dev)
         for k in reversed(range(self.n_flows)):
             fk = f["flows"][k]
             assert fk["c"] == c
             nh, col0 = c // 2, ng - c
-            Ws, bs = fk["start"]
-            done = timed("start")
-            check(lib.radmmm_wg_start(ptr(X), ng, col0, nh, ptr(Ws), ptr(bs), ptr(H), C, C, ptr(lens_g), R, Tg, s),
-                  "wg_start")
-            done()
-            Wc, bc = fk["cond"]
-            done = timed("cond_layer")
-            rowgemm(A=ci, lda=ldk, B=Wc, ldb=ldk, b_tap_stride=0, C=cond, ldc=2 * C * L, M=R, N=2 * C * L, K=n_mel * ng,
-                    taps=1, T=Tg, lens=lens_g, bias=bc)
-            done()
-            for i in range(L):
-                Wi, bi = fk["in"][i]
-                done = timed("in_layers")
-                rowgemm(A=H, lda=C, B=Wi, ldb=C, b_tap_stride=Wi.stride(0), C=A, ldc=2 * C, M=R, N=2 * C, K=C, taps=ksz,
-                        dil=2 ** i, T=Tg, lens=lens_g, a_mask_mode=1, bias=bi)
-                done()
-                done = timed("gate")
-                check(lib.radmmm_wg_gate(ptr(A), 2 * C, ptr(cond), 2 * C * L, 2 * C * i, ptr(acts), C, C, ptr(lens_g), R,
-                                         Tg, s), "wg_gate")
-                done()
-                last = i == L - 1
-                Wr, br = fk["rs"][i]
-                done = timed("res_skip_gemm")
-                rowgemm(A=acts, lda=C, B=Wr, ldb=C, b_tap_stride=0, C=rs, ldc=2 * C, M=R, N=C if last else 2 * C, K=C,
-                        taps=1, T=Tg, lens=lens_g, bias=br)
-                done()
-                done = timed("res_skip_update")
-                check(lib.radmmm_wg_res_skip(ptr(rs), 2 * C, ptr(H), C, ptr(S), C, C, int(i == 0), int(last),
-                                             ptr(lens_g), R, Tg, s), "wg_res_skip")
-                done()
+            S = self._wn(f, fk, X, col0, nh, ci, bufs, lens_g, R, Tg, timed)
             We, be = fk["end"]
             done = timed("end_coupling")
             check(lib.radmmm_wg_end_coupling(ptr(S), C, ptr(We), ptr(be), ptr(fk["inv"]), ptr(X), ng, col0, nh, C,
@@ -331,6 +391,134 @@ class WaveGlow(nn.Module):
         done = timed("ungroup")
         check(lib.radmmm_wg_ungroup(ptr(X), ng, 0, ng, ptr(audio), audio.stride(0), ptr(lens_g), B, Tg, s), "wg_ungroup")
         done()
+
+    # ---- audio -> latent ---------------------------------------------------------------------------------------------
+    def _args_fwd(self, mel, audio):
+        if not (mel.is_cuda and audio.is_cuda):
+            raise RadmmmError("WaveGlow needs GPU tensors (there is no CPU path)")
+        if mel.dim() != 3 or mel.shape[1] != self.n_mel_channels:
+            raise ValueError(f"mel must be [B, {self.n_mel_channels}, T], got {tuple(mel.shape)}")
+        B, _, T = mel.shape
+        if tuple(audio.shape) != (B, T * HOP):
+            raise ValueError(f"audio must be [B, T * {HOP}] = {(B, T * HOP)}, got {tuple(audio.shape)}")
+        return f32c(mel), f32c(audio)
+
+    def _analyze_run(self, mel, audio, lens_d, want_log_s: bool = False, events: Optional[dict] = None):
+        """mel [B, n_mel, T], audio [B, T*HOP] fp32 on the device, lens_d int32 [B] on the device (frames) ->
+        (z rows [B*Tg, n_group], parts [B, 2] float64 = (sum z^2, sum log_s) per item, the per-flow log_s rows
+        [B*Tg, n_half_k] or None).  Chunked over items as _run; events as there."""
+        B, _, T = mel.shape
+        dev = mel.device
+        ng = self.n_group
+        Tg = T * (HOP // ng)
+        f = self._fold()
+        Bc = self._chunk_items(f, Tg)
+        X = torch.empty(B * Tg, ng, device=dev, dtype=torch.float32)
+        ls = torch.empty(B * Tg, device=dev, dtype=torch.float32)
+        parts = torch.empty(B, 2, device=dev, dtype=torch.float64)
+        logs = None
+        if want_log_s:
+            logs = [torch.empty(B * Tg, fk["c"] // 2, device=dev, dtype=torch.float32) for fk in f["flows"]]
+        for b0 in range(0, B, Bc):
+            b1 = min(B, b0 + Bc)
+            r0, r1 = b0 * Tg, b1 * Tg
+            self._analyze_chunk(f, mel[b0:b1], audio[b0:b1], lens_d[b0:b1], X[r0:r1], ls[r0:r1], parts[b0:b1],
+                                None if logs is None else [t[r0:r1] for t in logs], events if b1 == B else None)
+        return X, parts, logs
+
+    def _analyze_chunk(self, f, mel, audio, lens_d, X, ls, parts, logs, events) -> None:
+        B, _, T = mel.shape
+        ng = self.n_group
+        per = HOP // ng
+        Tg, R = T * per, B * T * per
+        C = self.WN[0].n_channels
+        lens_g = lens_d * per
+        s = stream()
+        timed = self._timer(events, R)
+        ci = self._conditioning(f, mel, lens_d, lens_g, timed)
+        done = timed("group_audio")
+        check(lib.radmmm_wg_group_audio(ptr(audio), audio.stride(0), ptr(X), ng, ng, ptr(lens_g), B, Tg, s),
+              "wg_group_audio")
+        done()
+        bufs = self._wn_buffers(R, mel.device)
+        c = ng
+        for k in range(self.n_flows):
+            if k % self.n_early_every == 0 and k > 0:
+                c -= self.n_early_size              # an early output: its columns stay where they are, as part of z
+            fk = f["flows"][k]
+            assert fk["c"] == c
+            nh, col0 = c // 2, ng - c
+            done = timed("mix_fwd")
+            check(lib.radmmm_wg_mix_fwd(ptr(X), ng, col0, c, ptr(fk["mix"]), ptr(lens_g), R, Tg, s), "wg_mix_fwd")
+            done()
+            S = self._wn(f, fk, X, col0, nh, ci, bufs, lens_g, R, Tg, timed)
+            We, be = fk["end"]
+            done = timed("end_coupling_fwd")
+            check(lib.radmmm_wg_end_coupling_fwd(ptr(S), C, ptr(We), ptr(be), ptr(X), ng, col0, nh, C, ptr(ls),
+                                                 int(k == 0), None if logs is None else ptr(logs[k]), ptr(lens_g), R,
+                                                 Tg, s), "wg_end_coupling_fwd")
+            done()
+        assert c == self.n_remaining_channels
+        done = timed("nll_parts")
+        check(lib.radmmm_wg_nll_parts(ptr(X), ng, ng, ptr(ls), ptr(lens_g), B, Tg, ptr(parts), s), "wg_nll_parts")
+        done()
+
+    @fp32_region
+    def analyze(self, mel: torch.Tensor, audio: torch.Tensor, lens=None, sigma: float = 1.0) -> dict:
+        mel, audio = self._args_fwd(mel, audio)
+        B, _, T = mel.shape
+        ng = self.n_group
+        Tg = T * (HOP // ng)
+        lens_d, _ = _lens_arg(lens, B, T, mel.device)
+        X, parts, _ = self._analyze_run(mel, audio, lens_d)
+        logdet = self._fold()["logdet"]
+        n_groups = lens_d.long() * (HOP // ng)
+        sq, log_s_sum = parts[:, 0], parts[:, 1]
+        num = sq / (2.0 * float(sigma) ** 2) - log_s_sum - n_groups * logdet.sum()
+        return {"z": X.view(B, Tg, ng).transpose(1, 2).contiguous(), "log_s_sum": log_s_sum, "log_det_W": logdet,
+                "n_groups": n_groups, "nll": num / (n_groups * ng), "loss": num.sum() / (n_groups.sum() * ng)}
+
+    @fp32_region
+    def forward(self, forward_input):
+        mel, audio = forward_input
+        mel, audio = self._args_fwd(mel, audio)
+        B, _, T = mel.shape
+        ng = self.n_group
+        Tg = T * (HOP // ng)
+        lens_d, _ = _lens_arg(None, B, T, mel.device)
+        X, _, logs = self._analyze_run(mel, audio, lens_d, want_log_s=True)
+        logdet = self._fold()["logdet"]
+        z = X.view(B, Tg, ng).transpose(1, 2).contiguous()
+        log_s_list = [t.view(B, Tg, -1).transpose(1, 2).contiguous() for t in logs]
+        return z, log_s_list, [logdet[k] * (B * Tg) for k in range(self.n_flows)]
+
+    def noise_from_z(self, z: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+        """z [B, n_group, Tg] of analyze / forward -> the draws of infer's `noise`: the last n_remaining_channels
+        channels, then the early blocks from the latest exit to the earliest"""
+        if z.dim() != 3 or z.shape[1] != self.n_group:
+            raise ValueError(f"z must be [B, {self.n_group}, Tg], got {tuple(z.shape)}")
+        lo = self.n_group - self.n_remaining_channels
+        out = [z[:, lo:]]
+        while lo > 0:
+            out.append(z[:, lo - self.n_early_size:lo])
+            lo -= self.n_early_size
+        return tuple(t.contiguous() for t in out)
+
+
+class WaveGlowLoss(nn.Module):
+    """WaveGlowLoss(sigma) of glow.py:43-59 on the tuple WaveGlow.forward returns:
+    (sum z^2 / (2 sigma^2) - sum log_s - sum log_det_W) / z.numel(), a few reductions in float64"""
+
+    def __init__(self, sigma: float = 1.0):
+        super().__init__()
+        self.sigma = float(sigma)
+
+    def forward(self, model_output):
+        z, log_s_list, log_det_W_list = model_output
+        log_s_total = sum(t.double().sum() for t in log_s_list)
+        log_det_W_total = sum(t.double() for t in log_det_W_list)
+        loss = (z.double() ** 2).sum() / (2.0 * self.sigma * self.sigma) - log_s_total - log_det_W_total
+        return loss / z.numel()
 
 
 class WaveGlowDenoiser(Denoiser):

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Batched WaveGlow benchmark (rad_mmm_amd/waveglow.py, csrc/waveglow.hip): one JSON line.
 
-    python tools/waveglow_bench.py [--batch 32] [--frames 800] [--iters 3] [--warmup 1]
+    python tools/waveglow_bench.py [--batch 32] [--frames 800] [--iters 3] [--warmup 1] [--analyze]
 
 The shipped config (12 flows, 8 layers, 256 channels, n_group 8, 80 mels), random weights from a seed, every item at
 full length: device milliseconds of WaveGlow.infer (device events around the whole call, median after warm-up), audio
 seconds per second at 22050 Hz, the time of each launch family (events around every launch of one extra call; the last
 chunk of items only), and the in_layers row GEMMs' fraction of the fp32-MFMA peak (157.3 TFLOPS on
-paper, MI355X)."""
+paper, MI355X).  --analyze adds the other direction in the same run and at the same shape: WaveGlow.analyze on seeded
+audio, timed the same way, under "analyze" in the same JSON line with the ratio analyze / infer and the time of the
+launch families only that direction has (group_audio, mix_fwd, end_coupling_fwd, nll_parts)."""
 import argparse
 import json
 import os
@@ -51,6 +53,7 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--once", action="store_true", help="one untimed call only (for a kernel trace)")
+    ap.add_argument("--analyze", action="store_true", help="also time WaveGlow.analyze (audio -> latent) at the same shape")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("waveglow_bench needs an MI355X")
@@ -94,6 +97,28 @@ def main():
            "audio_seconds": audio_s, "audio_seconds_per_second": audio_s / (ms * 1e-3),
            "last_chunk_family_ms": fam, "last_chunk_rows": rows_chunk, "rows": B * T * HOP // 8,
            "in_layers_tflops": in_tflops, "in_layers_frac_of_fp32_mfma_peak": in_tflops * 1e12 / FP32_MFMA_PEAK}
+    if args.analyze:
+        audio = (0.3 * torch.randn(B, T * HOP, generator=torch.Generator().manual_seed(7))).to(dev)
+        for _ in range(args.warmup):
+            model.analyze(mel, audio, lens)
+        torch.cuda.synchronize()
+        ta = []
+        for _ in range(args.iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            model.analyze(mel, audio, lens)
+            e1.record()
+            e1.synchronize()
+            ta.append(e0.elapsed_time(e1))
+        ms_a = float(np.median(ta))
+        events = {}
+        model._analyze_run(mel, audio, lens_d, False, events)
+        torch.cuda.synchronize()
+        events.pop("rows")
+        fam_a = {k: sum(a.elapsed_time(b) for a, b in v) for k, v in events.items()}
+        new = ("group_audio", "mix_fwd", "end_coupling_fwd", "nll_parts")
+        out["analyze"] = {"device_ms": ms_a, "all_ms": ta, "ratio_to_infer": ms_a / ms, "last_chunk_family_ms": fam_a,
+                          "new_families_ms": sum(fam_a[k] for k in new)}
     print(json.dumps(out))
 
 

@@ -96,7 +96,10 @@ typedef struct { int fmt; int x8_exp; int32_t* sat_flag;
 typedef struct {
   const float* A; int lda;
   int64_t a_item_stride; /* 0: row r at A + r*lda; else item b, frame t at A + b*a_item_stride + t*lda
-                            (rows of one item may then overlap: lda < K is allowed, STFT framing) */
+                            (rows of one item may then overlap: lda < K is allowed, STFT framing).  With a_mask_mode 1
+                            an item may hold more frames than the T that are written (lens[b] > T, the inverse STFT's
+                            F = T + 1): a tap then reads frames up to min(lens[b], T + taps/2 * dil) - 1 of that item,
+                            the last item included, so the caller's buffer must hold every frame below lens[b] */
   const float* B; int ldb; int64_t b_tap_stride; int b_layout;
   float* C; int ldc;      /* radmmm_rowgemm_h3: may be NULL when Ch is given (no fp32 copy of the result is written) */
   int M, N, K;

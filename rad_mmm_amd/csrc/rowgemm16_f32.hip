@@ -357,8 +357,14 @@ int radmmm::launch_rowgemm16(const radmmm_rowgemm_desc& d, hipStream_t stream) {
     }
   }
   // byte extents of the operands for the buffer descriptors
+  // With a_item_stride and a_mask_mode 1 an item may hold more frames than the T that are written (lens[b] > T: the
+  // inverse STFT reads F = T + 1 frames per item), so a tap of the LAST item may reach taps/2 * dil frames past T - 1;
+  // the descriptor must span them, or that item reads zeros there while every other item reads the frames.  lens lives
+  // on the device, so the launcher cannot tell whether the last item is that long and always spans the reach; the
+  // kernel still masks every frame at or above lens[b], so the wider extent admits only frames the caller holds.
   const long long items = d.M / d.T;
-  const long long a_last = d.a_item_stride ? (items - 1) * d.a_item_stride + (long long)(d.T - 1) * d.lda
+  const long long reach = (d.a_item_stride && d.a_mask_mode && d.lens) ? (long long)(d.taps / 2) * d.dil : 0;
+  const long long a_last = d.a_item_stride ? (items - 1) * d.a_item_stride + (d.T - 1 + reach) * d.lda
                                            : (long long)(d.M - 1) * d.lda;
   const long long a_bytes = (a_last + d.K) * 4;
   // (measured on gfx950: the scalar offset IS part of the hardware range check, so the descriptor

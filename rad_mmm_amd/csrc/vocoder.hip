@@ -30,10 +30,10 @@ inline int grid_for(long long total, int block) {
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 // y[r, c] = lrelu(x[r, c] / div) for t < lens[b] (c < cols), 0 otherwise and in the padding columns
-// cols <= c < ldy.  ldx, ldy % 4 == 0: one float4 per thread.
-__global__ __launch_bounds__(256) void lrelu_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y,
-                                                    int ldy, long long rows, int cols, int T,
-                                                    const int32_t* __restrict__ lens, float div, float slope) {
+// cols <= c < ldy.  ldx, ldy % 4 == 0: one float4 per thread.  x and y carry no __restrict__: the generator calls this
+// in place (y == x, ldy == ldx), where every thread loads its float4 before it stores the same four floats.
+__global__ __launch_bounds__(256) void lrelu_kernel(const float* x, int ldx, float* y, int ldy, long long rows, int cols,
+                                                    int T, const int32_t* __restrict__ lens, float div, float slope) {
   const int q = ldy >> 2;
   const long long total = rows * q;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
@@ -177,7 +177,9 @@ __global__ __launch_bounds__(256) void istft_finish_kernel(float* __restrict__ y
   }
 }
 
-// audio[b, :] *= 1 / max|audio[b, :lens[b]]| (as a division, like the reference); one workgroup per item.
+// audio[b, :lens[b]] /= max|audio[b, :lens[b]]| (a division, like the reference); samples at or past lens[b] are
+// neither read nor written.  An all-zero item becomes NaN (0 / 0), as the reference's audio / max|audio| does.  One
+// workgroup per item.
 __global__ __launch_bounds__(1024) void normalize_kernel(float* __restrict__ audio, int lda,
                                                          const int32_t* __restrict__ lens, int S) {
   __shared__ float sh[17];

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _vocoder_kernels_ref as K
 from _vocoder_ref import V1, denoise_ref, generator_ref, load_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -192,3 +193,171 @@ def test_new_entry_points_bound_with_the_header_arity():
         fn = getattr(L.lib, name)
         assert len(fn.argtypes) == len(args.split(",")), name
     assert L.lib.radmmm_abi_version() == 4
+
+
+# ---- the per-kernel restatements of tests/_vocoder_kernels_ref.py (the oracle of tests/test_hip_vocoder_direct.py) ----
+
+
+@pytest.mark.parametrize("pad,S,lens", [(0, 5, [5, 1]), (3, 11, [11, 4, 7]), (512, 1500, [1500, 513, 900])])
+def test_reflect_pad_restatement_equals_numpy_pad(pad, S, lens):
+    g = np.random.default_rng(pad + S)
+    a = g.standard_normal((len(lens), S + 2))
+    pitch = S + 2 * pad + 3
+    out = K.reflect_pad_ref(a, lens, S, pad, pitch)
+    for b, n in enumerate(lens):
+        assert np.array_equal(out[b, :n + 2 * pad], np.pad(a[b, :n], pad, mode="reflect"))
+        assert not out[b, n + 2 * pad:].any()
+    full = K.reflect_pad_ref(a, None, S, pad, pitch)                         # lens = NULL: every item has S samples
+    assert np.array_equal(full[:, :S + 2 * pad], np.pad(a[:, :S], ((0, 0), (pad, pad)), mode="reflect"))
+
+
+def test_spec_bins_restatement_equals_the_polar_round_trip():
+    c = dict(cutoff=7, lds=17, rows=12, strength=0.5, seed=5)
+    for strength in (0.5, -0.5, 0.0):
+        inp = K.spec_inputs(dict(c, strength=strength))
+        out = K.spec_bins_ref(inp["spec"], 7, inp["bias"], strength)
+        s = inp["spec"].astype(np.float64)
+        re, im = s[:, :7], s[:, 7:14]
+        mag = np.clip(np.sqrt(re ** 2 + im ** 2) - inp["bias"].astype(np.float64) * strength, 0.0, None)
+        ph = np.arctan2(im, re)                                              # atan2(0, 0) = 0
+        assert np.abs(out[:, :7] - mag * np.cos(ph)).max() < 1e-14 * max(1.0, mag.max())
+        assert np.abs(out[:, 7:14] - mag * np.sin(ph)).max() < 1e-14 * max(1.0, mag.max())
+        assert np.array_equal(out[:, 14:], s[:, 14:])
+        assert (mag[inp["spec"][:, :7] ** 2 + inp["spec"][:, 7:14] ** 2 == 0] > 0).any() == (strength < 0)
+
+
+@pytest.mark.parametrize("n_fft,hop,S,lens", [(64, 16, 200, [200, 33, 96, 131]), (1024, 256, 1800, [1800, 513, 1024])])
+def test_kernel_chain_restatement_equals_the_denoiser_restatement(n_fft, hop, S, lens):
+    """reflect_pad_ref -> framing -> forward basis -> spec_bins_ref -> overlap-add -> istft_finish_ref is denoise_ref
+    (pinned to the reference's outputs above), item by item, in float64."""
+    from _vocoder_ref import _bases
+    g = np.random.default_rng(n_fft + S)
+    B = len(lens)
+    audio = g.standard_normal((B, S))
+    fwd, inv, winsq, cutoff = _bases(n_fft, hop)
+    fwd, inv = fwd[:, 0].numpy(), inv[:, 0].numpy()                          # [2 cutoff, n_fft]
+    bias = 2.0 + 3.0 * g.random(cutoff)
+    F_, G = 1 + S // hop, S // hop
+    frames = [n // hop + 1 for n in lens]
+    for strength in (0.1, 2.0):
+        xpad = K.reflect_pad_ref(audio, lens, S, n_fft // 2, S + n_fft)
+        spec = np.zeros((B * F_, 2 * cutoff))
+        for b in range(B):
+            for f in range(frames[b]):
+                spec[b * F_ + f] = fwd @ xpad[b, f * hop:f * hop + n_fft]
+        spec = K.spec_bins_ref(spec, cutoff, bias, strength)
+        full = np.zeros((B, n_fft + hop * (F_ - 1)))
+        for b in range(B):
+            for f in range(frames[b]):
+                full[b, f * hop:f * hop + n_fft] += inv.T @ spec[b * F_ + f]
+        y = full[:, n_fft // 2:n_fft // 2 + G * hop]
+        out = K.istft_finish_ref(y, frames, winsq, n_fft, hop, np.float64, env_dtype=np.float64)
+        out32 = K.istft_finish_ref(y, frames, winsq, n_fft, hop, np.float64)  # the reference's float32 envelope
+        for b, n in enumerate(lens):
+            ref = denoise_ref(torch.from_numpy(audio[b:b + 1, :n]), torch.from_numpy(bias), strength, n_fft, hop).numpy()
+            m = n // hop * hop
+            assert ref.shape == (m,)
+            err = np.abs(out[b, :m] - ref).max() / max(1.0, np.abs(ref).max())
+            assert err <= 1e-12, (strength, b, err)
+            assert not out[b, m:].any()
+            assert np.abs(out32[b, :m] - ref).max() <= 4 * K.U * max(1.0, np.abs(ref).max()) * (n_fft // hop)
+
+
+def _stand_in_bits(expect):
+    return lambda c, inp, bug=None: expect(c, inp, np.float32, bug)
+
+
+def _stand_in_f32(expect, pick=lambda v: v):
+    return lambda c, inp, bug=None: pick(expect(c, inp, bug)).astype(np.float32)
+
+
+_SUITES = {
+    "lrelu": (K.LRELU_CASES, K.LRELU_BUGS, K.lrelu_inputs, _stand_in_bits(K.lrelu_expect), K.lrelu_check, (True, False)),
+    "conv_post": (K.CONV_POST_CASES, K.CONV_POST_BUGS, K.conv_post_inputs, _stand_in_f32(K.conv_post_expect, lambda v: v[0]),
+                  K.conv_post_check, (True, False)),
+    "reflect_pad": (K.REFLECT_CASES, K.REFLECT_BUGS, K.reflect_inputs,
+                    lambda c, inp, bug=None: K.reflect_expect(c, inp, bug), K.reflect_check, (True, False)),
+    "spec_bins": (K.SPEC_CASES, K.SPEC_BUGS, K.spec_inputs, _stand_in_f32(K.spec_expect), K.spec_check, (True,)),
+    "istft_finish": (K.ISTFT_CASES, K.ISTFT_BUGS, K.istft_inputs, _stand_in_bits(K.istft_expect), K.istft_check, (True,)),
+    "normalize": (K.NORM_CASES, K.NORM_BUGS, K.normalize_inputs, _stand_in_bits(K.normalize_expect), K.normalize_check,
+                  (True, False)),
+    "framed_gemm": (K.FRAMED_CASES, K.FRAMED_BUGS, K.framed_inputs, _stand_in_f32(K.framed_expect), K.framed_check,
+                    (True, False)),
+}
+
+
+@pytest.mark.parametrize("kernel", list(_SUITES))
+def test_every_gpu_case_and_bar_rejects_the_named_wrong_variants(kernel):
+    """For every case of tests/test_hip_vocoder_direct.py (with lengths and with lens = NULL): the restatement rounded
+    to float32 passes the GPU test's own comparison, and every named wrong variant whose output differs at all on that
+    case is rejected by it; each case rejects at least one, each variant is rejected by some case."""
+    cases, bugs, inputs, stand_in, check, modes = _SUITES[kernel]
+    caught = set()
+    for c in cases:
+        for use_lens in modes:
+            inp = inputs(c, use_lens)
+            good = stand_in(c, inp)
+            if kernel == "reflect_pad" and use_lens and c["clamp"] is not None:      # no reflect pad is defined there:
+                b, n = c["clamp"], c["lens"][c["clamp"]]                             # any own sample is acceptable
+                good[b, :n + 2 * c["pad"]] = inp["audio"][b, 0]
+            check(c, inp, good)
+            rejected = []
+            for bug in bugs:
+                bad = stand_in(c, inp, bug)
+                if kernel == "reflect_pad" and use_lens and c["clamp"] is not None:
+                    bad[b, :n + 2 * c["pad"]] = inp["audio"][b, 0]
+                if K.bit_equal(bad, good).all():
+                    continue                                                          # the defect does not show here
+                with pytest.raises(AssertionError):
+                    check(c, inp, bad, name=f"{kernel} [{bug}]")
+                rejected.append(bug)
+            print(f"{kernel} {K.case_id(c)} lens={'yes' if use_lens else 'NULL'}: rejected {rejected}")
+            assert rejected, (kernel, K.case_id(c), use_lens)
+            caught.update(rejected)
+    assert caught == set(bugs), set(bugs) - caught
+
+
+def test_mag_out_and_short_item_comparisons_discriminate():
+    c = K.SPEC_CASES[4]
+    inp = K.spec_inputs(c)
+    mag = K.spec_mag_ref(inp["spec"], c["cutoff"]).astype(np.float32)
+    K.spec_mag_check(c, inp, mag, inp["spec"].copy())
+    with pytest.raises(AssertionError):                                     # the imaginary half left out
+        K.spec_mag_check(c, inp, np.abs(inp["spec"][:, :c["cutoff"]]), inp["spec"].copy())
+    with pytest.raises(AssertionError):                                     # spec rescaled although mag_out was given
+        K.spec_mag_check(c, inp, mag, K.spec_expect(c, inp).astype(np.float32))
+    c = K.REFLECT_CASES[1]                                                  # the item of 2 <= pad = 3 samples
+    inp = K.reflect_inputs(c, True)
+    got = K.reflect_expect(c, inp)
+    b, n = c["clamp"], c["lens"][c["clamp"]]
+    got[b, :n + 2 * c["pad"]] = inp["audio"][b - 1, 0]                      # a neighbour's sample
+    with pytest.raises(AssertionError):
+        K.reflect_check(c, inp, got)
+    got[b, :n + 2 * c["pad"]] = np.nan                                      # what lies past the item's length
+    with pytest.raises(AssertionError):
+        K.reflect_check(c, inp, got)
+
+
+def test_window_sumsquare_restatement_keeps_a_float32_running_sum():
+    w = K.hann_sq(16)
+    e32, e64 = K.window_sumsquare_ref(w, 6, 4, 16), K.window_sumsquare_ref(w, 6, 4, 16, np.float64)
+    assert e32.dtype == np.float32 and e32.shape == (16 + 4 * 5,)
+    acc = np.float32(0)
+    for f in range(4):                                                       # sample 16: frames 1 .. 4, in frame order
+        acc = np.float32(np.float64(acc) + w[16 - 4 * (f + 1)]) if 0 <= 16 - 4 * (f + 1) < 16 else acc
+    assert e32[16] == acc and abs(e64[16] - 1.5) < 1e-15
+
+
+@pytest.mark.parametrize("Kk,F,G", K.INVERSE_CASES)
+def test_inverse_form_comparison_rejects_a_shifted_tap_and_a_mask_at_T(Kk, F, G):
+    inp = K.inverse_inputs(Kk, F, G)
+    K.inverse_check(inp, K.inverse_expect(inp).astype(np.float32))
+    rejected = []
+    for bug in K.INVERSE_BUGS:
+        bad = K.inverse_expect(inp, bug).astype(np.float32)
+        if K.bit_equal(bad, K.inverse_expect(inp).astype(np.float32)).all():
+            continue                                      # masking at T shows only where lens[b] > T (G = F - 1)
+        with pytest.raises(AssertionError):
+            K.inverse_check(inp, bad, name=f"inverse form [{bug}]")
+        rejected.append(bug)
+    assert "tap_shifted" in rejected and (("mask_at_T" in rejected) == (G < F))

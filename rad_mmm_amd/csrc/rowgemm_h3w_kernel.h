@@ -17,13 +17,6 @@
 //     rounds of the 256 CUs: 12 800 frames x 1024 channels -> MB = 7 -> 58 x 4 = 232 workgroups
 //     in one round (89 % of the MFMA slots useful; 128-row tiles: 78 %).
 #pragma once
-// timing-only build switches (results wrong): -DRADMMM_EPI_NOSTORE removes the epilogue's stores (its arithmetic stays),
-// -DRADMMM_EPI_NONE the whole epilogue of the window kernel -- what the launch costs without them (tools/epi_cost.sh)
-#ifdef RADMMM_EPI_NOSTORE
-#define RADMMM_EPI_STORE(...) ((void)0)
-#else
-#define RADMMM_EPI_STORE(...) __VA_ARGS__
-#endif
 #include <stdlib.h>
 #include <type_traits>
 
@@ -39,12 +32,9 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
+__device__ __forceinline__ f32x16 mfma_f16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+
 constexpr int BN = 256, BK = 32, ROWB = 64;
-// operand format of the scaled cross-term MFMA: 0 = FP8 e4m3 (the product), 2 = FP6 e2m3 in a TIMING-ONLY build
-// (-DRADMMM_X_FMT=2: wrong results; what would MXFP6 cross terms buy the K loop?  DESIGN 7)
-#ifndef RADMMM_X_FMT
-#define RADMMM_X_FMT 0
-#endif
 constexpr int OOB = 0x7fffffff;
 
 // -DRADMMM_PHASE_TIMERS (measurement builds only, tools/phase_probe.py): every workgroup records the 100 MHz wall clock
@@ -118,19 +108,6 @@ __device__ __forceinline__ void epilogue_blocks(const f32x16 (&acc)[MB][2], floa
 // uniform branches (the asm statements keep the optimizer from turning the chain into a dynamic index -- which would
 // move all accumulators to scratch -- or into 7-way selects), so the body exists once (~13 KB of code; seven unrolled
 // copies do not fit the instruction cache: measured +50 us per launch in round 2).
-// TIMING-ONLY builds (wrong results; tools/floor_probe.sh, profiles/r05_nprod1_floor.txt): what is a launch made of?
-//   -DRADMMM_TIMING=1  the cross-term (FP8) MFMAs are not issued: half the matrix work, everything else in place
-//   -DRADMMM_TIMING=2  "nprod = 1" in the instruction stream: additionally no cross-fragment LDS reads (the DMA stays: the
-//                      counted vmcnt waits of the loops depend on the number of pieces)
-//   -DRADMMM_TIMING=3  no MFMA at all (fragments are still read: operands pinned by empty asm): the launch's non-MFMA floor
-#ifndef RADMMM_TIMING
-#define RADMMM_TIMING 0
-#endif
-#if RADMMM_TIMING == 3
-#define RADMMM_MFMA_F16(A, B, C) ([&] { asm volatile("" : : "v"(A), "v"(B)); return (C); }())
-#else
-#define RADMMM_MFMA_F16(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_f16((A), (B), (C), 0, 0, 0)
-#endif
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
@@ -201,21 +178,21 @@ __device__ __forceinline__ float store_pair_split(__amdgpu_buffer_rsrc_t rH, __a
   const float r0 = t0 - (float)h0, r1 = t1 - (float)h1;
   f16x2 hp;
   hp[0] = h0; hp[1] = h1;
-  RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, hp), rH, vH, sH, 0));
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, hp), rH, vH, sH, 0);
   if constexpr (!X8) {
     f16x2 lp;
     lp[0] = (_Float16)r0; lp[1] = (_Float16)r1;
-    RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lp), rL, vH, sH, 0));
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lp), rL, vH, sH, 0);
   } else {
     const float lm = x8_mul * 2048.f;
     const int w8h = __builtin_amdgcn_cvt_pk_fp8_f32(radmmm::clamp_e4m3(t0 * x8_mul), radmmm::clamp_e4m3(t1 * x8_mul), 0, false);
     const int w8l = __builtin_amdgcn_cvt_pk_fp8_f32(radmmm::clamp_e4m3(r0 * lm), radmmm::clamp_e4m3(r1 * lm), 0, false);
-    RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b16((unsigned short)w8h, rL, vXh, sH, 0));
-    RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b16((unsigned short)w8l, rL, vXl, sH, 0));
+    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)w8h, rL, vXh, sH, 0);
+    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)w8l, rL, vXl, sH, 0);
     if constexpr (has_lo16) {
       f16x2 lp;
       lp[0] = (_Float16)r0; lp[1] = (_Float16)r1;
-      RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lp), rLo16, vH, sH, 0));
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lp), rLo16, vH, sH, 0);
     }
   }
   return amax;
@@ -233,21 +210,21 @@ __device__ __forceinline__ float store_pair_split_rt(__amdgpu_buffer_rsrc_t rH, 
   const float r0 = t0 - (float)h0, r1 = t1 - (float)h1;
   f16x2 hp;
   hp[0] = h0; hp[1] = h1;
-  RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, hp), rH, vH, sH, 0));
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, hp), rH, vH, sH, 0);
   if constexpr (!X8) {
     f16x2 lp;
     lp[0] = (_Float16)r0; lp[1] = (_Float16)r1;
-    RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lp), rL, vH, sH, 0));
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lp), rL, vH, sH, 0);
   } else {
     const float lm = x8_mul * 2048.f;
     const int w8h = __builtin_amdgcn_cvt_pk_fp8_f32(radmmm::clamp_e4m3(t0 * x8_mul), radmmm::clamp_e4m3(t1 * x8_mul), 0, false);
     const int w8l = __builtin_amdgcn_cvt_pk_fp8_f32(radmmm::clamp_e4m3(r0 * lm), radmmm::clamp_e4m3(r1 * lm), 0, false);
-    RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b16((unsigned short)w8h, rL, vXh, sH, 0));
-    RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b16((unsigned short)w8l, rL, vXl, sH, 0));
+    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)w8h, rL, vXh, sH, 0);
+    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)w8l, rL, vXl, sH, 0);
     if (has_lo16) {
       f16x2 lp;
       lp[0] = (_Float16)r0; lp[1] = (_Float16)r1;
-      RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lp), rLo16, vH, sH, 0));
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lp), rLo16, vH, sH, 0);
     }
   }
   return amax;
@@ -436,11 +413,11 @@ __device__ __forceinline__ void direct_blocks(const f32x16 (&acc)[MB][2], const 
         x1 = actf(x1 * rf.z);
         f32x2 y;
         y[0] = x0; y[1] = x1;
-        RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), rC, vC, ru * p.ldc * 4, 0));
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), rC, vC, ru * p.ldc * 4, 0);
         if constexpr (C2M) {
           f32x2 c2;
           c2[0] = sidef[0] + x0; c2[1] = sidef[1] + x1;              // (side reads as zero when not accumulating)
-          RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, c2), rC2, vC2, ru * p.ldc2 * 4, 0));
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, c2), rC2, vC2, ru * p.ldc2 * 4, 0);
           if (c2split)
             sat = fmaxf(sat, store_pair_split_rt<X8>(rH, rL, rLo16, false, vH, vXh, vXl, ru * ldh * 2, x8_mul, sp_scale, c2[0], c2[1]));
         }
@@ -456,12 +433,12 @@ __device__ __forceinline__ void direct_blocks(const f32x16 (&acc)[MB][2], const 
           const float x0 = v[0][e], x1 = v[1][e];
           f32x2 y;
           y[0] = x0; y[1] = x1;
-          RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), rC, vC, ru * p.ldc * 4, 0));
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), rC, vC, ru * p.ldc * 4, 0);
           if constexpr (C2M) {
             const f32x2 sidef = __builtin_bit_cast(f32x2, side[e]);
             f32x2 c2;
             c2[0] = sidef[0] + x0; c2[1] = sidef[1] + x1;            // (side reads as zero when not accumulating)
-            RADMMM_EPI_STORE(__builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, c2), rC2, vC2, ru * p.ldc2 * 4, 0));
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, c2), rC2, vC2, ru * p.ldc2 * 4, 0);
             if constexpr (decltype(C2S)::value)
               sat = fmaxf(sat, store_pair_split<X8, false>(rH, rL, rLo16, vH, vXh, vXl, ru * ldh * 2, x8_mul, sp_scale, c2[0], c2[1]));
           }
@@ -691,9 +668,6 @@ __global__ __launch_bounds__(256, 1) void rowgemm_h3d_kernel(const radmmm_rowgem
   };
   // piece w of 0 .. NP-1 of tile (tap, kb) into stage `buf`
   auto dma_piece = [&](int buf, int w, int tap, int kb) __attribute__((always_inline)) {
-#ifdef RADMMM_ABL_NODMA                                // measurement builds: K loop without operand delivery
-    if (buf >= 0) return;
-#endif
     const int sbase = buf * G::STAGE;
     if (w < NPA) {
       const int dst = a_dst[w] < 0 ? 2 * G::STAGE + wave * 1024 : sbase + a_dst[w];
@@ -767,9 +741,6 @@ __global__ __launch_bounds__(256, 1) void rowgemm_h3d_kernel(const radmmm_rowgem
     acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc[i][j], 0, 0, 0, x_sa, 0, x_sb);
   };
   auto mfma_item = [&](int t) __attribute__((always_inline)) {
-#ifdef RADMMM_ABL_NOMFMA                               // measurement builds: operand delivery alone
-    if (t >= 0) return;
-#endif
     const int kb = item_kb(t), i = item_i(t);
     if constexpr (PR == 1) {
       acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fah[t], bh[kb][0], acc[i][0], 0, 0, 0);

@@ -125,9 +125,6 @@ __global__ __launch_bounds__(256, 1) void rowgemm_win_kernel(const radmmm_rowgem
     const int lr = 16 * j + d_row;                                    // LDS row 0 .. 255, interleaved as in rowgemm_h3d
     const int n = n0 + (lr & ~63) + 2 * (lr & 31) + ((lr >> 5) & 1);
     b_voff[k] = n < p.N ? (n * q.ldb_h + d_chunk * 8) * 2 : OOB;
-#ifdef RADMMM_TIMING_BOOB      // timing only (wrong results): 1 = every second B piece, 2 = every B piece is an out-of-range
-    if (RADMMM_TIMING_BOOB == 2 || (k & 1)) b_voff[k] = OOB;   // DMA -- zeros written to LDS, nothing fetched from L2
-#endif
     b_dst[k] = j * 1024;
   }
   const __amdgpu_buffer_rsrc_t rAh = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(q.Ah), 0, a_bytes, 0x00020000);
@@ -171,71 +168,29 @@ __global__ __launch_bounds__(256, 1) void rowgemm_win_kernel(const radmmm_rowgem
   };
   auto read_lo = [&](int t, auto tapc, auto parc) __attribute__((always_inline)) {
     constexpr int tap = decltype(tapc)::value, par = decltype(parc)::value;
-#if RADMMM_TIMING == 2
-    (void)t;
-#elif defined(RADMMM_SKIP_LO_READS)         // TIMING-ONLY build (wrong results): the cross-term MFMAs run on the hi fragments -- what do
-    fal[t] = fah[t];                        // the 14 lo-fragment LDS reads per wave and K step cost a power-bound launch?
-#else
-#ifdef RADMMM_WIN_SKIP6       // TIMING-ONLY build (wrong results): 6 of the 36 fragment reads per wave and K step are not
-    if ((t & 1) == 0 && t < 12) {   // issued -- the read count of a 2 x 2 wave layout on 16 x 16 MFMAs (30 per wave), same MFMAs, same DMA
-      fal[t] = fah[t];              // (profiles/r06_tile_probes.txt)
-      return;
-    }
-#endif
     fal[t] = *reinterpret_cast<const f16x8*>(sm + ((t & 1) ? aad1 : aad0)[t >> 1][tap] + par * G::W_BYTES + G::W_PLANE);
-#endif
   };
   auto read_b1 = [&](int set, int stage, int kb, int j) __attribute__((always_inline)) {
     const int fo = kb ? bad1 : bad0;
     bh[set][kb][j] = *reinterpret_cast<const f16x8*>(sm + stage * G::B_STAGE + j * 32 * ROWB + fo);
-#if RADMMM_TIMING != 2
     bl[set][kb][j] = *reinterpret_cast<const f16x8*>(sm + stage * G::B_STAGE + G::B_BYTES + j * 32 * ROWB + fo);
-#endif
   };
-#ifdef RADMMM_B_GLOBAL
-  // EXPERIMENT (round 5, -DRADMMM_B_GLOBAL; MEASURED AND REJECTED, profiles/r05_nprod1_floor.txt): the wave-private B fragments
-  // straight from global memory into registers -- no LDS-DMA pieces and no ds_reads for B: 32 KB of LDS writes and 32 KB of LDS
-  // reads per CU and K step less on a port that is 81 % busy.  Bit-identical (38 shared-window cases, the step's loss), but the
-  // launch gets SLOWER: 5-tap forward 255 -> 282 us, fused data gradient 316 -> 353 us, step 41.9 -> 43.5 ms -- a fragment load
-  // touches 32 weight rows with 32 bytes each (half cache lines through the texture path), which costs more than the LDS port
-  // it relieves; the LDS-DMA path moves the same bytes as 16 rows x 64 bytes per instruction.  Lane
-  // (n = lane & 31, half) of column block j wants the 16 bytes of weight row n0 + 64 wave + 2 n + j (the interleaved order of
-  // the direct epilogue) at k block kb: chunk 2 kb + half of the 64-byte K step.
-  int gb_vo[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int n = n0 + wave * 64 + 2 * (lane & 31) + j;
-    gb_vo[j] = n < p.N ? (n * q.ldb_h + half * 8) * 2 : OOB;
-  }
-  auto load_b_piece = [&](int w, int set, int soff) __attribute__((always_inline)) {      // w = 4 arr + 2 kb + j
-    const int arr = w >> 2, kb = (w >> 1) & 1, j = w & 1;
-    const f16x8 v = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(arr ? rBl : rBh, gb_vo[j] + kb * 32, soff, 0));
-    if (arr) bl[set][kb][j] = v;
-    else bh[set][kb][j] = v;
-  };
-#endif
   const int x_sa = (lane >> 5) ? 127 - 11 - q.a8_exp : 127 - q.a8_exp;       // E8M0 block scales (rowgemm_h3d, PR 2)
   const int x_sb = (lane >> 5) ? 127 - q.b8_exp : 127 - 11 - q.b8_exp;
   auto cross = [&](int set, int i, int j) __attribute__((always_inline)) {
     if constexpr (PR == 3) {                // three f16 products (rowgemm_onetap.h): Al.Bh + Ah.Bl of both k blocks
-#if RADMMM_TIMING == 0
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fal[2 * i + kb], bh[set][kb][j], acc[i][j], 0, 0, 0);
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fah[2 * i + kb], bl[set][kb][j], acc[i][j], 0, 0, 0);
       }
-#endif
       return;
     }
     const i32x8 a8 = __builtin_shufflevector(__builtin_bit_cast(i32x4, fal[2 * i]), __builtin_bit_cast(i32x4, fal[2 * i + 1]),
                                              0, 1, 2, 3, 4, 5, 6, 7);
     const i32x8 b8 = __builtin_shufflevector(__builtin_bit_cast(i32x4, bl[set][0][j]), __builtin_bit_cast(i32x4, bl[set][1][j]),
                                              0, 1, 2, 3, 4, 5, 6, 7);
-#if RADMMM_TIMING == 0
-    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc[i][j], RADMMM_X_FMT, RADMMM_X_FMT, 0, x_sa, 0, x_sb);
-#elif RADMMM_TIMING != 2
-    asm volatile("" : : "v"(a8), "v"(b8));
-#endif
+    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc[i][j], 0, 0, 0, x_sa, 0, x_sb);
   };
   // DMA with the step's position as the instruction's SCALAR offset (no vector add per piece; an out-of-range vector offset
   // stays out of range: the scalar offset takes part in the range check on gfx950)
@@ -268,11 +223,6 @@ __global__ __launch_bounds__(256, 1) void rowgemm_win_kernel(const radmmm_rowgem
   //   The look-ahead crosses the step boundary: items 12 / 13 read items 0 / 1 of the NEXT step (next tap's row shift).
 #pragma unroll
   for (int k = 0; k < NPW; ++k) dma_win2(k, 0, 0);
-#ifdef RADMMM_B_GLOBAL
-#pragma unroll
-  for (int w = 0; w < 8; ++w) load_b_piece(w, 0, 0);
-  __syncthreads();
-#else
 #pragma unroll
   for (int w = 0; w < 8; ++w) dma_b2(w, 0, 0);
 #pragma unroll
@@ -282,7 +232,6 @@ __global__ __launch_bounds__(256, 1) void rowgemm_win_kernel(const radmmm_rowgem
   for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
     for (int j = 0; j < 2; ++j) read_b1(0, 0, kb, j);
-#endif
 #pragma unroll
   for (int t = 0; t < D; ++t) {
     read_hi(t, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
@@ -296,8 +245,6 @@ __global__ __launch_bounds__(256, 1) void rowgemm_win_kernel(const radmmm_rowgem
     constexpr int ntap = tap == WTAPS - 1 ? 0 : tap + 1, npar = tap == WTAPS - 1 ? (par ^ 1) : par;   // tile of step + 1
     constexpr int tap2 = (tap + 2) % WTAPS;                           // tile of step + 2
     const int soff2 = tap2 * b_tap_bytes + (kb + (tap + 2) / WTAPS) * (BK * 2);
-    const int soff1 = ntap * b_tap_bytes + (kb + (tap + 1) / WTAPS) * (BK * 2);        // tile of step + 1 (RADMMM_B_GLOBAL)
-    (void)soff1;
     using TapC = std::integral_constant<int, tap>;
     using ParC = std::integral_constant<int, par>;
     using NTapC = std::integral_constant<int, ntap>;
@@ -314,34 +261,24 @@ __global__ __launch_bounds__(256, 1) void rowgemm_win_kernel(const radmmm_rowgem
         __builtin_amdgcn_sched_barrier(0);
       }
       // slot A
-      acc[i][0] = RADMMM_MFMA_F16(fah[t], bh[set][kbk][0], acc[i][0]);
+      acc[i][0] = mfma_f16(fah[t], bh[set][kbk][0], acc[i][0]);
       if (t + D < NT) read_hi(t + D, TapC{}, ParC{});
       else read_hi(t + D - NT, NTapC{}, NParC{});
-#ifndef RADMMM_B_GLOBAL
       if (t >= TW) read_b1(set ^ 1, set ^ 1, t - TW, 0);
-#endif
       __builtin_amdgcn_sched_barrier(0);
       // slot B
-      acc[i][1] = RADMMM_MFMA_F16(fah[t], bh[set][kbk][1], acc[i][1]);
+      acc[i][1] = mfma_f16(fah[t], bh[set][kbk][1], acc[i][1]);
       if (t + D < NT) read_lo(t + D, TapC{}, ParC{});
       else read_lo(t + D - NT, NTapC{}, NParC{});
-#ifndef RADMMM_B_GLOBAL
       if (t >= TW) read_b1(set ^ 1, set ^ 1, t - TW, 1);
-#endif
       __builtin_amdgcn_sched_barrier(0);
       // slot C (items 1 .. 13; the 14th follows the loop)
       if (t > 0) {
         if (kbk == 1) cross(set, i, 0);
         else cross(set, i - 1, 1);
         const int c = t - 1;
-#ifdef RADMMM_B_GLOBAL
-        // B(s + 1) first (into the register set this step does not use: a whole step of flight time), the window pieces behind
-        if (c < 8) load_b_piece(c, set ^ 1, soff1);
-        else if (c - 8 < NW) dma_win2(G::WPT * tap + (c - 8), par ^ 1, kb + 1);
-#else
         if (c < NW) dma_win2(G::WPT * tap + c, par ^ 1, kb + 1);
         else if (c - NW < 8) dma_b2(c - NW, set, soff2);
-#endif
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -399,19 +336,8 @@ __global__ __launch_bounds__(256, 1) void rowgemm_win_kernel(const radmmm_rowgem
     rowf4[tid] = make_float4(q.acc_scale * pre, post, rsc, 0.f);
   }
   __syncthreads();
-#ifdef RADMMM_EPI_NONE
-  {                                                                    // (timing only: keep the accumulators alive)
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) s += acc[i][0][e] + acc[i][1][e];
-    if (s == 1.2345e-30f) p.C[0] = s;
-  }
-#else
   direct_epilogue<MB, EK, PR == 2>(acc, rowf4, p, m0, n0, lane, wave, sat);
   radmmm::raise_sat_flag(p.sat_flag, sat, (p.Ch && p.split_fmt != RADMMM_SPLIT_F16) ? __builtin_ldexpf(1.f, p.ch_x8_exp) : 0.f);
-#endif
 }
 
 template <int MB, int EK, bool XT, int PR = 2>

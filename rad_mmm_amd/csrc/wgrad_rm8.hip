@@ -70,27 +70,6 @@ __device__ __forceinline__ void dma16s(__amdgpu_buffer_rsrc_t rsrc, lds_u32_ptr 
 #endif
 }
 
-#ifdef RADMMM_WG8_NOMASK                              // TIMING-ONLY build (wrong at utterance boundaries): no row masks on the X pieces
-using WG8Plain = std::true_type;
-#else
-using WG8Plain = std::false_type;
-#endif
-
-// TIMING-ONLY builds (wrong results; rowgemm_h3w_kernel.h has the list): 1 / 2 no cross-term MFMAs, 3 no MFMA at all
-#ifndef RADMMM_TIMING
-#define RADMMM_TIMING 0
-#endif
-#if RADMMM_TIMING == 3
-#define WG8_MFMA_F16(A, B, C) ([&] { asm volatile("" : : "v"(A), "v"(B)); return (C); }())
-#else
-#define WG8_MFMA_F16(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_f16((A), (B), (C), 0, 0, 0)
-#endif
-#if RADMMM_TIMING == 0
-#define WG8_MFMA_X(A, B, C, SA, SB) __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4((A), (B), (C), 0, 0, 0, (SA), 0, (SB))
-#else
-#define WG8_MFMA_X(A, B, C, SA, SB) ([&] { asm volatile("" : : "v"(A), "v"(B)); return (C); }())
-#endif
-
 struct Frag { i32x2 lo, hi; };
 // Fragment addressing.  All lane-dependent parts of a fragment's LDS address are computed ONCE (round 3, second pass: the K
 // step carried ~270 VALU instructions beside its 48 MFMAs -- more than the MFMA gaps hide -- of which 30 were these address
@@ -134,13 +113,9 @@ __device__ __forceinline__ void frag_wait3(Frag& a, Frag& b, Frag& c) {
 __device__ __forceinline__ int cvt4_fp8(int lo2, int hi2, float inv) {
   // two packed conversions into the two halves of ONE register.  As inline asm with a write-only destination: the builtin's
   // destination is read-modify-write, and the compiler materialises its (dead) initial value with a v_mov -- 40 per K step.
-#ifdef RADMMM_TIMING_NOCVT                 // TIMING-ONLY build (wrong results): the 80 hi8 conversions per K step are not issued --
-  return lo2 ^ hi2;                         // upper bound of "read the hi8 halves from the cross arrays instead" (profiles/r05_wgrad_hi8.txt)
-#else
   int o;
   asm("v_cvt_scalef32_pk_fp8_f16 %0, %1, %3\n\tv_cvt_scalef32_pk_fp8_f16 %0, %2, %3 op_sel:[0,0,1]" : "=&v"(o) : "v"(lo2), "v"(hi2), "v"(inv));
   return o;
-#endif
 }
 __device__ __forceinline__ i32x4 hi8_of(const Frag& f0, const Frag& f1, float inv) {
   i32x4 r;
@@ -249,7 +224,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
     int vo = p_off[w];
     if (isx) {
       vo += rel * stepb;
-      if (!WG8Plain::value) vo |= ((int)(nmask << p_sh[w]) >> 31) & OOB;
+      vo |= ((int)(nmask << p_sh[w]) >> 31) & OOB;
     }
     const int dst = lo8 ? 2 * HARR + isx * LARR + (4 * ((w - 8) & 1) + wave) * 1024 : isx * HARR + (4 * (w & 3) + wave) * 1024;
     dma16s(lo8 ? (isx ? rXl : rGl) : (isx ? rXh : rGh), (lds_u32_ptr)(sm + buf * STAGE + dst), vo, isx ? 0 : rel * stepb);
@@ -383,10 +358,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
         if (i == 6) {
           // tile s + 1 has landed as far as this wave fetched it, every read of tile s is complete: publish, and free
           // tile s's stage for tile s + 3
-#ifdef RADMMM_WG8_GY_EVERY
-          if ((l_rel % RADMMM_WG8_GY_EVERY) != 0) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-          else
-#endif
           asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)\n\ts_barrier" ::: "memory");
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -395,40 +366,28 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
         const i32x8 a8 = __builtin_shufflevector(ah8[i & 1], l8c, 0, 1, 2, 3, 4, 5, 6, 7);
         i32x4 h8n;                                                 // hi8 of block i + 1, converted under this block's f16 MFMAs
         // slot 0
-        acc[i][0] = WG8_MFMA_F16(ah0, bh0[0], acc[i][0]);
+        acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah0, bh0[0], acc[i][0], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);                         // (the MFMA opens its slot)
-        // -DRADMMM_WG8_SKIP_READS, TIMING-ONLY (wrong results): the A-side fragment reads of every other row block are not
-        // issued -- 24 of the 60 LDS reads of a K step; a 2 x 2 wave tiling of the same 256 x 256 tile would save 12 (48 reads
-        // instead of 60): an upper bound of that redesign before anything is built (profiles/r05_wgrad_hi8.txt)
-#ifdef RADMMM_WG8_SKIP_READS
-        const bool do_rd = (i2 & 1) == 0;
-#else
-        const bool do_rd = true;
-#endif
-        if (do_rd) {
-          if (i2 < 4) frag_issue<0>(ga0[nx2], ah_base[i2 & 3] + sb2);
-          else frag_issue<256>(ga0[nx2], ah_base[i2 & 3] + sb2);
-        }
+        if (i2 < 4) frag_issue<0>(ga0[nx2], ah_base[i2 & 3] + sb2);
+        else frag_issue<256>(ga0[nx2], ah_base[i2 & 3] + sb2);
         frag_wait3<2>(ga0[nx1], ga1[nx1], ga8[nx1]);               // block i + 1's fragments (read a whole block ago): two younger reads in flight
         if (i == 7) frag_issue<0>(xb0[0], bh_base[0] + sbn);        // (bh0[0] holds the old value: last read by the MFMA above)
         __builtin_amdgcn_sched_barrier(0);
         // slot 1
-        acc[i][1] = WG8_MFMA_F16(ah0, bh0[1], acc[i][1]);
+        acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah0, bh0[1], acc[i][1], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);                         // (the MFMA opens its slot)
-        if (do_rd) {
-          if (i2 < 4) frag_issue<8192>(ga1[nx2], ah_base[i2 & 3] + sb2);
-          else frag_issue<8192 + 256>(ga1[nx2], ah_base[i2 & 3] + sb2);
-        }
+        if (i2 < 4) frag_issue<8192>(ga1[nx2], ah_base[i2 & 3] + sb2);
+        else frag_issue<8192 + 256>(ga1[nx2], ah_base[i2 & 3] + sb2);
         if (i == 7) frag_issue<0>(xb0[1], bh_base[1] + sbn);
         __builtin_amdgcn_sched_barrier(0);
         // slot 2
-        acc[i][0] = WG8_MFMA_F16(ah1, bh1[0], acc[i][0]);
+        acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah1, bh1[0], acc[i][0], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);                         // (the MFMA opens its slot)
-        if (do_rd) frag8_issue(ga8[nx2], a8_base[i2] + sb2);
+        frag8_issue(ga8[nx2], a8_base[i2] + sb2);
         if (i == 7) frag_issue<8192>(xb1[0], bh_base[0] + sbn);
         __builtin_amdgcn_sched_barrier(0);
         // slot 3
-        acc[i][1] = WG8_MFMA_F16(ah1, bh1[1], acc[i][1]);
+        acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah1, bh1[1], acc[i][1], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);                         // (the MFMA opens its slot)
         if (i == 0) {
           frag_wait2<6>(xb8[0], xb8[1]);                           // (younger: this block's six A reads)
@@ -439,19 +398,9 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
         if (i == 7) frag_issue<8192>(xb1[1], bh_base[1] + sbn);
         __builtin_amdgcn_sched_barrier(0);
         // slot 4
-        acc[i][0] = WG8_MFMA_X(a8, b8[0], acc[i][0], x_sa, x_sb);
+        acc[i][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8[0], acc[i][0], 0, 0, 0, x_sa, 0, x_sb);
         __builtin_amdgcn_sched_barrier(0);                         // (the MFMA opens its slot)
-        // -DRADMMM_WG8_GY_EVERY=n, TIMING-ONLY (wrong results; VERDICT r5 item 2b measured before built): the GY pieces of a
-        // tile (0..3 hi, 8 / 9 lo8: half of the 12) are issued in one step of n only -- the stage keeps older GY frames, real
-        // data -- i.e. the instruction and L2 -> LDS byte mix of a tile that keeps GY resident for all five taps (n = 5: 40 % of
-        // the DMA pieces gone); the step's wait counts what the step issued.  profiles/r06_tile_probes.txt
-#ifdef RADMMM_WG8_GY_EVERY
-#define WG8_PIECE_ON(w) (((w) >= 4 && (w) != 8 && (w) != 9) || gy_step)
-        const bool gy_step = (l_rel % RADMMM_WG8_GY_EVERY) == 0;
-#else
-#define WG8_PIECE_ON(w) true
-#endif
-        if (i < 6 && WG8_PIECE_ON(2 * i)) dma_piece(nbuf, 2 * i, l_rel, nmask);
+        if (i < 6) dma_piece(nbuf, 2 * i, l_rel, nmask);
         if (i == 1) nmask = row_mask();                            // (first needed by block 2's pieces)
         h8n[0] = cvt4_fp8(ga0[nx1].lo[0], ga0[nx1].lo[1], g_inv);
         h8n[1] = cvt4_fp8(ga0[nx1].hi[0], ga0[nx1].hi[1], g_inv);
@@ -462,9 +411,9 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
         }
         __builtin_amdgcn_sched_barrier(0);
         // slot 5
-        acc[i][1] = WG8_MFMA_X(a8, b8[1], acc[i][1], x_sa, x_sb);
+        acc[i][1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8[1], acc[i][1], 0, 0, 0, x_sa, 0, x_sb);
         __builtin_amdgcn_sched_barrier(0);                         // (the MFMA opens its slot)
-        if (i < 6 && WG8_PIECE_ON(2 * i + 1)) dma_piece(nbuf, 2 * i + 1, l_rel, nmask);
+        if (i < 6) dma_piece(nbuf, 2 * i + 1, l_rel, nmask);
         h8n[2] = cvt4_fp8(ga1[nx1].lo[0], ga1[nx1].lo[1], g_inv);
         h8n[3] = cvt4_fp8(ga1[nx1].hi[0], ga1[nx1].hi[1], g_inv);
         ah8[(i + 1) & 1] = h8n;

@@ -12,7 +12,7 @@ import os
 
 import torch
 
-from ._lib import lib, check, ptr, stream, amp_fwd, amp_bwd, rowgemm_h3, debug_env
+from ._lib import lib, check, ptr, stream, amp_fwd, amp_bwd, rowgemm_h3
 from ._trace import traced
 
 
@@ -40,7 +40,7 @@ class BiLSTMFn(torch.autograd.Function):
         x2 = x.reshape(B * T, I).contiguous()
         W_ih = torch.cat((w_ih_f, w_ih_r), 0)                    # [8H, I]
         bias = torch.cat((b_ih_f + b_hh_f, b_ih_r + b_hh_r))     # [8H]
-        if (8 * H) % 4 == 0 and B * T >= 4096 and debug_env("RADMMM_LSTM_PROJ", "hip") != "torch":
+        if (8 * H) % 4 == 0 and B * T >= 4096:
             # frame-rate inputs: the input projection on the split-f16 row GEMM (three f16 products, 2e-6): 114 GFLOP at
             # the benchmark size in ~0.4 ms instead of 0.91 ms on the fp32 library GEMM; W_ih [8H, I] is already the
             # K-contiguous B operand.  (Its gradient GEMMs: BiLSTMFn.backward.)
@@ -96,8 +96,7 @@ class BiLSTMFn(torch.autograd.Function):
         hp[:, 1:, :H] = y3[:, :-1, :H]                           # forward direction: h_{t-1}
         hp[:, :-1, H:] = y3[:, 1:, H:]                           # reverse direction: h_{t+1}
         hp = hp.view(B * T, 2 * H)
-        if (ctx.box is not None and B * T >= 4096 and (8 * H) % 32 == 0 and I % 4 == 0 and H % 2 == 0 and
-                debug_env("RADMMM_LSTM_GRADS", "hip") != "torch"):
+        if ctx.box is not None and B * T >= 4096 and (8 * H) % 32 == 0 and I % 4 == 0 and H % 2 == 0:
             # frame-rate batches: the four gradient GEMMs (226 + 57 GFLOP at the benchmark size, 2.5 ms on the fp32 library
             # GEMMs) on the split-f16 kernels: ONE transposing pass over dG feeds both weight gradients (contraction over
             # frames) and yields the bias gradient as its column sums; the input gradient is a row GEMM on dG's split copy.
@@ -107,8 +106,7 @@ class BiLSTMFn(torch.autograd.Function):
             SG = ops.grad_scale(box, dy2)
             flag = ops.sat_flag_bwd_of(box)
             gh, gl = ops.split_f16(dG, 8 * H, SG, 8 * H, 3, 0, flag)       # row-major split pair of dG: operand of all four GEMMs
-            if (xpair is not None and T >= 32 and B <= 1024 and (4 * H) % 8 == 0 and
-                    debug_env("RADMMM_WGRAD_RM", "1") != "0"):
+            if xpair is not None and T >= 32 and B <= 1024 and (4 * H) % 8 == 0:
                 # weight gradients straight from the row-major pairs (radmmm_wgrad_rm: transposition in the LDS read); the
                 # pair of x was made for the forward projection, the pairs of h_prev (one per direction, each with its own
                 # 16-byte aligned row pitch) cost what the transposed copy did
@@ -193,10 +191,10 @@ class MergedBiLSTMFn(torch.autograd.Function):
         # result IS the merged gate layout, and in backward the same pair of operands gives dW_ih / dx / dW_hh on the row-major
         # split kernels (three f16 products, 2e-6) -- instead of 3 x {fp32 library GEMM at 40 TFLOP/s + a strided scatter of 105 MB}
         # each way (joint step: 2.96 ms of `Cijk_*` launches per step, profiles/r05_joint_kernel_stats.txt).  The zero blocks
-        # cost 2/3 of 121 GFLOP of MFMA work nobody waits for.  RADMMM_MERGED_LSTM_GEMMS=torch (RADMMM_DEBUG): the library path.
+        # cost 2/3 of 121 GFLOP of MFMA work nobody waits for.  Smaller batches: the library path.
         I = xs[0].shape[2]
         split = bool(box is not None and B * T >= 4096 and all(x.shape[2] == I for x in xs) and (P * I) % 32 == 0 and H % 8 == 0
-                     and T >= 32 and B <= 1024 and debug_env("RADMMM_MERGED_LSTM_GEMMS", "hip") != "torch")
+                     and T >= 32 and B <= 1024)
         ctx.split = split
         if split:
             from . import ops

@@ -9,6 +9,7 @@ from __future__ import annotations
 import collections
 import math
 import os
+import types
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -578,11 +579,10 @@ def conv_norm(x, v, g, bias, lens, B, T, dil=1, partial=False, mask_out=False, a
     # amplifies errors of its parameters in backward as well) can still take the FP8-cross kernel for its WEIGHT
     # gradient -- a leaf: its rounding (~1e-4 of the tensor, the WN convs' own weight-gradient accuracy) goes nowhere else --
     # on the slot-pinned radmmm_wgrad_rm8 instead of the three-product radmmm_wgrad_rm (configs[4]: 6.8 ms per step)
-    meta["wgrad8"] = bool(wgrad8 and prec == "f8x" and meta["nprod"] == 3 and x.shape[0] >= int(debug_env("RADMMM_F8X_MIN_ROWS", "4096"))
-                          and debug_env("RADMMM_FILM_WGRAD8", "1") != "0")
+    meta["wgrad8"] = bool(wgrad8 and prec == "f8x" and meta["nprod"] == 3 and x.shape[0] >= int(debug_env("RADMMM_F8X_MIN_ROWS", "4096")))
     h3_ok = (prec in NPROD and (taps // 2) * dil <= 16 and x.shape[0] >= min_rows and
              x.shape[0] * max(round_up(Cin, 32), Cout) < 2 ** 30)
-    if h3_ok and Cin % 32 != 0 and x.is_cuda and debug_env("RADMMM_CONVNORM_PAD", "1") != "0":
+    if h3_ok and Cin % 32 != 0 and x.is_cuda:
         # the split-f16 kernels want K % 32 == 0: an odd input width (the RADMMM configs' n_text_dim = 520 in the text encoder,
         # the key projection and the predictors' bottlenecks) is zero-padded -- x by one small copy, the weight by autograd's
         # pad, whose zeros leave the weight norm alone -- instead of running the conv on the fp32-MFMA kernels (joint step:
@@ -845,9 +845,8 @@ class ColsumBatch:
         self.items, self.keep = [], []
 
 
-def dact_mul_transposed(g, saved, C, B, T, act, scale, role, yh, yl, fmt, x8_exp, sat_flag, sum_out=None, ylo16=None, defer=None):
-    """y = g * act'(saved) written as the row-major split pair yh/yl (format fmt; ylo16: the fp16 lo part as well when
-    yl is an 8-bit cross array), as the transposed zero-gapped split-f16 copy (pool `role`; role None: no transposed copy)
+def dact_mul_transposed(g, saved, C, B, T, act, scale, role, yh, yl, fmt, x8_exp, sat_flag, sum_out=None, defer=None):
+    """y = g * act'(saved) written as the row-major split pair yh/yl (format fmt), as the transposed zero-gapped split-f16 copy (pool `role`; role None: no transposed copy)
     and as column sums, in one pass and without an fp32 y (radmmm_dact_mul_transposed) -> (transposed-copy tuple, sums [C])."""
     if role is None:
         Tp = T + _TS_FRONT
@@ -860,7 +859,7 @@ def dact_mul_transposed(g, saved, C, B, T, act, scale, role, yh, yl, fmt, x8_exp
     sums = sum_out if (sum_out is not None and sum_out.numel() == C) else _empty(C, like=g)
     check(lib.radmmm_dact_mul_transposed(ptr(g), g.shape[1], ptr(saved), saved.shape[1] if saved is not None else 0, C, B, T, Tp,
                                          _TS_FRONT, act, scale, ptr(yh), ptr(yl), yh.shape[1] if yh is not None else 0,
-                                         split_opts(fmt, x8_exp, sat_flag, ylo16), ptr(oh), ptr(ol), ldk, ptr(part), stream()),
+                                         split_opts(fmt, x8_exp, sat_flag), ptr(oh), ptr(ol), ldk, ptr(part), stream()),
           "dact_mul_transposed")
     if defer is not None:
         defer.add(part, sums, nparts, C)
@@ -919,8 +918,6 @@ def wgrad_h3_slabs(gy_t, x_t, Mc, Nc, ldp, taps, dil, acc_scale, nprod=3):
     assert Kt == Kt2
     tiles = int(lib.radmmm_wgrad_h3_tiles(Mc, Nc, taps))
     S = pick_splits(tiles, Kt, slots=int(lib.radmmm_gemm_cu_slots()))            # one workgroup per CU
-    if debug_env("RADMMM_WGRAD_SPLITS"):              # experiments
-        S = int(debug_env("RADMMM_WGRAD_SPLITS"))
     P = torch.empty(S, taps, Mc, ldp, device=gh.device, dtype=torch.float32)
     if ldp != Nc:
         P.zero_()
@@ -1207,8 +1204,6 @@ def module_scale_box(module, new_forward_on=None) -> "GradScale":
     """The GradScale a module outside the decoder (text encoder, alignment attention) keeps for its stand-alone conv_norm
     calls: with a throw-away dict every conv's backward reads its gradient's maximum on the host -- a synchronisation per
     conv and step.  new_forward_on = device: mark the start of a training forward (publishes the previous pass's stats)."""
-    if debug_env("RADMMM_CONV_OWN_SCALE", "0") == "1":      # A/B aid: every conv's backward scales by its OWN gradient's maximum
-        return {}
     box = module.__dict__.get("_scale_box")
     if box is None:
         box = module.__dict__["_scale_box"] = GradScale()
@@ -1308,6 +1303,39 @@ def ctx_acc_add(acc: dict, slot: int, alloc, write):
     return buf
 
 
+FlowPlan = collections.namedtuple("FlowPlan", "use_rm pair_only layout")
+FlowPlan.__doc__ = """Path decisions of one AffineFlowStepH3Fn node: made once, in forward, by shape and precision; backward reads them.
+use_rm: the weight gradients contract ROW-major split pairs (saved groups X0pair, Hh / Hl, OUTpair) and the bias gradients
+of the in_layer / start convs leave the data-gradient GEMMs' epilogues.  pair_only: these pairs are (hi, 8-bit cross array)
+for radmmm_wgrad_rm8 and there is no fp32 copy of X0, of the hidden states or of the pre-activation gradients.
+layout: what save_groups returned."""
+
+
+def save_groups(ctx, **groups):
+    """ctx.save_for_backward of NAMED groups, each a tensor or a list of tensors; a group that is None is not saved (the path
+    taken does not have it).  Returns the layout load_groups wants."""
+    layout, flat = [], []
+    for name, g in groups.items():
+        if g is None:
+            layout.append((name, None))
+        elif isinstance(g, torch.Tensor):
+            layout.append((name, -1))
+            flat.append(g)
+        else:
+            layout.append((name, len(g)))
+            flat.extend(g)
+    ctx.save_for_backward(*flat)
+    return tuple(layout)
+
+
+def load_groups(ctx, layout):
+    """The groups of save_groups by name: a tensor, a list of tensors, None for a group that was not saved."""
+    it, out = iter(ctx.saved_tensors), {}
+    for name, n in layout:
+        out[name] = None if n is None else next(it) if n < 0 else [next(it) for _ in range(n)]
+    return types.SimpleNamespace(**out)
+
+
 class AffineFlowStepH3Fn(torch.autograd.Function):
     """Same contract as AffineFlowStepFn; the WN convs run on radmmm_rowgemm_h3 (split operands on the f16 / fp8 matrix
     cores, fp32 accumulate).  meta["nprod"]: 3 = split-f16 (three f16 products), 2 = f16 product + FP8 cross terms
@@ -1336,29 +1364,23 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
         gin = dict(nprod=NPR, a8_exp=X8_ACT_EXP, b8_exp=X8_W_EXP, acc_scale=inv_ws, T=T, sat_flag=flag)
         gout = dict(split_fmt=fa, ch_x8_exp=X8_ACT_EXP, c2h_x8_exp=X8_ACT_EXP)
 
-        # Weight gradients contract the ROW-major split pairs (hi, fp16 lo) of the activations / gradients directly
-        # (radmmm_wgrad_rm): the pairs of X0 and of every hidden state are kept for backward; under the FP8-cross scheme
-        # the GEMMs' second operand array is the 8-bit cross array, so the producers write the fp16 lo part as well.
-        use_rm = (NPR in (2, 3) and T >= 32 and B <= 1024 and any(ctx.needs_input_grad) and
-                  debug_env("RADMMM_WGRAD_RM", "1") != "0")
-        # (NPR 2: radmmm_wgrad_rm8 contracts (hi, cross array) pairs -- no fp16 lo copies; RADMMM_DEBUG + RADMMM_WGRAD_RM8=0
-        #  keeps the three-product gradient on (hi, fp16 lo) pairs for A/B runs)
-        rm8 = use_rm and NPR == 2 and Wc % 32 == 0 and debug_env("RADMMM_WGRAD_RM8", "1") != "0"
-        lo16 = (lambda: torch.empty(N, Wc, device=z_in.device, dtype=torch.float16)) if (use_rm and NPR == 2 and not rm8) else (lambda: None)
-        # Round 5: with the FP8-cross weight gradient (rm8) NOTHING reads an fp32 copy of the WN input or of the hidden states
+        # Weight gradients contract the ROW-major split pairs of the activations / gradients directly: the pairs of X0, of
+        # every hidden state and of OUT are kept for backward.  Three products: (hi, fp16 lo) pairs on radmmm_wgrad_rm;
+        # FP8-cross scheme: (hi, 8-bit cross array) pairs on radmmm_wgrad_rm8, the GEMMs' own operands.
+        use_rm = bool(NPR in (2, 3) and T >= 32 and B <= 1024 and any(ctx.needs_input_grad))
+        # Round 5: with the FP8-cross weight gradient NOTHING reads an fp32 copy of the WN input or of the hidden states
         # any more -- the GEMMs and the weight gradients take the split pairs, and the data gradient's softplus' factor is
         # rebuilt from the pair (radmmm_rowgemm_desc.dact_h / dact_x: hi + lo8 * 2^-(11+e), 2^-15 relative) -- so the
         # producers write the pair only (C = NULL): 8 instead of 16 bytes per hidden-state element leave the forward
-        # epilogues, 311 MB per flow step at the benchmark size.  RADMMM_KEEP_FP32=1 (RADMMM_DEBUG) keeps round 4's copies.
-        pair_only = bool(rm8 and debug_env("RADMMM_KEEP_FP32", "0") != "1")
+        # epilogues, 311 MB per flow step at the benchmark size.
+        pair_only = use_rm and NPR == 2
         hid = (lambda: None) if pair_only else (lambda: _empty(N, Wc, like=z_in))
         z1 = _empty(N, ZLD, like=z_in)
         rowgemm(A=z_in, lda=ZLD, B=W_eff, ldb=ZLD, b_layout=0, C=z1, ldc=ZLD, M=N, N=ZLD, K=ZLD, T=T, bias=b_eff)
         X0 = None if pair_only else _empty(N, Kp, like=z_in)
         X0h, X0l = _halves(N, Kp, like=z_in)
-        X0lo = torch.empty(N, Kp, device=z_in.device, dtype=torch.float16) if (use_rm and NPR == 2 and not rm8) else None
         check(lib.radmmm_wn_input_fwd(ptr(cond), D, ptr(z1), ZLD, ptr(X0), Kp, N, D, h, ptr(X0h), ptr(X0l),
-                                      split_opts(fa, X8_ACT_EXP, None, X0lo), stream()), "wn_input_fwd")
+                                      split_opts(fa, X8_ACT_EXP), stream()), "wn_input_fwd")
         perm = (h, D, 0)
         # all conv weights of the flow step in one launch (round 4)
         specs = [(start_v, start_g, Kp, perm)]
@@ -1374,14 +1396,12 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
 
         H = [hid()]
         Hh, Hl = _halves(N, Wc, like=z_in)
-        Hlo = lo16()
         rowgemm_h3(Ah=X0h, Al=X0l, lda_h=Kp, Bh=Wsh, Bl=Wsl, ldb_h=Kp, C=H[0], ldc=Wc, M=N, N=Wc, K=Kp,
-                   bias=start_b, Ch=Hh, Cl=Hl, Clo=Hlo, ldch=Wc, ch_scale=1.0, **gin, **gout)
-        pairs = [(Hh, Hlo if Hlo is not None else Hl)]
-        out_pair = bool(use_rm and (rm8 or NPR == 3) and debug_env("RADMMM_END_WGRAD_RM", "1") != "0")
+                   bias=start_b, Ch=Hh, Cl=Hl, ldch=Wc, ch_scale=1.0, **gin, **gout)
+        pairs = [(Hh, Hl)]
         res_src = bool(2 <= nl <= 4 and debug_env("RADMMM_RES_SRC", "1") != "0")
         # (no fp32 OUT at all when the backward takes OUT's split pair: the last layer's C2 stores are dropped)
-        OUT = None if (res_src and out_pair) else _empty(N, Wc, like=z_in)
+        OUT = None if (res_src and use_rm) else _empty(N, Wc, like=z_in)
         OUTh, OUTl = _halves(N, Wc, like=z_in)
         R = []
         # Round 6 (measured before anything was built: tools/pair_overlap_probe.py,
@@ -1401,14 +1421,13 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
             kt = in_p[3 * j].shape[2]
             Hn = hid()
             Hnh, Hnl = _halves(N, Wc, like=z_in)
-            Hnlo = lo16()
             rowgemm_h3(Ah=Hh, Al=Hl, lda_h=Wc, Bh=Wih[j], Bl=Wil[j], ldb_h=Wc, b_tap_stride_h=Wih[j].stride(0),
                        C=Hn, ldc=Wc, M=N, N=Wc, K=Wc, taps=kt, dil=d, sign=1, lens=lens,
                        a_mask_mode=1 if partial else 0, bias=in_p[3 * j + 2], pconv=1 if partial else 0, ratio_taps=kt,
-                       ratio_dil=d, postmask=1, act=act, Ch=Hnh, Cl=Hnl, Clo=Hnlo, ldch=Wc, ch_scale=1.0, **gin, **gout)
+                       ratio_dil=d, postmask=1, act=act, Ch=Hnh, Cl=Hnl, ldch=Wc, ch_scale=1.0, **gin, **gout)
             H.append(Hn)
             Hh, Hl = Hnh, Hnl
-            pairs.append((Hnh, Hnlo if Hnlo is not None else Hnl))
+            pairs.append((Hnh, Hnl))
             Rj = _empty(N, Wc, like=z_in)
             last = j == nl - 1
             if pair_res and not last:
@@ -1454,23 +1473,16 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
                                              stream()), "affine_coupling_fwd")
         ctx.meta = meta
         ctx.nl = nl
-        ctx.use_rm = use_rm
-        ctx.rm8 = rm8
-        ctx.pair_only = pair_only
-        if pair_only:                             # (placeholders keep the saved-tensor layout; never read on this path)
-            X0 = z1[:0]
-            H = [z1[:0]] * (nl + 1)
-        rm_saved = [X0h, X0lo if X0lo is not None else X0l, *[t for pr in pairs for t in pr]] if use_rm else []
         # the end conv's weight gradient contracts gO with OUT: with OUT's split pair kept (52 MB per flow step) it runs on
         # the same row-major kernels as every other weight gradient of the step instead of the fp32-MFMA one (50 -> ~25 us)
-        ctx.out_pair = out_pair
-        if ctx.out_pair:
-            rm_saved += [OUTh, OUTl]
-        if OUT is None:
-            OUT = z1[:0]                              # (placeholder in the saved-tensor layout; never read with out_pair)
-        ctx.save_for_backward(z_in, z1, X0, OUT, O, lens, W_eff, start_v, start_g, end_w, Wsh, Wsl, inv_s, Weh, Wel,
-                              start_b, end_b,
-                              *H, *R, *Wih, *Wil, *inv_i, *Wrh, *Wrl, *inv_r, *rm_saved, *layer_params)
+        layout = save_groups(
+            ctx, z_in=z_in, z1=z1, O=O, lens=lens, W_eff=W_eff, start_v=start_v, start_g=start_g, end_w=end_w, Wsh=Wsh, Wsl=Wsl,
+            inv_s=inv_s, Weh=Weh, Wel=Wel, start_b=start_b, end_b=end_b, R=R, Wih=Wih, Wil=Wil, inv_i=inv_i, Wrh=Wrh, Wrl=Wrl,
+            inv_r=inv_r, layer_params=layer_params,
+            X0=None if pair_only else X0, H=None if pair_only else H, OUT=None if use_rm else OUT,
+            X0pair=(X0h, X0l) if use_rm else None, Hh=[pr[0] for pr in pairs] if use_rm else None,
+            Hl=[pr[1] for pr in pairs] if use_rm else None, OUTpair=(OUTh, OUTl) if use_rm else None)
+        ctx.plan = FlowPlan(use_rm, pair_only, layout)
         return z_out, log_s
 
     @staticmethod
@@ -1482,25 +1494,15 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
         WPR = 3 if NPR == 2 else NPR             # weight gradients: split-f16 (or the throughput mode's single product)
         B, T, C, D = meta["B"], meta["T"], meta["C"], meta["D"]
         act, scaling, partial = meta["act"], meta["scaling"], meta["partial"]
-        sv = ctx.saved_tensors
-        z_in, z1, X0, OUT, O, lens, W_eff, start_v, start_g, end_w, Wsh, Wsl, inv_s, Weh, Wel, start_b, end_b = sv[:17]
-        p = 17
-        H = sv[p: p + nl + 1]; p += nl + 1
-        R = sv[p: p + nl]; p += nl
-        Wih = sv[p: p + nl]; p += nl
-        Wil = sv[p: p + nl]; p += nl
-        inv_i = sv[p: p + nl]; p += nl
-        Wrh = sv[p: p + nl]; p += nl
-        Wrl = sv[p: p + nl]; p += nl
-        inv_r = sv[p: p + nl]; p += nl
-        use_rm = ctx.use_rm
-        if use_rm:                                # row-major split pairs (hi, fp16 lo) of X0 and of the hidden states
-            X0pair = (sv[p], sv[p + 1]); p += 2
-            Hpair = [(sv[p + 2 * i], sv[p + 2 * i + 1]) for i in range(nl + 1)]; p += 2 * (nl + 1)
-        OUTpair = None
-        if getattr(ctx, "out_pair", False):
-            OUTpair = (sv[p], sv[p + 1]); p += 2
-        layer_params = sv[p:]
+        plan = ctx.plan
+        use_rm, pair_only = plan.use_rm, plan.pair_only
+        sv = load_groups(ctx, plan.layout)
+        z_in, z1, O, lens, W_eff, start_v, start_g, end_w = sv.z_in, sv.z1, sv.O, sv.lens, sv.W_eff, sv.start_v, sv.start_g, sv.end_w
+        Wsh, Wsl, inv_s, Weh, Wel, start_b, end_b = sv.Wsh, sv.Wsl, sv.inv_s, sv.Weh, sv.Wel, sv.start_b, sv.end_b
+        R, Wih, Wil, inv_i, Wrh, Wrl, inv_r, layer_params = sv.R, sv.Wih, sv.Wil, sv.inv_i, sv.Wrh, sv.Wrl, sv.inv_r, sv.layer_params
+        X0, H, OUT = sv.X0, sv.H, sv.OUT                   # fp32 copies: the paths without the split pairs below
+        X0pair, OUTpair = sv.X0pair, sv.OUTpair           # use_rm: row-major split pairs of X0, OUT and of the hidden states
+        Hpair = list(zip(sv.Hh, sv.Hl)) if use_rm else None
         in_p, res_p = layer_params[: 3 * nl], layer_params[3 * nl:]
         h = C // 2
         N = B * T
@@ -1510,12 +1512,9 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
         if g_logs is not None:
             g_logs = g_logs.contiguous()
         box = meta["scale_box"]
-        rm8 = ctx.rm8
-        pair_only = getattr(ctx, "pair_only", False)
-        lo16 = (lambda: torch.empty(N, Wc, device=z_in.device, dtype=torch.float16)) if (use_rm and NPR == 2 and not rm8) else (lambda: None)
 
         def wg_rm(gpair, xpair_, Mc_, Nc_, taps_, dil_, lens_=None):
-            if rm8:
+            if pair_only:                          # (hi, 8-bit cross array) pairs
                 return wgrad_rm8_slabs(gpair, GE, xpair_, X8_ACT_EXP, B, T, Mc_, Nc_, taps_, dil_, 1.0 / SG, lens_)
             return wgrad_rm_slabs(gpair, xpair_, B, T, Mc_, Nc_, taps_, dil_, 1.0 / SG, lens_)
         SG = grad_scale(box, g_zout)
@@ -1534,20 +1533,19 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
         g_end_b = colsum(gO, C, out=grad_out(end_b))
         g_end_w = grad_out(end_w)
         gOh, gOl = split_f16(gO, ZLD, SG, ZLD, NPR, GE, flag)
-        if OUTpair is not None:
+        if use_rm:
             torch.sum(wg_rm((gOh, gOl), OUTpair, C, Wc, 1, 1), dim=0, out=g_end_w.view(1, C, Wc))
         else:
             torch.sum(wgrad_slabs(gO, C, OUT, Wc, Wc, T, None), dim=0, out=g_end_w.view(1, C, Wc))
         # the transposed weights of the whole flow step in ONE launch (round 4; FP8-cross scheme): end conv, per layer the
         # in_layer stack (with the free slot of the fused data gradient filled by res_skip j-1's weights) and the start conv
-        fuse = debug_env("RADMMM_FUSED_DGRAD", "1") != "0"
         pre = None
-        if NPR == 2 and debug_env("RADMMM_MULTI_TRANSPOSE", "1") != "0":
+        if NPR == 2:
             specs, slot = [(Weh, Wel, C, Wc, ZLD, None)], {"end": 0}
             stacks = {}
             for j in range(nl - 1, -1, -1):
                 kt_j = in_p[3 * j].shape[2]
-                if fuse and j > 0:                       # keep_pair below: in_layer j's stack with one free slot
+                if j > 0:                                # keep_pair below: in_layer j's stack with one free slot
                     stacks[j] = _halves(kt_j + 1, Wc, Wc, like=z_in)
                     slot[("in", j)] = len(specs)
                     specs.append((Wih[j], Wil[j], Wc, Wc, Wc, (stacks[j][0][:kt_j], stacks[j][1][:kt_j])))
@@ -1556,7 +1554,7 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
                     specs.append((Wih[j], Wil[j], Wc, Wc, Wc, None))
             for j in range(nl - 1, -1, -1):
                 slot[("res", j)] = len(specs)
-                if fuse and j + 1 < nl:                  # fused below: into the stack of in_layer j + 1
+                if j + 1 < nl:                           # fused below: into the stack of in_layer j + 1
                     kt_n = in_p[3 * (j + 1)].shape[2]
                     specs.append((Wrh[j], Wrl[j], Wc, Wc, Wc, (stacks[j + 1][0][kt_n:], stacks[j + 1][1][kt_n:])))
                 else:
@@ -1571,63 +1569,56 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
         rowgemm_h3(Ah=gOh, Al=gOl, lda_h=ZLD, Bh=WeTh, Bl=WeTl, ldb_h=ZLD, C=gOUT, ldc=Wc, M=N, N=Wc, K=ZLD, **gin)
         g_in: List[Optional[torch.Tensor]] = [None] * (3 * nl)
         g_res: List[Optional[torch.Tensor]] = [None] * (3 * nl)
-        G = None
-        Gh = Gl = Glo = None
         # dL/dH_{j+1} = (k-tap data gradient of in_layer j+1) + (1x1 data gradient of res_skip j): the two GEMMs share their
         # output, so they run as ONE launch -- the 1x1 part is an extra K segment of the k-tap GEMM (radmmm_rowgemm_h3's
         # extra_tap) -- and dL/dH_{j+1} itself never exists in memory.  For that the split copies of g_conv_{j+1} and of
         # gQ_j live in one [2N, Wc] pair (rows [0, N) / [N, 2N)) and the transposed weights of in_layer j+1 and res_skip j
-        # in one [taps + 1] tap stack.  RADMMM_FUSED_DGRAD=0 keeps the two-launch arrangement (A/B runs).
-        # bias gradients of the in_layer convs and of the start conv: column sums of the data-gradient GEMMs' values before
-        # their row scale, taken from the accumulators in the epilogue (radmmm_rowgemm_desc.colsum_out) instead of a pass
-        # over the 52 MB output each.  RADMMM_FUSED_COLSUM=0: the separate radmmm_colsum launches (A/B runs).
-        fuse_cs = use_rm and debug_env("RADMMM_FUSED_COLSUM", "1") != "0"
-        cs_scratch = _empty(int(lib.radmmm_rowgemm_h3_colsum_scratch_floats(N, Wc)), like=z_in) if fuse_cs else None
-        # round 5: the finals of all these partial sums (9 per flow step) are deferred into one launch (ColsumBatch);
-        # RADMMM_COLSUM_BATCH=0 (RADMMM_DEBUG) keeps one radmmm_colsum_final launch each
-        batch = ColsumBatch() if debug_env("RADMMM_COLSUM_BATCH", "1") != "0" else None
+        # in one [taps + 1] tap stack.
+        # use_rm: the bias gradients of the in_layer convs and of the start conv are column sums of the data-gradient GEMMs'
+        # values before their row scale, taken from the accumulators in the epilogue (radmmm_rowgemm_desc.colsum_out) instead
+        # of a pass over the 52 MB output each.  Round 5: the finals of all partial sums of the step (9) are deferred into
+        # one launch.
+        batch = ColsumBatch()
 
         def cs_args(param):
+            """use_rm: (bias gradient of `param`, the scratch its partial rows stay in until the batch is flushed)"""
+            if not use_rm:
+                return None, {}
             gb = grad_out(param)
             gb = gb if (gb is not None and gb.numel() == Wc) else _empty(Wc, like=z_in)
-            if batch is not None:                   # partial rows stay in scratch of their own until the batch is flushed
-                return gb, dict(colsum_scratch=_empty(int(lib.radmmm_rowgemm_h3_colsum_scratch_floats(N, Wc)), like=z_in), _defer=gb)
-            return gb, dict(colsum_out=gb, colsum_scratch=cs_scratch)
+            return gb, dict(colsum_scratch=_empty(int(lib.radmmm_rowgemm_h3_colsum_scratch_floats(N, Wc)), like=z_in))
 
-        def gemm_cs(**kw):
-            """rowgemm_h3 whose column sums are deferred into `batch` when the launch can leave partial rows"""
-            gb = kw.pop("_defer", None)
-            if gb is not None:
-                rows = L.rowgemm_h3_colsum_rows(**kw)
-                if rows > 0:
-                    rowgemm_h3(**kw)
-                    batch.add(kw["colsum_scratch"], gb, rows, kw["N"])
-                    return
+        def gemm_cs(gb, **kw):
+            """rowgemm_h3; the column sums of its accumulators go to gb (if any): through `batch` when the launch leaves partial
+            rows, directly otherwise"""
+            rows = L.rowgemm_h3_colsum_rows(**kw) if gb is not None else 0
+            if gb is not None and rows == 0:
                 kw["colsum_out"] = gb
             rowgemm_h3(**kw)
+            if rows > 0:
+                batch.add(kw["colsum_scratch"], gb, rows, kw["N"])
         pair_h = pair_l = None           # [2N, Wc]: g_conv_{j+1} split in the first half, gQ_j goes into the second
         WT_prev = None                   # (WiT stack [kt+1][Wc][Wc] of layer j+1 with its last slot free, kt, dil)
         x_prev = None
         # Round 5: gQ_j = gOUT * act'(R_j) of ALL res/skip layers in one pass over gOUT (radmmm_dact_mul_rows_multi; gOUT is the
         # same 52 MB for the four layers).  Their destinations are the second halves of the layer pairs, which are therefore
         # allocated up front.  RADMMM_DACT_MULTI=0 (RADMMM_DEBUG): one launch per layer as before.
-        multi = bool(use_rm and fuse and 2 <= nl <= 4 and act and debug_env("RADMMM_DACT_MULTI", "1") != "0")
+        multi = bool(use_rm and 2 <= nl <= 4 and act and debug_env("RADMMM_DACT_MULTI", "1") != "0")
         pre_pairs, gq_pre = {}, None
         if multi:
             for j in range(nl - 1, 0, -1):
                 pre_pairs[j] = _halves(2 * N, Wc, like=z_in)
             top = _halves(N, Wc, like=z_in)
             gq_dst = [(pre_pairs[j + 1][0][N:], pre_pairs[j + 1][1][N:]) if j < nl - 1 else top for j in range(nl)]
-            gq_lo = [lo16() for _ in range(nl)]
-            gq_sums = dact_mul_rows_multi(gOUT, [R[j] for j in range(nl)], Wc, B, T, act, SG, gq_dst, gq_lo, fa, GE, flag,
+            gq_sums = dact_mul_rows_multi(gOUT, [R[j] for j in range(nl)], Wc, B, T, act, SG, gq_dst, [None] * nl, fa, GE, flag,
                                           [grad_out(res_p[3 * j + 2]) for j in range(nl)], defer=batch)
-            gq_pre = (gq_dst, gq_lo, gq_sums)
+            gq_pre = (gq_dst, gq_sums)
         for j in range(nl - 1, -1, -1):
             d = 2 ** j
             kt = in_p[3 * j].shape[2]
-            fused = fuse and pair_h is not None
+            fused = pair_h is not None
             if gq_pre is not None:
-                (gQh, gQl), gQlo, g_res[3 * j + 2] = gq_pre[0][j], gq_pre[1][j], gq_pre[2][j]
+                (gQh, gQl), g_res[3 * j + 2] = gq_pre[0][j], gq_pre[1][j]
                 gy_t = None
             else:
                 if fused:
@@ -1636,45 +1627,41 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
                     gQh, gQl = _halves(N, Wc, like=z_in)
                 # through softplus of the res/skip branch: gQ = gOUT * act'(R_j), written as the dgrad GEMM's row-major split
                 # operand, as the weight gradient's transposed split operand and as bias sums in one pass (no fp32 gQ)
-                gQlo = lo16()
                 gy_t, g_res[3 * j + 2] = dact_mul_transposed(gOUT, R[j], Wc, B, T, act, SG, None if use_rm else "gy", gQh, gQl, fa,
-                                                             GE, flag, sum_out=grad_out(res_p[3 * j + 2]), ylo16=gQlo, defer=batch)
+                                                             GE, flag, sum_out=grad_out(res_p[3 * j + 2]), defer=batch)
             if use_rm:
-                slabs = wg_rm((gQh, gQlo if gQlo is not None else gQl), Hpair[j + 1], Wc, Wc, 1, 1)
+                slabs = wg_rm((gQh, gQl), Hpair[j + 1], Wc, Wc, 1, 1)
             else:
                 # H[j+1]'s transposed copy may still be in the pool from layer j+1's in_layer weight gradient (x_prev, set
                 # below only when that length-masked copy is IDENTICAL to the unmasked one this gradient needs)
                 x_t = x_prev if x_prev is not None else transpose_split_act(H[j + 1], Wc, B, T, None, 0, 1.0, "x")
                 slabs = wgrad_h3_slabs(gy_t, x_t, Wc, Wc, Wc, 1, 1, 1.0 / SG, WPR)
             g_res[3 * j], g_res[3 * j + 1] = weightnorm_bwd(res_p[3 * j], res_p[3 * j + 1], inv_r[j], slabs, Wc, poison=poison)
-            keep_pair = fuse and j > 0               # g_conv_j's split copy becomes the first half of the next pair
+            keep_pair = j > 0                        # g_conv_j's split copy becomes the first half of the next pair
             nh, nlo = pre_pairs[j] if (keep_pair and j in pre_pairs) else _halves(2 * N if keep_pair else N, Wc, like=z_in)
             gch, gcl = nh[:N], nlo[:N]
-            gclo = lo16()
-            cs_here = fuse_cs and (fused or G is None)         # (a launch with an `add` input keeps the separate pass)
             # the fp32 copy of the pre-activation gradient is read by nobody when its bias sums come out of the epilogue
             # and the weight gradient contracts the pair (round 5: C = NULL, 52 MB per launch less to write)
-            g_conv = None if (pair_only and cs_here and use_rm) else _empty(N, Wc, like=z_in)
+            g_conv = None if pair_only else _empty(N, Wc, like=z_in)
             if pair_only:                            # softplus' of the hidden state from its split pair (hi, cross array)
                 dsrc = dict(dact_h=Hpair[j + 1][0], dact_x=Hpair[j + 1][1], lddact_h=Wc, dact_x8_exp=X8_ACT_EXP)
             else:
                 dsrc = dict(dact_src=H[j + 1], lddact=Wc)
             epi = dict(C=g_conv, ldc=Wc, M=N, N=Wc, K=Wc, lens=lens, dact=act, **dsrc,
-                       rowscale=2 if partial else 1, ratio_taps=kt, ratio_dil=d, Ch=gch, Cl=gcl, Clo=gclo, ldch=Wc, ch_scale=SG)
-            gb, cs = cs_args(in_p[3 * j + 2]) if cs_here else (None, {})
+                       rowscale=2 if partial else 1, ratio_taps=kt, ratio_dil=d, Ch=gch, Cl=gcl, ldch=Wc, ch_scale=SG)
+            gb, cs = cs_args(in_p[3 * j + 2])
             if fused:
                 WTh, WTl, ktn, dn = WT_prev
                 if pre is None:
                     transpose_split(Wrh[j], Wrl[j], Wc, Wc, Wc, NPR, out=(WTh[ktn:], WTl[ktn:]))
-                gemm_cs(Ah=pair_h, Al=pair_l, lda_h=Wc, Bh=WTh, Bl=WTl, ldb_h=Wc, b_tap_stride_h=WTh.stride(0), taps=ktn,
+                gemm_cs(gb, Ah=pair_h, Al=pair_l, lda_h=Wc, Bh=WTh, Bl=WTl, ldb_h=Wc, b_tap_stride_h=WTh.stride(0), taps=ktn,
                         dil=dn, sign=-1, a_mask_mode=0, extra_tap=1, extra_a_rows=N, **epi, **gin, **gout, **cs)
             else:
                 WrTh, WrTl = pre[("res", j)] if pre else transpose_split(Wrh[j], Wrl[j], Wc, Wc, Wc, NPR)
-                gemm_cs(Ah=gQh, Al=gQl, lda_h=Wc, Bh=WrTh, Bl=WrTl, ldb_h=Wc, add=G, ldadd=Wc, **epi, **gin, **gout, **cs)
+                gemm_cs(gb, Ah=gQh, Al=gQl, lda_h=Wc, Bh=WrTh, Bl=WrTl, ldb_h=Wc, **epi, **gin, **gout, **cs)
             if use_rm:
-                g_in[3 * j + 2] = gb if cs_here else colsum(g_conv, Wc, 2 if partial else 0, T, lens, kt, d,
-                                                            out=grad_out(in_p[3 * j + 2]))
-                slabs = wg_rm((gch, gclo if gclo is not None else gcl), Hpair[j], Wc, Wc, kt, d, lens if partial else None)
+                g_in[3 * j + 2] = gb
+                slabs = wg_rm((gch, gcl), Hpair[j], Wc, Wc, kt, d, lens if partial else None)
             elif (kt // 2) * d <= _TS_FRONT:
                 gy_t, g_in[3 * j + 2] = transpose_split_act(g_conv, Wc, B, T, None, 0, SG, "gy",
                                                             colsum=(2 if partial else 0, lens, kt, d),
@@ -1701,34 +1688,27 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
                     transpose_split(Wih[j], Wil[j], Wc, Wc, Wc, NPR, out=(WTh[:kt], WTl[:kt]))
                 WT_prev = (WTh, WTl, kt, d)
                 pair_h, pair_l = nh, nlo
-                G = None
-            else:
+            else:                                    # j == 0
                 WiTh, WiTl = pre[("in", j)] if pre else transpose_split(Wih[j], Wil[j], Wc, Wc, Wc, NPR)   # [taps][ci][co]
-                if j == 0:
-                    Gh, Gl = _halves(N, Wc, like=z_in)
-                    Glo = lo16()
-                # (dL/dH_0: consumed as its split pair by the start conv's gradients; fp32 only for an unfused bias sum)
-                G = None if (pair_only and fuse_cs and j == 0) else _empty(N, Wc, like=z_in)
-                g_start_b, cs = cs_args(start_b) if (fuse_cs and j == 0) else (None, {})
-                gemm_cs(Ah=gch, Al=gcl, lda_h=Wc, Bh=WiTh, Bl=WiTl, ldb_h=Wc, b_tap_stride_h=WiTh.stride(0),
+                Gh, Gl = _halves(N, Wc, like=z_in)
+                # (dL/dH_0: consumed as its split pair by the start conv's gradients; fp32 for the transposed-copy path)
+                G = None if pair_only else _empty(N, Wc, like=z_in)
+                g_start_b, cs = cs_args(start_b)
+                gemm_cs(g_start_b, Ah=gch, Al=gcl, lda_h=Wc, Bh=WiTh, Bl=WiTl, ldb_h=Wc, b_tap_stride_h=WiTh.stride(0),
                         C=G, ldc=Wc, M=N, N=Wc, K=Wc, taps=kt, dil=d, sign=-1, lens=lens,
-                        a_mask_mode=0, premask=1 if partial else 0, Ch=Gh if j == 0 else None, Cl=Gl if j == 0 else None,
-                        Clo=Glo if j == 0 else None, ldch=Wc, ch_scale=SG, **gin, **gout, **cs)
+                        a_mask_mode=0, premask=1 if partial else 0, Ch=Gh, Cl=Gl, ldch=Wc, ch_scale=SG,
+                        **gin, **gout, **cs)
                 pair_h = pair_l = None
             check_saturation(box)
             if j == 2 and nl >= 3:
-                if batch is not None:
-                    batch.flush()                    # (the bias gradients announced below must be final)
+                batch.flush()                        # (the bias gradients announced below must be final)
                 # the gradients of the end conv and of WN layers >= 2 are final (their kernels are queued): a gradient
                 # reducer may start their bucket's all-reduce now (rad_mmm_amd/ddp.py, bucket '.hi')
                 notify_grads_final([end_w, end_b] + [t for jj in range(2, nl) for t in (*in_p[3 * jj: 3 * jj + 3], *res_p[3 * jj: 3 * jj + 3])])
-        if batch is not None:
-            batch.flush()
+        batch.flush()
         perm = (h, D, 0)
         if use_rm:
-            if not fuse_cs:
-                g_start_b = colsum(G, Wc, out=grad_out(start_b))
-            slabs = wg_rm((Gh, Glo if Glo is not None else Gl), X0pair, Wc, Kp, 1, 1)
+            slabs = wg_rm((Gh, Gl), X0pair, Wc, Kp, 1, 1)
         else:
             gy_t, g_start_b = transpose_split_act(G, Wc, B, T, None, 0, SG, "gy", colsum=(0, None, 1, 1),
                                                   sum_out=grad_out(start_b))
@@ -1749,7 +1729,7 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
             g_cond = _empty(N, D, like=z_in)
             check(lib.radmmm_wn_input_bwd(ptr(gX0), Kp, ptr(g_cond), D, 0, ptr(gz1), ZLD, N, D, h, stream()), "wn_input_bwd")
         g_b_eff = colsum(gz1, ZLD) if ctx.needs_input_grad[5] else None   # LUS conv: constant zero bias
-        if OUTpair is not None and T % 16 != 0:
+        if use_rm and T % 16 != 0:
             # the channel mix's weight gradient (gz1^T z_in, 160 x 160 over all frames): the fp32-MFMA fast path needs K steps
             # of 16 frames inside one utterance (T % 16 == 0); where it does not apply (configs[4]: T' = 1000, 155 us on the
             # generic kernel) two 8-bit split passes + a one-tile launch of the row-major split kernel replace it.  At
@@ -1787,8 +1767,7 @@ class ConvNormH3Fn(torch.autograd.Function):
         ldy = round_up(Cout, 4)
         # weight gradient on the FP8-cross kernel (conv_norm's wgrad8): ONE split pass writes the input as hi + 8-bit cross array
         # (the weight gradient's pair) AND the fp16 lo part (the three-product GEMM's second operand)
-        wg8 = bool(meta.get("wgrad8") and NPR == 3 and T >= 32 and B <= 1024 and Kx % 32 == 0 and Cout % 4 == 0 and ldy % 4 == 0 and
-                   debug_env("RADMMM_WGRAD_RM", "1") != "0" and debug_env("RADMMM_DACT_ROWS", "1") != "0")
+        wg8 = bool(meta.get("wgrad8") and NPR == 3 and T >= 32 and B <= 1024 and Kx % 32 == 0 and Cout % 4 == 0 and ldy % 4 == 0)
         if wg8:
             xl = torch.empty(N, Kx, device=x.device, dtype=torch.float16)
             xh, xx = split_f16(x, Cin, 1.0, Kx, 2, X8_ACT_EXP, flag, lo16=xl)
@@ -1804,9 +1783,11 @@ class ConvNormH3Fn(torch.autograd.Function):
         ctx.meta = meta
         ctx.has_g, ctx.has_bias, ctx.has_lens = g is not None, bias is not None, lens is not None
         # the row-major split pair of x is the weight gradient's operand (radmmm_wgrad_rm) when it is an fp16 pair
-        ctx.has_xpair = bool(wg8 or (NPR in (2, 3) and T >= 32 and B <= 1024 and Cin % (32 if NPR == 2 else 8) == 0 and
-                                     debug_env("RADMMM_WGRAD_RM", "1") != "0"))
-        ctx.wg8 = wg8
+        ctx.has_xpair = bool(wg8 or (NPR in (2, 3) and T >= 32 and B <= 1024 and Cin % (32 if NPR == 2 else 8) == 0))
+        # with the row-major weight gradient nothing reads an fp32 copy of the pre-activation gradient: backward writes it as the
+        # split pair only and the bias sums leave the same pass as partials (radmmm_dact_mul_rows: 12 instead of 20 bytes per
+        # element over two passes; 32 000-row FiLM convs: dact_mul 77 + colsum 27 us -> one launch).  wg8 implies fused_rows.
+        ctx.wg8, ctx.fused_rows = wg8, bool(ctx.has_xpair and Cout % 4 == 0 and ldy % 4 == 0)
         ctx.save_for_backward(x, v, g if g is not None else v, lens if lens is not None else v, Wh, Wl,
                               inv if inv is not None else v, y, *(((xh, xx) if wg8 else (xh, xl)) if ctx.has_xpair else ()))
         return y
@@ -1833,12 +1814,7 @@ class ConvNormH3Fn(torch.autograd.Function):
         Kp = round_up(Cout, 32)
         rowscale = 2 if partial else (1 if mask_out else 0)
         gph, gpl = _halves(N, Kp, like=y, zero=(Kp != Cout))       # K padding of the data gradient must read as zeros
-        # with the row-major weight gradient nothing reads an fp32 copy of the pre-activation gradient: it is written as the
-        # split pair only and the bias sums leave the same pass as partials (radmmm_dact_mul_rows: 12 instead of 20 bytes per
-        # element over two passes; 32 000-row FiLM convs: dact_mul 77 + colsum 27 us -> one launch)
-        fused_rows = (xpair is not None and Cout % 4 == 0 and ldy % 4 == 0 and N == B * T and
-                      debug_env("RADMMM_DACT_ROWS", "1") != "0")
-        wg8 = bool(getattr(ctx, "wg8", False) and fused_rows)
+        wg8, fused_rows = ctx.wg8, ctx.fused_rows
         gpx = None
         if fused_rows:
             gpre = None

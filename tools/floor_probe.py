@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """What is a GEMM launch of the flow step made of?  Times the step's launch shapes (M = 12 800 frames, 1024 channels, FP8-cross
-scheme) on whatever library RADMMM_LIB_PATH names -- the product build and the timing-only builds of tools/floor_probe.sh
-(-DRADMMM_TIMING=1/2/3: no cross-term MFMAs / no cross-fragment reads either / no MFMA at all; -DRADMMM_TIMING_NOCVT: the
-weight gradient without its in-register hi8 conversions).  Each launch is bracketed by its own pair of HIP events and
+scheme) on whatever library RADMMM_LIB_PATH names (default: the product build; the timing-only builds this probe once
+compared it with are retired, see the "Retired" table of INTEGRATION.md and profiles/r05_nprod1_floor.txt).  Each launch is bracketed by its own pair of HIP events and
 alternates with a 52 MB device copy (a memory-bound neighbour, as inside the training step: twenty GEMMs back to back run
 into the chip's power limit and read 15 % slower); the copy's own time is not part of the figure.
 

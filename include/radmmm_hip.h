@@ -548,6 +548,18 @@ int radmmm_wgrad_rm8(const void* GYh, const void* GYx, int ldg, int g8_exp, cons
                      int R, int T, const int32_t* lens, int x_mask, float* P, int ldp, int64_t split_stride, int Mc, int Nc,
                      int taps, int dil, int splits, float acc_scale, radmmm_stream_t stream);
 
+/* The same weight gradient on ONE product: GYh . Xh alone, on the f16 matrix pipe (csrc/wgrad_rm8.hip, the one-product
+ * instantiation of radmmm_wgrad_rm8's kernel).  For weight gradients that are leaves of the step: the operands are the
+ * fp16 hi planes only, so each operand carries a relative rounding of at most 2^-11 and an element of P differs from the
+ * exact contraction by at most 2^-10 * sum_f |GY||X| (plus the fp32 accumulation); over thousands of frames the
+ * roundings average out (profiles/wgrad_one_pass_emulation.txt).  Tiles, tile order, split-K ranges, masks, tap shifts
+ * and the accumulation order are radmmm_wgrad_rm8's: the slabs differ from that function's by its cross terms only.
+ * GYh [R][ldg] / Xh [R][ldx] as there; ldg, ldx multiples of 32, 16-byte aligned operands, T >= 32, at most 1024
+ * utterances, splits >= 1, radmmm_wgrad_rm_tiles tiles.  Bad arguments return -1 before any HIP call. */
+int radmmm_wgrad_rmh(const void* GYh, int ldg, const void* Xh, int ldx, int R, int T, const int32_t* lens, int x_mask, float* P,
+                     int ldp, int64_t split_stride, int Mc, int Nc, int taps, int dil, int splits, float acc_scale,
+                     radmmm_stream_t stream);
+
 /* Bidirectional single-layer LSTM, recurrent part (reference: the decoder's context LSTM,
  * models/radmmm.py:141-146 = torch.nn.LSTM(bidirectional, batch_first) on a packed batch; gate order
  * i, f, g, o; frames t >= lens[b] produce h = c = 0 as pad_packed_sequence does).

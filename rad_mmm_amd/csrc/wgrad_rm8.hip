@@ -20,6 +20,11 @@
 // barrier ever waits for a transfer that has just been started (with two stages the 32-frame step took 2.4 us against
 // 1.08 us of MFMA work).  Every LDS read of the loop is inline asm: the compiler would otherwise order its own reads
 // behind all outstanding LDS-DMA with vmcnt(0).
+//
+// ONE product (wgrad_rm8_kernel<1>, radmmm_wgrad_rmh): GYh.Xh alone, for the weight gradients of the flow steps' WN convs --
+// leaves of the step, whose rounding feeds nothing else.  The same tile machine (tiles, tile order, split-K ranges, masks,
+// tap shifts, accumulation order k block 0, k block 1 per step, stores) without the lo8 planes: a stage is the two hi arrays
+// (32 KiB), a wave issues 8 DMA pieces per step, and there are no 8-bit fragments, conversions or scaled MFMAs (hh_steps).
 #include <cstdlib>
 #include <type_traits>
 
@@ -39,9 +44,11 @@ typedef __attribute__((address_space(3))) unsigned int* lds_u32_ptr;
 constexpr int BK = 32, TM = 256, TN = 256;          // frames per K step, output tile
 constexpr int HARR = BK * TM * 2;                    // bytes of one fp16 hi array in a stage: 32 rows x 512 B
 constexpr int LARR = BK * TM;                        // bytes of one lo8 array in a stage: 32 rows x 256 B
-constexpr int STAGE = 2 * HARR + 2 * LARR;           // GYh, Xh, GYl8, Xl8 = 48 KiB
 constexpr int NSTAGE = 3;                            // LDS ring: the tile of step s + 2 is fetched during step s
-constexpr int SMEM = NSTAGE * STAGE;                 // 144 KiB
+// PR: products per K step.  2: GYh, Xh, GYl8, Xl8 = 48 KiB per stage, 144 KiB; 1: GYh, Xh = 32 KiB per stage, 96 KiB
+constexpr int stage_bytes(int PR) { return 2 * HARR + (PR == 2 ? 2 * LARR : 0); }
+constexpr int HH_NSTAGE = 3;                         // ring depth of the one-product kernel (hh_steps is written for any depth >= 3)
+constexpr int smem_bytes(int PR) { return (PR == 2 ? NSTAGE : HH_NSTAGE) * stage_bytes(PR); }
 constexpr int OOB = 0x7fffffff;
 
 struct Rm8Args {
@@ -126,9 +133,128 @@ __device__ __forceinline__ i32x4 hi8_of(const Frag& f0, const Frag& f1, float in
   return r;
 }
 
+// ---- The K steps of the ONE-product kernel: prologue, loop and drain.  dma_piece / row_mask / advance_window are the
+// kernel's own (pieces 0..7, stages of 32 KiB); acc[i][j] receives, per step, k block 0 then k block 1 -- the order of the
+// f16 MFMAs of the two-product loop.  Four slots per row block, each opened by its MFMA (32 cycles):
+//     slot 0: MFMA (i, 0, k block 0) | hi fragments of block i + 2, k block 0 (block 7: X unit 0, k block 0, in place)
+//     slot 1: MFMA (i, 1, k block 0) | hi fragments ..., k block 1           (block 7: X unit 1, k block 0)
+//     slot 2: MFMA (i, 0, k block 1) | DMA piece 2 i of the fetched tile (blocks 0 .. 3) (block 7: X unit 0, k block 1)
+//     slot 3: MFMA (i, 1, k block 1) | DMA piece 2 i + 1                                 (block 7: X unit 1, k block 1)
+// Counts.  vmcnt: with a ring of NST stages a wave issues its 8 pieces of tile s + NST - 1 in blocks 0 .. 3 of step s, so at
+// the barrier in front of block 6 the pieces of tiles s + 2 .. s + NST - 1 -- 8 (NST - 2) -- are younger than those of tile
+// s + 1.  lgkmcnt counts ds_read instructions, two per fragment; the stream of a step is, per block, [A k0] [A k1], and in
+// block 7 [A k0] [X0 k0] [A k1] [X1 k0] [X0 k1] [X1 k1]:
+//   * block i, slot 0, after its own [A k0]: block i + 1's fragments are complete when at most 2 reads are younger (block 0:
+//     8 -- the four X reads of block 7 and this one -- but 2 holds there too and is what every block uses);
+//   * top of a step: X k block 0 of both units is complete when at most 4 reads ([X0 k1] [X1 k1]) are younger;
+//   * block 0, slot 1, after its [A k1]: X k block 1 is complete when at most 4 reads (block 0's two fragments) are younger.
+// The prologue issues block 0, then block 7's stream for block 1 and the X fragments, so that step 0 finds the same order.
+// No fragment that is still in flight is ever copied: a fragment register is rewritten only after the last MFMA that
+// reads its old value, and every value is used only behind its wait.
+template <int NST, class Dma, class Mask, class Adv>
+__device__ __forceinline__ void hh_steps(f32x16 (&acc)[8][2], unsigned sm_base, int wave, int lane, int nsteps, const Dma& dma_piece,
+                                         const Mask& row_mask, const Adv& advance_window) {
+  constexpr int STG = stage_bytes(1);
+  constexpr int AHEAD = 8 * (NST - 2);                              // pieces a wave has in flight behind those of the NEXT tile
+#pragma unroll
+  for (int t = 0; t < NST - 1; ++t) {                               // tiles 0 .. NST - 2
+    if (t) advance_window();
+    const unsigned nm = row_mask();
+#pragma unroll
+    for (int w = 0; w < 8; ++w) dma_piece(t, w, t, nm);
+  }
+  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(AHEAD) : "memory");      // tile 0 has landed
+  unsigned ah_base[4], bh_base[2];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) ah_base[q] = sm_base + hi_lane_base(q, lane);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int u = 2 * wave + j;
+    bh_base[j] = sm_base + HARR + hi_lane_base(u & 3, lane) + (u >> 2) * 256;
+  }
+  Frag ga0[4], ga1[4];                                              // A side (GY): ring of four row blocks, k block 0 / 1
+  Frag xb0[2], xb1[2];                                              // X side, unit j, k block 0 / 1
+  frag_issue<0>(ga0[0], ah_base[0]);
+  frag_issue<8192>(ga1[0], ah_base[0]);
+  frag_issue<0>(ga0[1], ah_base[1]);
+  frag_wait2<2>(ga0[0], ga1[0]);
+  frag_issue<0>(xb0[0], bh_base[0]);
+  frag_issue<8192>(ga1[1], ah_base[1]);
+  frag_issue<0>(xb0[1], bh_base[1]);
+  frag_issue<8192>(xb1[0], bh_base[0]);
+  frag_issue<8192>(xb1[1], bh_base[1]);
+  __builtin_amdgcn_sched_barrier(0);
+
+  int buf = 0;
+  for (int s = 0; s < nsteps; ++s) {
+    advance_window();                                              // the window follows the tile being fetched: s + NST - 1
+    const int l_rel = s + NST - 1;
+    unsigned nmask = 0;
+    const int nbuf = buf >= 1 ? buf - 1 : NST - 1;                 // its stage: the one tile s - 1 has left
+    const int xbuf = buf + 1 < NST ? buf + 1 : 0;                  // stage of tile s + 1
+    const unsigned sb = (unsigned)(buf * STG), sbn = (unsigned)(xbuf * STG);
+    frag_wait2<4>(xb0[0], xb0[1]);
+    const f16x8 bh0[2] = {frag_val(xb0[0]), frag_val(xb0[1])};
+    f16x8 bh1[2];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int cur = i & 3, nx1 = (i + 1) & 3, nx2 = (i + 2) & 3;
+      const int i2 = (i + 2) & 7;                                  // row block being read (of this tile, or of the next one)
+      const unsigned sb2 = i + 2 < 8 ? sb : sbn;
+      if (i == 6) {
+        // tile s + 1 has landed as far as this wave fetched it, every read of tile s is complete: publish, and free
+        // tile s's stage for tile s + NST
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(AHEAD) : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      const f16x8 ah0 = frag_val(ga0[cur]), ah1 = frag_val(ga1[cur]);
+      // slot 0
+      acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah0, bh0[0], acc[i][0], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);                           // (the MFMA opens its slot)
+      if (i2 < 4) frag_issue<0>(ga0[nx2], ah_base[i2 & 3] + sb2);
+      else frag_issue<256>(ga0[nx2], ah_base[i2 & 3] + sb2);
+      frag_wait2<2>(ga0[nx1], ga1[nx1]);                           // block i + 1's fragments, read a whole block ago
+      if (i == 7) frag_issue<0>(xb0[0], bh_base[0] + sbn);          // (bh0[0] holds the old value: last read by the MFMA above)
+      __builtin_amdgcn_sched_barrier(0);
+      // slot 1
+      acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah0, bh0[1], acc[i][1], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (i2 < 4) frag_issue<8192>(ga1[nx2], ah_base[i2 & 3] + sb2);
+      else frag_issue<8192 + 256>(ga1[nx2], ah_base[i2 & 3] + sb2);
+      if (i == 0) {
+        frag_wait2<4>(xb1[0], xb1[1]);
+        bh1[0] = frag_val(xb1[0]);
+        bh1[1] = frag_val(xb1[1]);
+      }
+      if (i == 7) frag_issue<0>(xb0[1], bh_base[1] + sbn);
+      __builtin_amdgcn_sched_barrier(0);
+      // slot 2
+      acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah1, bh1[0], acc[i][0], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (i < 4) dma_piece(nbuf, 2 * i, l_rel, nmask);
+      if (i == 1) nmask = row_mask();                              // (first needed by block 2's pieces: the X arrays)
+      if (i == 7) frag_issue<8192>(xb1[0], bh_base[0] + sbn);
+      __builtin_amdgcn_sched_barrier(0);
+      // slot 3
+      acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah1, bh1[1], acc[i][1], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (i < 4) dma_piece(nbuf, 2 * i + 1, l_rel, nmask);
+      if (i == 7) frag_issue<8192>(xb1[1], bh_base[1] + sbn);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    buf = xbuf;
+  }
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __syncthreads();                                                 // the trailing (out-of-range) pieces and look-ahead reads
+}
+
+template <int PR>
 __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
-  asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");      // MODE.FP16_OVFL: the fp8 conversions saturate
+  constexpr int STAGE = stage_bytes(PR);
+  constexpr int NPIECE = PR == 2 ? 12 : 8;                              // DMA pieces of one wave per stage
+  if constexpr (PR == 2) asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");      // MODE.FP16_OVFL: the fp8 conversions saturate
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntm = (a.Mc + TM - 1) / TM, ntn = (a.Nc + TN - 1) / TN;
@@ -153,6 +279,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
   //              4 (w & 3) + wave; lane: row of the pair lane >> 5, LDS unit (lane & 31) >> 2, 16-byte part lane & 3
   //   lo8 planes: 8 pieces per array (four 256-byte frame rows each) -> piece w = 8..11: array (w - 8) >> 1 (GYl8, Xl8), row
   //              quad 4 ((w - 8) & 1) + wave; lane: row of the quad lane >> 4, LDS unit (lane >> 1) & 7, 16-byte half lane & 1
+  //              (PR = 2 only: one product has pieces 0..7 alone, and the lo8 resources below are never used)
   // Per piece: this lane's frame offset within a K step, its byte offset at step 0 of the split, and (X arrays) the
   // frame-in-utterance counter of its row at the step being fetched.
   const __amdgpu_buffer_rsrc_t rGh = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.GYh), 0, a.g_bytes, 0x00020000);
@@ -192,7 +319,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
     p_off[w] = ch < ld ? ((f0 + (isx ? shift : 0)) * ld + ch) * 2 : OOB;
   }
 #pragma unroll
-  for (int w = 8; w < 12; ++w) {
+  for (int w = 8; w < NPIECE; ++w) {
     const int isx = (w - 8) >> 1, q = 4 * ((w - 8) & 1) + wave;
     const int k = 4 * q + (lane >> 4);
     const int u = ((lane >> 1) & 7) ^ (k & 7);                   // source 32-channel unit that lands at this lane's LDS unit
@@ -253,7 +380,9 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
   const int x_sb = (lane >> 5) ? 127 - a.x8_exp : 127 - 11 - a.x8_exp;
   const float g_inv = __builtin_ldexpf(1.f, -a.g8_exp), x_inv = __builtin_ldexpf(1.f, -a.x8_exp);
 
-  if (nsteps > 0) {
+  if constexpr (PR == 1) {
+    if (nsteps > 0) hh_steps<HH_NSTAGE>(acc, (unsigned)reinterpret_cast<size_t>((lds_u32_ptr)sm), wave, lane, nsteps, dma_piece, row_mask, advance_window);
+  } else if (nsteps > 0) {
     // prologue: tiles 0 and 1 (the pieces of a step beyond the split's end are issued all the same, with out-of-range
     // offsets -- zeros into a stage nobody reads -- so that every step issues exactly 12 pieces per wave)
     {
@@ -466,8 +595,8 @@ extern "C" int radmmm_wgrad_rm8(const void* GYh, const void* GYx, int ldg, int g
   const long long g_bytes = (long long)R * ldg * 2, x_bytes = (long long)R * ldx * 2;
   RADMMM_REQUIRE(g_bytes < 0x7fffffffLL && x_bytes < 0x7fffffffLL, "wgrad_rm8: operand >= 2 GiB");
   static int once = [] {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_rm8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       SMEM + 4096);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_rm8_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       smem_bytes(2) + 4096);
     if (e != hipSuccess) {
       radmmm::set_error("hipFuncSetAttribute(wgrad_rm8): %s", hipGetErrorString(e));
       return -2;
@@ -486,6 +615,39 @@ extern "C" int radmmm_wgrad_rm8(const void* GYh, const void* GYx, int ldg, int g
   a.P = P; a.ldp = ldp; a.split_stride = split_stride; a.acc_scale = acc_scale;
   a.g_bytes = (int)g_bytes; a.x_bytes = (int)x_bytes; a.gl_bytes = (int)g_bytes; a.xl_bytes = (int)x_bytes;
   const int tiles = ((Mc + TM - 1) / TM) * ((Nc + TN - 1) / TN) * taps;
-  hipLaunchKernelGGL(wgrad_rm8_kernel, dim3(tiles * splits), dim3(256), SMEM + 4096, static_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(wgrad_rm8_kernel<2>, dim3(tiles * splits), dim3(256), smem_bytes(2) + 4096, static_cast<hipStream_t>(stream), a);
   return radmmm::check_launch("wgrad_rm8");
+}
+
+// One product: GYh . Xh alone (wgrad_rm8_kernel<1>).  GYh / Xh as above; no 8-bit arrays.  Everything else as radmmm_wgrad_rm8:
+// the same tiles, split-K ranges, masks and accumulation order, so the slabs differ from that kernel's by the cross terms only.
+extern "C" int radmmm_wgrad_rmh(const void* GYh, int ldg, const void* Xh, int ldx, int R, int T, const int32_t* lens, int x_mask,
+                                float* P, int ldp, int64_t split_stride, int Mc, int Nc, int taps, int dil, int splits,
+                                float acc_scale, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(GYh && Xh && P, "wgrad_rmh: null pointer");
+  RADMMM_REQUIRE(Mc > 0 && Nc > 0 && taps >= 1 && dil >= 1 && splits >= 1 && R > 0 && T > 0 && R % T == 0 && ldg >= Mc &&
+                     ldx >= Nc && ldg % 32 == 0 && ldx % 32 == 0 && ldp >= Nc && T >= BK && R / T <= 1024,
+                 "wgrad_rmh: bad dims (ldg, ldx %% 32 == 0, R = B * T, T >= 32, B <= 1024, splits >= 1)");
+  RADMMM_REQUIRE(radmmm::aligned16(GYh) && radmmm::aligned16(Xh), "wgrad_rmh: 16-byte aligned operands");
+  const long long g_bytes = (long long)R * ldg * 2, x_bytes = (long long)R * ldx * 2;
+  RADMMM_REQUIRE(g_bytes < 0x7fffffffLL && x_bytes < 0x7fffffffLL, "wgrad_rmh: operand >= 2 GiB");
+  static int once = [] {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_rm8_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       smem_bytes(1) + 4096);
+    if (e != hipSuccess) {
+      radmmm::set_error("hipFuncSetAttribute(wgrad_rmh): %s", hipGetErrorString(e));
+      return -2;
+    }
+    return 0;
+  }();
+  if (once) return once;
+  Rm8Args a = {};
+  a.GYh = static_cast<const _Float16*>(GYh); a.Xh = static_cast<const _Float16*>(Xh);
+  a.lens = lens; a.x_mask = x_mask;
+  a.R = R; a.T = T; a.ldg = ldg; a.ldx = ldx; a.Mc = Mc; a.Nc = Nc; a.taps = taps; a.dil = dil; a.splits = splits;
+  a.P = P; a.ldp = ldp; a.split_stride = split_stride; a.acc_scale = acc_scale;
+  a.g_bytes = (int)g_bytes; a.x_bytes = (int)x_bytes;
+  const int tiles = ((Mc + TM - 1) / TM) * ((Nc + TN - 1) / TN) * taps;
+  hipLaunchKernelGGL(wgrad_rm8_kernel<1>, dim3(tiles * splits), dim3(256), smem_bytes(1) + 4096, static_cast<hipStream_t>(stream), a);
+  return radmmm::check_launch("wgrad_rmh");
 }

@@ -961,6 +961,21 @@ def wgrad_rm8_slabs(gy_pair, g8_exp, x_pair, x8_exp, B, T, Mc, Nc, taps, dil, ac
     return P
 
 
+def wgrad_rmh_slabs(gh, xh, B, T, Mc, Nc, taps, dil, acc_scale, lens=None):
+    """Weight gradient on ONE product from the ROW-major fp16 hi planes [B*T, ld] (radmmm_wgrad_rmh: GYh.Xh on the f16
+    pipe; for leaves of the step) -> P [S, taps, Mc, Nc].  The same slab count as wgrad_rm8_slabs."""
+    R = B * T
+    assert gh.shape[0] >= R and xh.shape[0] >= R and gh.dtype == torch.float16 and xh.dtype == torch.float16
+    tiles = int(lib.radmmm_wgrad_rm_tiles(Mc, Nc, taps))
+    S = pick_splits(tiles, R, slots=int(lib.radmmm_gemm_cu_slots()))              # one workgroup per CU
+    P = torch.empty(S, taps, Mc, Nc, device=gh.device, dtype=torch.float32)
+    assert gh.stride(1) == 1 and xh.stride(1) == 1
+    check(lib.radmmm_wgrad_rmh(ptr(gh), gh.stride(0), ptr(xh), xh.stride(0), R, T, ptr(lens), 1 if lens is not None else 0,
+                               ptr(P), Nc, P.stride(0), Mc, Nc, taps, dil, S, acc_scale, stream()),
+          "wgrad_rmh")
+    return P
+
+
 def _all_reduce_or(flags: torch.Tensor) -> torch.Tensor:
     """bitwise OR of small non-negative int32 flag words over the ranks of the default process group.  RCCL / NCCL have no
     BOR reduction (torch raises "Cannot use ReduceOp.BOR with NCCL"): the low 16 bits go out as 0/1 words under MAX."""
@@ -1303,12 +1318,25 @@ def ctx_acc_add(acc: dict, slot: int, alloc, write):
     return buf
 
 
-FlowPlan = collections.namedtuple("FlowPlan", "use_rm pair_only layout")
+FlowPlan = collections.namedtuple("FlowPlan", "use_rm pair_only wgrad_products layout")
 FlowPlan.__doc__ = """Path decisions of one AffineFlowStepH3Fn node: made once, in forward, by shape and precision; backward reads them.
 use_rm: the weight gradients contract ROW-major split pairs (saved groups X0pair, Hh / Hl, OUTpair) and the bias gradients
 of the in_layer / start convs leave the data-gradient GEMMs' epilogues.  pair_only: these pairs are (hi, 8-bit cross array)
 for radmmm_wgrad_rm8 and there is no fp32 copy of X0, of the hidden states or of the pre-activation gradients.
+wgrad_products (pair_only): 1 = the WN convs' weight gradients (start, in_layers, res_skip layers, end) contract the hi planes
+alone (radmmm_wgrad_rmh), 2 = hi planes and FP8 cross terms (radmmm_wgrad_rm8); wgrad_products_env().
 layout: what save_groups returned."""
+
+
+def wgrad_products_env() -> int:
+    """RADMMM_WGRAD_PRODUCTS: products of the WN convs' weight gradients under the FP8-cross scheme, 1 (default) or 2.  A
+    weight gradient is a leaf of the step -- its rounding feeds no other result -- and over the frames of a batch the
+    roundings of the fp16 hi planes average out (profiles/wgrad_one_pass_emulation.txt).  Read where a flow
+    step's plan is made (forward); backward follows the plan."""
+    v = os.environ.get("RADMMM_WGRAD_PRODUCTS", "1")
+    if v not in ("1", "2"):
+        raise ValueError(f"RADMMM_WGRAD_PRODUCTS={v!r}: 1 or 2")
+    return int(v)
 
 
 def save_groups(ctx, **groups):
@@ -1482,7 +1510,7 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
             X0=None if pair_only else X0, H=None if pair_only else H, OUT=None if use_rm else OUT,
             X0pair=(X0h, X0l) if use_rm else None, Hh=[pr[0] for pr in pairs] if use_rm else None,
             Hl=[pr[1] for pr in pairs] if use_rm else None, OUTpair=(OUTh, OUTl) if use_rm else None)
-        ctx.plan = FlowPlan(use_rm, pair_only, layout)
+        ctx.plan = FlowPlan(use_rm, pair_only, wgrad_products_env() if pair_only else NPR, layout)
         return z_out, log_s
 
     @staticmethod
@@ -1513,7 +1541,9 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
             g_logs = g_logs.contiguous()
         box = meta["scale_box"]
 
-        def wg_rm(gpair, xpair_, Mc_, Nc_, taps_, dil_, lens_=None):
+        def wg_rm(gpair, xpair_, Mc_, Nc_, taps_, dil_, lens_=None, leaf=True):
+            if pair_only and leaf and plan.wgrad_products == 1:      # a WN conv's weight gradient: the hi planes alone
+                return wgrad_rmh_slabs(gpair[0], xpair_[0], B, T, Mc_, Nc_, taps_, dil_, 1.0 / SG, lens_)
             if pair_only:                          # (hi, 8-bit cross array) pairs
                 return wgrad_rm8_slabs(gpair, GE, xpair_, X8_ACT_EXP, B, T, Mc_, Nc_, taps_, dil_, 1.0 / SG, lens_)
             return wgrad_rm_slabs(gpair, xpair_, B, T, Mc_, Nc_, taps_, dil_, 1.0 / SG, lens_)
@@ -1736,7 +1766,7 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
             # T % 16 == 0 the same move was measured at 42.34 / 42.35 against 42.31 / 42.32 ms per step: nothing, not taken.
             gzh, gzl = split_f16(gz1, ZLD, SG, ZLD, NPR, GE, flag)
             zh, zl = split_f16(z_in, ZLD, 1.0, ZLD, NPR, X8_ACT_EXP)
-            g_W_eff = wg_rm((gzh, gzl), (zh, zl), ZLD, ZLD, 1, 1).sum(0).view(ZLD, ZLD)
+            g_W_eff = wg_rm((gzh, gzl), (zh, zl), ZLD, ZLD, 1, 1, leaf=False).sum(0).view(ZLD, ZLD)      # (not a WN conv: as it was)
         else:
             g_W_eff = wgrad_slabs(gz1, ZLD, z_in, ZLD, ZLD, T, None).sum(0).view(ZLD, ZLD)
         g_zin = _empty(N, ZLD, like=z_in)

@@ -12,10 +12,17 @@ every WN convolution (forward product and data-gradient product) replaced by an 
 
 A = activations / gradients, B = weights (x256), f16 split x = hi + lo, q8 = OCP e4m3 round-to-nearest with
 saturation at 448 (lo parts scaled by 2^11 first).  All split values are exactly representable, so products are exact in
-fp32 and only the fp32 accumulation (as on the MFMA) rounds.  Weight gradients stay exact fp32 here (they run on their own
-kernel).  Test infrastructure: imports oracle/.
+fp32 and only the fp32 accumulation (as on the MFMA) rounds.  Weight gradients stay exact fp32 in that table (they run on
+their own kernel).
 
-    python tools/emu_products.py [--tag cfg2_small]
+--wgrad {exact,f8x,1p}: a second table, for the WEIGHT gradients of the same convolutions.  Forward and data gradient are
+emulated as f8x (the default parity mode); the weight gradient gy^T x is contracted on the split operands (x at scale 1, gy
+at the pass's power-of-two scale) as f8x (hi.hi + both e4m3 cross terms: radmmm_wgrad_rm8) or 1p (hi.hi alone:
+radmmm_wgrad_rmh), and every parameter gradient of dimension >= 2 is compared with the exact fp32 run: L2 rel, max over
+max, norm rel -- the worst of each with its parameter.  --tag bench8: the benchmark's architecture on the first 8
+utterances of its batch (seed 1234, T = 800).  Test infrastructure: imports oracle/.
+
+    python tools/emu_products.py [--tag cfg2_small] [--wgrad f8x 1p]
 """
 import argparse
 import json
@@ -31,6 +38,7 @@ sys.path.insert(0, ROOT)
 from oracle import radmmm_oracle as O  # noqa: E402
 
 MODE = "exact"
+WGRAD = "exact"
 W_SCALE = 256.0
 GRAD_S = [None]
 
@@ -116,7 +124,16 @@ class EmuConv(torch.autograd.Function):
             amax = float(gy.abs().max())
             GRAD_S[0] = 2.0 ** np.floor(np.log2(16.0 / amax)) if amax > 0 else 1.0
         gx = product(lambda a, b: F.conv_transpose1d(a, b, None, 1, pad, 0, 1, dil), gy, w, GRAD_S[0], W_SCALE, (1, 0))
-        gw = torch.nn.grad.conv1d_weight(x, w.shape, gy, 1, pad, dil)
+        cw = lambda a, b: torch.nn.grad.conv1d_weight(a, w.shape, b, 1, pad, dil)      # noqa: E731
+        if WGRAD == "exact":
+            gw = cw(x, gy)
+        else:
+            xh, xl = f16_split(x)
+            gh, gl = f16_split(gy * GRAD_S[0])
+            gw = cw(xh, gh)
+            if WGRAD == "f8x":
+                gw = gw + cw(q8_lo(xl), q8(gh)) + cw(q8(xh), q8_lo(gl))
+            gw = gw / GRAD_S[0]
         return gx, gw, None, None
 
 
@@ -131,12 +148,68 @@ def emu_conv1d(x, w, b=None, stride=1, padding=0, dilation=1, groups=1):
 _real_conv1d = F.conv1d
 
 
-def run(tag):
-    g = dict(np.load(os.path.join(ROOT, "tests", "golden", f"decoder_{tag}.npz")))
-    kw = {k[4:]: (v.item() if v.shape == () else v) for k, v in g.items() if k.startswith("cfg.")}
-    cfg = O.DecoderConfig(**kw)
+BENCH = dict(n_speaker_dim=16, use_accent_emb_for_decoder=True, n_accent_dim=8, n_text_dim=512, n_f0_dims=1,
+             n_energy_avg_dims=1, n_mel_channels=80, n_early_size=2, n_early_every=2, n_group_size=2, scaling_fn="tanh",
+             affine_activation="softplus", use_partial_padding=True, n_conv_layers_per_step=4, n_flows=8)      # bench.py's headline
+
+
+def load_case(tag):
+    if tag == "bench8":
+        cfg = O.DecoderConfig(**BENCH)
+        b = {k: torch.from_numpy(v[:8]) for k, v in O.synthetic_batch(32, 800, cfg, 1234, False).items()}
+    else:
+        g = dict(np.load(os.path.join(ROOT, "tests", "golden", f"decoder_{tag}.npz")))
+        kw = {k[4:]: (v.item() if v.shape == () else v) for k, v in g.items() if k.startswith("cfg.")}
+        cfg = O.DecoderConfig(**kw)
+        b = {k: torch.from_numpy(v) for k, v in O.synthetic_batch(int(g["B"]), int(g["T"]), cfg, 1234, bool(g["ragged"])).items()}
     sd = {k: torch.from_numpy(np.asarray(v)) for k, v in O.procedural_decoder_state(O.decoder_state_shapes(cfg)).items()}
-    b = {k: torch.from_numpy(v) for k, v in O.synthetic_batch(int(g["B"]), int(g["T"]), cfg, 1234, bool(g["ragged"])).items()}
+    return cfg, sd, b
+
+
+def grads(cfg, sd, b, mode, wgrad):
+    """Parameter gradients of forward + NLL + backward with the products emulated as `mode` and the weight gradients as `wgrad`."""
+    global MODE, WGRAD
+    MODE, WGRAD = mode, wgrad
+    GRAD_S[0] = None
+    p = {k: (v.clone().requires_grad_(True) if v.dtype == torch.float32 and "running" not in k
+             and not k.endswith((".p", "lower_diag", "input_mean")) else v) for k, v in sd.items()}
+    O.F.conv1d = emu_conv1d
+    try:
+        out = O.decoder_forward(p, cfg, b["mel"], b["spk"], b["context"], b["lengths"], b["f0"], b["energy"], b["accent"])
+        lm, _ = O.decoder_loss(out, b["lengths"], cfg.n_group_size)
+        lm.backward()
+    finally:
+        O.F.conv1d = _real_conv1d
+        MODE, WGRAD = "exact", "exact"
+    return {k: v.grad.double() for k, v in p.items() if v.requires_grad and v.grad is not None and v.dim() >= 2}
+
+
+def run_wgrad(tag, wgrads):
+    cfg, sd, b = load_case(tag)
+    ex = grads(cfg, sd, b, "exact", "exact")
+    return [wgrad_row(tag, b, ex, grads(cfg, sd, b, "f8x", wgrad), wgrad) for wgrad in wgrads]
+
+
+def wgrad_row(tag, b, ex, em, wgrad):
+    worst = {"l2_rel": (0.0, None), "max_over_max": (0.0, None), "norm_rel": (0.0, None)}
+    for k, e in ex.items():
+        if float(e.norm()) <= 1e-7:
+            continue
+        d = em[k] - e
+        fig = {"l2_rel": float(d.norm() / e.norm()), "max_over_max": float(d.abs().max() / e.abs().max()),
+               "norm_rel": abs(float(em[k].norm()) - float(e.norm())) / float(e.norm())}
+        for name, v in fig.items():
+            if v > worst[name][0]:
+                worst[name] = (v, k)
+    row = {"case": tag, "products": "f8x", "wgrad": wgrad, "mel_frames": int(b["mel"].shape[0] * b["mel"].shape[2])}
+    for name, (v, k) in worst.items():
+        row[name], row[name + "_at"] = v, k
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def run(tag):
+    cfg, sd, b = load_case(tag)
     res = {}
     for mode in ("exact", "h3", "f8x", "f6x", "2pa", "2pb", "1p"):
         global MODE
@@ -173,6 +246,11 @@ def run(tag):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--tag", default="cfg2_small")
+    ap.add_argument("--wgrad", choices=("exact", "f8x", "1p"), nargs="+", default=None,
+                    help="the weight-gradient table instead: products f8x, weight gradients as given (one row each), per-parameter figures")
     a = ap.parse_args()
     torch.set_num_threads(8)
-    run(a.tag)
+    if a.wgrad is not None:
+        run_wgrad(a.tag, a.wgrad)
+    else:
+        run(a.tag)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""radmmm_wgrad_rm8 at the benchmark shapes (12 800 frames, 1024 x 1024; 5 taps dil 2 = the in_layer conv, 1 tap = res_skip):
-launch time, and -- for A/B builds of the library (RADMMM_LIB_PATH) -- a dump / bit comparison of the results.
-    python tools/wgrad8_probe.py [--dump FILE | --compare FILE] [--reps 30] [--loop N]   (--loop: launches only, for rocprofv3 --pmc)"""
+"""radmmm_wgrad_rm8 (--products 2, the default) or radmmm_wgrad_rmh (--products 1: the hi planes alone) at the benchmark shapes
+(12 800 frames, 1024 x 1024; 5 taps dil 2 = the in_layer conv, 1 tap = res_skip): launch time, and -- for A/B builds of the
+library (RADMMM_LIB_PATH) -- a dump / bit comparison of the results.
+    python tools/wgrad8_probe.py [--products 1] [--dump FILE | --compare FILE] [--reps 30] [--loop N]   (--loop: launches only, for rocprofv3 --pmc)"""
 import argparse
 import json
 import os
@@ -18,6 +19,7 @@ def main():
     ap.add_argument("--dump")
     ap.add_argument("--compare")
     ap.add_argument("--loop", type=int, default=0)
+    ap.add_argument("--products", type=int, choices=(1, 2), default=2)
     args = ap.parse_args()
     import rad_mmm_amd  # noqa: F401
     from rad_mmm_amd import ops
@@ -33,7 +35,10 @@ def main():
     cases = [("in_layer (5 taps, dil 2, masked)", 5, 2, lens), ("res_skip (1 tap)", 1, 1, None), ("5 taps, dil 1, masked", 5, 1, lens)]
     outs = {}
     for name, taps, dil, ln in cases:
-        fn = lambda: ops.wgrad_rm8_slabs((gh, gx), ops.X8_GRAD_EXP, (xh, xx), ops.X8_ACT_EXP, B, T, C, C, taps, dil, 1.0 / SG, ln)
+        if args.products == 1:
+            fn = lambda: ops.wgrad_rmh_slabs(gh, xh, B, T, C, C, taps, dil, 1.0 / SG, ln)
+        else:
+            fn = lambda: ops.wgrad_rm8_slabs((gh, gx), ops.X8_GRAD_EXP, (xh, xx), ops.X8_ACT_EXP, B, T, C, C, taps, dil, 1.0 / SG, ln)
         if args.loop:
             if taps == 5 and dil == 2:
                 for _ in range(args.loop):
@@ -50,7 +55,7 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         us = e0.elapsed_time(e1) * 1e3 / args.reps
-        print(json.dumps({"case": name, "splits": int(P.shape[0]), "us": round(us, 1),
+        print(json.dumps({"products": args.products, "case": name, "splits": int(P.shape[0]), "us": round(us, 1),
                           "fp32_equiv_tflops": round(2.0 * B * T * C * C * taps / us / 1e6, 1)}), flush=True)
     if args.dump:
         torch.save(outs, args.dump)

@@ -729,6 +729,43 @@ int radmmm_wg_end_coupling_fwd(const float* S, int lds, const float* Wend, const
 int radmmm_wg_nll_parts(const float* X, int ldx, int n_group, const float* ls, const int32_t* lens, int B, int Tg,
                         double* parts, radmmm_stream_t stream);
 
+/* The backward pass of that direction: what the row GEMMs (b_layout 1), radmmm_wgrad_f32 and radmmm_colsum do not cover.
+ * Rows at or past an item's length are never read, and every gradient row there is written as 0.  No atomics: every
+ * result is bitwise repeatable.  Additive entry points of ABI 4.
+ *   wg_coupling_bwd  o = Wend S[r] + bend recomputed as wg_end_coupling_fwd does; x1 = Xs[r, col0 + n_half ..] the
+ *                    coupling's saved input, g = dX[r, col0 + n_half ..] the gradient of its output:
+ *                      dO[r] = [g, g * exp(log_s) * x1 + g_ls]  ([rows][2 n_half]: the gradient of o)
+ *                      dX[r, col0 + n_half + k] = g[k] * exp(log_s[k])  in place
+ *                      dS[r, :] = Wend^T dO[r]
+ *                    g_ls: ldg == 0: one device value for every row and channel (the likelihood's -1/N); else
+ *                    g_ls[r*ldg + k].  The limits of wg_end_coupling.
+ *   wg_gate_bwd      dA[r, c] = g[r, c] * sig * (1 - tanh^2), dA[r, C + c] = g[r, c] * tanh * sig * (1 - sig), tanh and
+ *                    sig of wg_gate's arguments a[r, :] + cond[r, cond_off:]; dA may be a column slice of the
+ *                    conditioning gradient (ldda its pitch)
+ *   wg_start_bwd     dX[r, col0 + i] += sum_c Wt[i*C + c] * dH[r, c], Wt [n_half][C] the start weight transposed, n_half <= 4
+ *   wg_outer_reduce  out[m*N + n] = sum over the valid rows of A[r*lda + m] * B[r*ldb + n], m < M <= 8 (A == NULL: M = 1,
+ *                    A = 1: column sums): the weight / bias gradients of end, start and the 1x1 mix.  One partial per
+ *                    256-row tile in scratch (radmmm_wg_outer_reduce_scratch_floats(rows, M, N) floats), added in tile
+ *                    order by radmmm_colsum_final.
+ *   wg_inv_logdet    for n <= 32 square matrices of sizes cs[k] <= 8 (a HOST array) packed one after the other in W:
+ *                    Winv (same packing, fp32) and logdet[k] = log|det W_k| (float64) by Gauss-Jordan elimination with
+ *                    partial pivoting in float64, one launch: the training step never leaves the device for them
+ *   wg_ungroup_cond  the inverse permutation of wg_group_cond: up[b*up_item_stride + (g*n_group + j)*n_mel + m] =
+ *                    rows[(b*Tg + g)*ldr + m*n_group + j], 0 for g >= lens[b] */
+int radmmm_wg_coupling_bwd(const float* S, int lds, const float* Wend, const float* bend, const float* Xs, int ldxs,
+                           float* dX, int ldx, int col0, int n_half, int C, const float* g_ls, int ldg, float* dO,
+                           float* dS, int ldds, const int32_t* lens, int rows, int T, radmmm_stream_t stream);
+int radmmm_wg_gate_bwd(const float* a, int lda, const float* cond, int ldcond, int cond_off, const float* g, int ldg,
+                       float* dA, int ldda, int C, const int32_t* lens, int rows, int T, radmmm_stream_t stream);
+int radmmm_wg_start_bwd(const float* dH, int ldh, const float* Wt, float* dX, int ldx, int col0, int n_half, int C,
+                        const int32_t* lens, int rows, int T, radmmm_stream_t stream);
+int radmmm_wg_outer_reduce(const float* A, int lda, int M, const float* B, int ldb, int N, float* out, float* scratch,
+                           const int32_t* lens, int rows, int T, radmmm_stream_t stream);
+int64_t radmmm_wg_outer_reduce_scratch_floats(int rows, int M, int N);
+int radmmm_wg_inv_logdet(const float* W, const int32_t* cs, int n, float* Winv, double* logdet, radmmm_stream_t stream);
+int radmmm_wg_ungroup_cond(const float* rows, int ldr, float* up, int64_t up_item_stride, const int32_t* lens, int B,
+                           int Tg, int n_mel, int n_group, radmmm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Batched synthesis glue (TTSModel.sample_full / reconstruct_from_batch_attributes, tts_lightning_modules.py:286-437).
  * Additive entry points of ABI 4.  No floating-point atomics: every result is bitwise repeatable.

@@ -224,6 +224,12 @@ def _load() -> C.CDLL:
         "radmmm_wg_mix_fwd": [p, i, i, i, p, p, i, i, p],
         "radmmm_wg_end_coupling_fwd": [p, i, p, p, p, i, i, i, i, p, i, p, p, i, i, p],
         "radmmm_wg_nll_parts": [p, i, i, p, p, i, i, p, p],
+        "radmmm_wg_coupling_bwd": [p, i, p, p, p, i, p, i, i, i, i, p, i, p, p, i, p, i, i, p],
+        "radmmm_wg_gate_bwd": [p, i, p, i, i, p, i, p, i, i, p, i, i, p],
+        "radmmm_wg_start_bwd": [p, i, p, p, i, i, i, i, p, i, i, p],
+        "radmmm_wg_outer_reduce": [p, i, i, p, i, i, p, p, p, i, i, p],
+        "radmmm_wg_inv_logdet": [p, p, i, p, p, p],
+        "radmmm_wg_ungroup_cond": [p, i, p, i64, p, i, i, i, i, p],
         "radmmm_synth_durations": [p, i64, p, i, i, i, p, p, p, p],
         "radmmm_synth_regulate": [p, i64, i, i, i, p, p, i, i, p, i, p],
         "radmmm_synth_f0_stats": [p, i64, p, i64, p, i, i, p, i, p],
@@ -246,6 +252,7 @@ def _load() -> C.CDLL:
                        "radmmm_stft_mel_scratch_floats": [i, i, i, i, i],
                        "radmmm_collate_scratch_floats": [i, i, i, i, i],
                        "radmmm_lstm_scratch_bytes": [i, i, i], "radmmm_lstm_hseq_bytes": [i, i, i],
+                       "radmmm_wg_outer_reduce_scratch_floats": [i, i, i],
                        "radmmm_sumsq_scratch_floats": []}.items():
         fn = getattr(lib, name)
         fn.argtypes = args

@@ -621,3 +621,370 @@ extern "C" int radmmm_wg_nll_parts(const float* X, int ldx, int n_group, const f
                        Tg, parts);
   return radmmm::check_launch("wg_nll_parts");
 }
+
+// ---- the backward pass of the audio -> latent direction ------------------------------------------------------------
+// What the row GEMMs, radmmm_wgrad_f32 and radmmm_colsum do not cover.  Rows at or past an item's length are never read
+// and every gradient row there is written as 0, so the GEMMs that follow may read all rows.  No atomics: the row
+// reductions (wg_outer_reduce) leave one partial per 256-row tile, summed in tile order by radmmm_colsum_final.
+namespace {
+
+// o = Wend S[r] + bend recomputed as the forward does (end_dot), b = o[:NH], log_s = o[NH:], x1 the saved coupling input:
+//   d_b = dX1', d_log_s = dX1' * exp(log_s) * x1 + g_ls, dX1 = dX1' * exp(log_s) (in place), dO[r] = [d_b, d_log_s],
+//   dS[r, :] = Wend^T dO[r].  g_ls: one value for every row (ldg == 0) or [rows][ldg].
+template <int NO>
+__global__ __launch_bounds__(256) void coupling_bwd_kernel(const float* __restrict__ S, int lds,
+                                                           const float* __restrict__ Wend,
+                                                           const float* __restrict__ bend,
+                                                           const float* __restrict__ Xs, int ldxs, float* __restrict__ dX,
+                                                           int ldx, int col0, int C, const float* __restrict__ gls,
+                                                           int ldg, float* __restrict__ dO, float* __restrict__ dS,
+                                                           int ldds, const int32_t* __restrict__ lens, long long rows,
+                                                           int T) {
+  extern __shared__ __align__(16) float sh[];
+  float* w = sh;                    // [NO][C]
+  float* be = sh + NO * C;          // [NO]
+  for (int i = threadIdx.x; i < NO * C; i += blockDim.x) w[i] = Wend[i];
+  for (int i = threadIdx.x; i < NO; i += blockDim.x) be[i] = bend ? bend[i] : 0.f;
+  __syncthreads();
+  constexpr int NH = NO / 2;
+  const int sub = threadIdx.x & 15, rloc = threadIdx.x >> 4;
+  for (long long r0 = blockIdx.x * 16LL; r0 < rows; r0 += gridDim.x * 16LL) {
+    const long long r = r0 + rloc;
+    const bool valid = row_valid(r, rows, lens, T);
+    float acc[NO];
+    end_dot<NO>(S, lds, w, C, r, valid, sub, acc);
+    float d[NO];
+#pragma unroll
+    for (int o = 0; o < NO; ++o) d[o] = 0.f;
+    if (valid) {
+      // every lane of the row computes the same NO values (a few loads that hit the same cache line)
+      const float* x1 = Xs + r * ldxs + col0 + NH;
+      const float* g1 = dX + r * ldx + col0 + NH;
+#pragma unroll
+      for (int k = 0; k < NH; ++k) {
+        const float e = expf(acc[NH + k] + be[NH + k]);
+        const float g = g1[k];
+        d[k] = g;
+        d[NH + k] = fmaf(g * e, x1[k], ldg ? gls[r * ldg + k] : gls[0]);
+      }
+    }
+    if (r < rows) {
+      float* dsr = dS + r * ldds;
+      for (int c = sub * 4; c < C; c += 64) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int o = 0; o < NO; ++o) {
+          const float4 ww = *reinterpret_cast<const float4*>(w + o * C + c);
+          v.x = fmaf(ww.x, d[o], v.x);
+          v.y = fmaf(ww.y, d[o], v.y);
+          v.z = fmaf(ww.z, d[o], v.z);
+          v.w = fmaf(ww.w, d[o], v.w);
+        }
+        *reinterpret_cast<float4*>(dsr + c) = v;
+      }
+    }
+    __syncthreads();   // every lane of a row has read dX1' before lane 0 overwrites it (uniform trip count: r0 is per block)
+    if (sub == 0 && r < rows) {
+      float* g1 = dX + r * ldx + col0 + NH;
+#pragma unroll
+      for (int k = 0; k < NH; ++k) g1[k] = valid ? d[k] * expf(acc[NH + k] + be[NH + k]) : 0.f;
+#pragma unroll
+      for (int o = 0; o < NO; ++o) dO[r * NO + o] = d[o];
+    }
+  }
+}
+
+__device__ __forceinline__ void gate_bwd1(float ta, float tc, float sa, float sc, float g, float& dt, float& ds) {
+  const float t = tanhf(ta + tc), s = 1.f / (1.f + expf(-(sa + sc)));
+  dt = g * s * (1.f - t * t);
+  ds = g * t * s * (1.f - s);
+}
+
+// dA[r, c] = g[r, c] * sig * (1 - tanh^2), dA[r, C + c] = g[r, c] * tanh * sig * (1 - sig) of the gate's inputs
+// a[r, :] + cond[r, off:]; 0 in the rows past an item's length (a / cond / g are not read there)
+__global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__ a, int lda,
+                                                       const float* __restrict__ cond, int ldcond, int off,
+                                                       const float* __restrict__ g, int ldg, float* __restrict__ dA,
+                                                       int ldda, int C, const int32_t* __restrict__ lens,
+                                                       long long rows, int T) {
+  const int q = C >> 2;
+  const long long total = rows * q;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / q;
+    const int c = (int)(i - r * q) * 4;
+    float4 dt = make_float4(0.f, 0.f, 0.f, 0.f), ds = dt;
+    if (row_valid(r, rows, lens, T)) {
+      const float* ar = a + r * lda + c;
+      const float* cr = cond + r * ldcond + off + c;
+      const float4 ta = *reinterpret_cast<const float4*>(ar), sa = *reinterpret_cast<const float4*>(ar + C);
+      const float4 tc = *reinterpret_cast<const float4*>(cr), sc = *reinterpret_cast<const float4*>(cr + C);
+      const float4 gv = *reinterpret_cast<const float4*>(g + r * ldg + c);
+      gate_bwd1(ta.x, tc.x, sa.x, sc.x, gv.x, dt.x, ds.x);
+      gate_bwd1(ta.y, tc.y, sa.y, sc.y, gv.y, dt.y, ds.y);
+      gate_bwd1(ta.z, tc.z, sa.z, sc.z, gv.z, dt.z, ds.z);
+      gate_bwd1(ta.w, tc.w, sa.w, sc.w, gv.w, dt.w, ds.w);
+    }
+    float* dr = dA + r * ldda + c;
+    *reinterpret_cast<float4*>(dr) = dt;
+    *reinterpret_cast<float4*>(dr + C) = ds;
+  }
+}
+
+// dX[r, col0 + i] += sum_c Wt[i*C + c] * dH[r, c], i < NH (Wt = the start weight transposed, in LDS): end_dot's sum
+template <int NH>
+__global__ __launch_bounds__(256) void start_bwd_kernel(const float* __restrict__ dH, int ldh,
+                                                        const float* __restrict__ Wt, float* __restrict__ dX, int ldx,
+                                                        int col0, int C, const int32_t* __restrict__ lens,
+                                                        long long rows, int T) {
+  extern __shared__ __align__(16) float sh[];
+  for (int i = threadIdx.x; i < NH * C; i += blockDim.x) sh[i] = Wt[i];
+  __syncthreads();
+  const int sub = threadIdx.x & 15, rloc = threadIdx.x >> 4;
+  for (long long r0 = blockIdx.x * 16LL; r0 < rows; r0 += gridDim.x * 16LL) {
+    const long long r = r0 + rloc;
+    const bool valid = row_valid(r, rows, lens, T);
+    float acc[NH];
+    end_dot<NH>(dH, ldh, sh, C, r, valid, sub, acc);
+    if (sub == 0 && valid) {
+      float* xr = dX + r * ldx + col0;
+#pragma unroll
+      for (int i = 0; i < NH; ++i) xr[i] += acc[i];
+    }
+  }
+}
+
+// part[(tile*M + m)*N + n] = sum over the valid rows r of the 256-row tile of A[r*lda + m] * B[r*ldb + n] (A == NULL:
+// M = 1 and A = 1, a column sum).  A thread owns one column n and M <= 8 accumulators; with N < 256 the 256 / NB row
+// subsets of a tile (NB = N rounded up to a power of two) are added in subset order through LDS.
+constexpr int OR_TILE = 256, OR_MAX_M = 8;
+__global__ __launch_bounds__(256) void outer_reduce_kernel(const float* __restrict__ A, int lda, int M,
+                                                           const float* __restrict__ Bm, int ldb, int N, int NB,
+                                                           float* __restrict__ part,
+                                                           const int32_t* __restrict__ lens, long long rows, int T) {
+  __shared__ float red[256 * OR_MAX_M];
+  const int RS = 256 / NB;
+  const int nl = threadIdx.x % NB, rsub = threadIdx.x / NB;
+  const int n = blockIdx.y * NB + nl;
+  const long long tile0 = (long long)blockIdx.x * OR_TILE;
+  float acc[OR_MAX_M];
+#pragma unroll
+  for (int m = 0; m < OR_MAX_M; ++m) acc[m] = 0.f;
+  if (n < N) {
+    for (int k = rsub; k < OR_TILE; k += RS) {
+      const long long r = tile0 + k;
+      if (!row_valid(r, rows, lens, T)) continue;
+      const float b = Bm[r * ldb + n];
+      if (A) {
+        const float* ar = A + r * lda;
+#pragma unroll
+        for (int m = 0; m < OR_MAX_M; ++m)
+          if (m < M) acc[m] = fmaf(ar[m], b, acc[m]);
+      } else {
+        acc[0] += b;
+      }
+    }
+  }
+  if (RS > 1) {
+#pragma unroll
+    for (int m = 0; m < OR_MAX_M; ++m) red[(rsub * OR_MAX_M + m) * NB + nl] = acc[m];
+    __syncthreads();
+    if (rsub == 0) {
+#pragma unroll
+      for (int m = 0; m < OR_MAX_M; ++m) {
+        float s = 0.f;
+        for (int q = 0; q < RS; ++q) s += red[(q * OR_MAX_M + m) * NB + nl];
+        acc[m] = s;
+      }
+    }
+  }
+  if (rsub == 0 && n < N) {
+#pragma unroll
+    for (int m = 0; m < OR_MAX_M; ++m)
+      if (m < M) part[((long long)blockIdx.x * M + m) * N + n] = acc[m];
+  }
+}
+
+// per flow k (one thread each): Winv = W^-1 (fp32) and logdet[k] = log|det W| by Gauss-Jordan elimination with partial
+// pivoting in float64; W is c x c, c <= 8, flow k's matrix at offs[k] floats in both packed arrays
+struct inv_plan { int n; int c[32]; int off[32]; };
+__global__ void inv_logdet_kernel(const float* __restrict__ W, inv_plan plan, float* __restrict__ Winv,
+                                  double* __restrict__ logdet) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= plan.n) return;
+  const int c = plan.c[k];
+  const float* w = W + plan.off[k];
+  double a[8][16];
+  for (int i = 0; i < c; ++i)
+    for (int j = 0; j < c; ++j) {
+      a[i][j] = (double)w[i * c + j];
+      a[i][c + j] = i == j ? 1.0 : 0.0;
+    }
+  double ld = 0.0;
+  for (int p = 0; p < c; ++p) {
+    int best = p;
+    for (int i = p + 1; i < c; ++i)
+      if (fabs(a[i][p]) > fabs(a[best][p])) best = i;
+    if (best != p)
+      for (int j = 0; j < 2 * c; ++j) {
+        const double t = a[p][j];
+        a[p][j] = a[best][j];
+        a[best][j] = t;
+      }
+    const double piv = a[p][p];
+    ld += log(fabs(piv));
+    for (int j = 0; j < 2 * c; ++j) a[p][j] /= piv;
+    for (int i = 0; i < c; ++i) {
+      if (i == p) continue;
+      const double f = a[i][p];
+      for (int j = 0; j < 2 * c; ++j) a[i][j] -= f * a[p][j];
+    }
+  }
+  float* o = Winv + plan.off[k];
+  for (int i = 0; i < c; ++i)
+    for (int j = 0; j < c; ++j) o[i * c + j] = (float)a[i][c + j];
+  logdet[k] = ld;
+}
+
+// the inverse permutation of group_cond_kernel: up[b*item_stride + (g*ng + j)*n_mel + m] = rows[(b*Tg + g)*ldr + m*ng + j]
+// for g < lens[b], else 0 (rows past an item's length are not read)
+__global__ __launch_bounds__(256) void ungroup_cond_kernel(const float* __restrict__ rows, int ldr,
+                                                           float* __restrict__ up, long long item_stride,
+                                                           const int32_t* __restrict__ lens, long long R, int Tg,
+                                                           int n_mel, int ng) {
+  const int cols = n_mel * ng;
+  const long long total = R * cols;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / cols;
+    const int c = (int)(i - r * cols);             // = j*n_mel + m: the order of the destination
+    const int j = c / n_mel, m = c - j * n_mel;
+    const int b = (int)(r / Tg), g = (int)(r - (long long)b * Tg);
+    const bool valid = !lens || g < lens[b];
+    up[b * item_stride + (long long)g * cols + c] = valid ? rows[r * ldr + m * ng + j] : 0.f;
+  }
+}
+
+}  // namespace
+
+extern "C" int radmmm_wg_coupling_bwd(const float* S, int lds, const float* Wend, const float* bend, const float* Xs,
+                                      int ldxs, float* dX, int ldx, int col0, int n_half, int C, const float* g_ls,
+                                      int ldg, float* dO, float* dS, int ldds, const int32_t* lens, int rows, int T,
+                                      radmmm_stream_t stream) {
+  RADMMM_REQUIRE(S && Wend && Xs && dX && g_ls && dO && dS, "wg_coupling_bwd: null pointer");
+  const int NO = 2 * n_half;
+  const long long smem_twin = ((long long)NO * C + NO * NO + NO) * 4;   // the limit of the forward kernels
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && C > 0 && C % 4 == 0 && lds % 4 == 0 && lds >= C &&
+                     ldds % 4 == 0 && ldds >= C && n_half >= 1 && n_half <= 4 && col0 >= 0 && col0 + NO <= ldx &&
+                     col0 + NO <= ldxs && (ldg == 0 || ldg >= n_half) && smem_twin <= 32768,
+                 "wg_coupling_bwd: bad dims (rows=%d T=%d C=%d lds=%d ldds=%d n_half=%d col0=%d ldx=%d ldxs=%d ldg=%d)",
+                 rows, T, C, lds, ldds, n_half, col0, ldx, ldxs, ldg);
+  RADMMM_REQUIRE(radmmm::aligned16(S) && radmmm::aligned16(Wend) && radmmm::aligned16(dS),
+                 "wg_coupling_bwd: S / Wend / dS must be 16B aligned");
+  const size_t smem = ((size_t)NO * C + NO) * 4;
+  const dim3 grid(grid_for(((long long)rows + 15) / 16, 1)), block(256);
+#define WG_CPL_BWD(NOV)                                                                                              \
+  hipLaunchKernelGGL(coupling_bwd_kernel<NOV>, grid, block, smem, ST(stream), S, lds, Wend, bend, Xs, ldxs, dX, ldx, \
+                     col0, C, g_ls, ldg, dO, dS, ldds, lens, (long long)rows, T)
+  switch (NO) {
+    case 2: WG_CPL_BWD(2); break;
+    case 4: WG_CPL_BWD(4); break;
+    case 6: WG_CPL_BWD(6); break;
+    default: WG_CPL_BWD(8); break;
+  }
+#undef WG_CPL_BWD
+  return radmmm::check_launch("wg_coupling_bwd");
+}
+
+extern "C" int radmmm_wg_gate_bwd(const float* a, int lda, const float* cond, int ldcond, int cond_off, const float* g,
+                                  int ldg, float* dA, int ldda, int C, const int32_t* lens, int rows, int T,
+                                  radmmm_stream_t stream) {
+  RADMMM_REQUIRE(a && cond && g && dA, "wg_gate_bwd: null pointer");
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && C > 0 && C % 4 == 0 && lda % 4 == 0 && lda >= 2 * C &&
+                     ldcond % 4 == 0 && cond_off >= 0 && cond_off % 4 == 0 && cond_off + 2 * C <= ldcond &&
+                     ldg % 4 == 0 && ldg >= C && ldda % 4 == 0 && ldda >= 2 * C,
+                 "wg_gate_bwd: bad dims (rows=%d T=%d C=%d lda=%d ldcond=%d cond_off=%d ldg=%d ldda=%d)", rows, T, C, lda,
+                 ldcond, cond_off, ldg, ldda);
+  RADMMM_REQUIRE(radmmm::aligned16(a) && radmmm::aligned16(cond) && radmmm::aligned16(g) && radmmm::aligned16(dA),
+                 "wg_gate_bwd: a / cond / g / dA must be 16B aligned");
+  hipLaunchKernelGGL(gate_bwd_kernel, dim3(grid_for((long long)rows * (C / 4), 256)), dim3(256), 0, ST(stream), a, lda,
+                     cond, ldcond, cond_off, g, ldg, dA, ldda, C, lens, (long long)rows, T);
+  return radmmm::check_launch("wg_gate_bwd");
+}
+
+extern "C" int radmmm_wg_start_bwd(const float* dH, int ldh, const float* Wt, float* dX, int ldx, int col0, int n_half,
+                                   int C, const int32_t* lens, int rows, int T, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(dH && Wt && dX, "wg_start_bwd: null pointer");
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && C > 0 && C % 4 == 0 && ldh % 4 == 0 && ldh >= C && n_half >= 1 &&
+                     n_half <= 4 && col0 >= 0 && col0 + n_half <= ldx && (long long)n_half * C * 4 <= 32768,
+                 "wg_start_bwd: bad dims (rows=%d T=%d C=%d ldh=%d n_half=%d col0=%d ldx=%d)", rows, T, C, ldh, n_half,
+                 col0, ldx);
+  RADMMM_REQUIRE(radmmm::aligned16(dH) && radmmm::aligned16(Wt), "wg_start_bwd: dH / Wt must be 16B aligned");
+  const size_t smem = (size_t)n_half * C * 4;
+  const dim3 grid(grid_for(((long long)rows + 15) / 16, 1)), block(256);
+#define WG_START_BWD(NHV)                                                                                          \
+  hipLaunchKernelGGL(start_bwd_kernel<NHV>, grid, block, smem, ST(stream), dH, ldh, Wt, dX, ldx, col0, C, lens, \
+                     (long long)rows, T)
+  switch (n_half) {
+    case 1: WG_START_BWD(1); break;
+    case 2: WG_START_BWD(2); break;
+    case 3: WG_START_BWD(3); break;
+    default: WG_START_BWD(4); break;
+  }
+#undef WG_START_BWD
+  return radmmm::check_launch("wg_start_bwd");
+}
+
+extern "C" int64_t radmmm_wg_outer_reduce_scratch_floats(int rows, int M, int N) {
+  return ((int64_t)rows + OR_TILE - 1) / OR_TILE * (int64_t)(M > 0 ? M : 1) * N;
+}
+
+extern "C" int radmmm_wg_outer_reduce(const float* A, int lda, int M, const float* B, int ldb, int N, float* out,
+                                      float* scratch, const int32_t* lens, int rows, int T, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(B && out && scratch, "wg_outer_reduce: null pointer");
+  if (!A) M = 1;
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && M >= 1 && M <= OR_MAX_M && N >= 1 && ldb >= N && (!A || lda >= M) &&
+                     (long long)M * N <= 0x7fffffffLL,
+                 "wg_outer_reduce: bad dims (rows=%d T=%d M=%d N=%d lda=%d ldb=%d; M <= 8)", rows, T, M, N, lda, ldb);
+  int NB = 1;
+  while (NB < N && NB < 256) NB <<= 1;
+  const int tiles = (rows + OR_TILE - 1) / OR_TILE;
+  RADMMM_REQUIRE((N + NB - 1) / NB <= 65535, "wg_outer_reduce: N=%d too wide", N);
+  hipLaunchKernelGGL(outer_reduce_kernel, dim3(tiles, (N + NB - 1) / NB), dim3(256), 0, ST(stream), A, lda, M, B, ldb, N,
+                     NB, scratch, lens, (long long)rows, T);
+  const int rc = radmmm::check_launch("wg_outer_reduce");
+  if (rc) return rc;
+  return radmmm_colsum_final(scratch, out, tiles, M * N, stream);
+}
+
+extern "C" int radmmm_wg_inv_logdet(const float* W, const int32_t* cs, int n, float* Winv, double* logdet,
+                                    radmmm_stream_t stream) {
+  RADMMM_REQUIRE(W && cs && Winv && logdet, "wg_inv_logdet: null pointer");
+  RADMMM_REQUIRE(n >= 1 && n <= 32, "wg_inv_logdet: n=%d flows (1 .. 32)", n);
+  RADMMM_REQUIRE((reinterpret_cast<uintptr_t>(logdet) & 7) == 0, "wg_inv_logdet: logdet must be 8B aligned");
+  inv_plan plan;
+  plan.n = n;
+  int off = 0;
+  for (int k = 0; k < n; ++k) {
+    RADMMM_REQUIRE(cs[k] >= 1 && cs[k] <= 8, "wg_inv_logdet: matrix %d is %d x %d (1 .. 8)", k, cs[k], cs[k]);
+    plan.c[k] = cs[k];
+    plan.off[k] = off;
+    off += cs[k] * cs[k];
+  }
+  for (int k = n; k < 32; ++k) plan.c[k] = plan.off[k] = 0;
+  hipLaunchKernelGGL(inv_logdet_kernel, dim3(1), dim3(64), 0, ST(stream), W, plan, Winv, logdet);
+  return radmmm::check_launch("wg_inv_logdet");
+}
+
+extern "C" int radmmm_wg_ungroup_cond(const float* rows, int ldr, float* up, int64_t up_item_stride, const int32_t* lens,
+                                      int B, int Tg, int n_mel, int n_group, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(up && rows, "wg_ungroup_cond: null pointer");
+  RADMMM_REQUIRE(B > 0 && Tg > 0 && n_mel > 0 && n_group > 0 && ldr >= n_mel * n_group &&
+                     up_item_stride >= (int64_t)Tg * n_group * n_mel && (int64_t)B * Tg <= 0x7fffffffLL,
+                 "wg_ungroup_cond: bad dims (B=%d Tg=%d n_mel=%d n_group=%d ldr=%d item_stride=%lld)", B, Tg, n_mel,
+                 n_group, ldr, (long long)up_item_stride);
+  const long long R = (long long)B * Tg;
+  hipLaunchKernelGGL(ungroup_cond_kernel, dim3(grid_for(R * n_mel * n_group, 256)), dim3(256), 0, ST(stream), rows, ldr,
+                     up, (long long)up_item_stride, lens, R, Tg, n_mel, n_group);
+  return radmmm::check_launch("wg_ungroup_cond");
+}

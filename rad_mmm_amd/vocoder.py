@@ -76,12 +76,12 @@ def pack_polyphase(w: torch.Tensor, u: int, p: int, off: int = 0, ldk: Optional[
     Cin, Cout, k = w.shape
     ldk = ldk or Cin
     h = polyphase_shifts(k, u, p, off)
-    j = torch.arange(k)
+    j = torch.arange(k, device=w.device)        # on w's device: no host -> device copy, so a training step can call it
     r = (j - p) % u
     s = (r + p - j) // u
     tap = off + s + h
     Wp = torch.zeros(2 * h + 1, u, Cout, ldk, dtype=w.dtype, device=w.device)
-    Wp[tap.to(w.device), r.to(w.device), :, :Cin] = w.permute(2, 1, 0)
+    Wp[tap, r, :, :Cin] = w.permute(2, 1, 0)
     return Wp.reshape(2 * h + 1, u * Cout, ldk)
 
 

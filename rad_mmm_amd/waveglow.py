@@ -22,10 +22,17 @@ The other direction, audio -> latent (glow.py:207-249 WaveGlow.forward, :43-59 W
 on the untouched half: the audio enters the rows with all n_group columns live (wg_group_audio), each flow is the forward
 1x1 mix (wg_mix_fwd), the WN, and the forward coupling with the row's sum of log_s (wg_end_coupling_fwd); an early
 output is n_early_size columns that simply stop being live, so the final X IS z in the reference's channel order; the
-likelihood's two ragged sums are wg_nll_parts.  No backward pass: this evaluates a model, it does not train one.
+likelihood's two ragged sums are wg_nll_parts.
+
+Training (train.py:62-152 of that vocoder): in training mode nll_loss and forward come out of one autograd node
+(_WaveGlowFn) whose backward walks the flows from last to first, runs one flow's WN again into per-layer buffers and
+back-propagates through it with row GEMMs (b_layout 1), radmmm_wgrad_f32, radmmm_colsum and the wg_*_bwd kernels;
+apply_weight_norm / remove_weight_norm switch between the reference's weight_g / weight_v parameters and the folded
+form.  Eval mode records no graph and runs exactly the launches above.
 """
 from __future__ import annotations
 
+import ctypes
 import json
 import pickle
 from typing import Optional, Sequence, Tuple, Union
@@ -34,13 +41,14 @@ import torch
 from torch import nn
 
 from . import ops
-from ._lib import RadmmmError, check, f32c, fp32_region, lib, ptr, rowgemm, stream
+from ._lib import RadmmmError, check, f32c, fp32_region, lib, ptr, rowgemm, stream, wgrad
 from .vocoder import Denoiser, _lens_arg, _to_device, fold_weight_norm, pack_polyphase
 
 UPSAMPLE_KERNEL = 1024     # glow.py:183-186: hard-coded in the reference
 HOP = 256
 _A_OPERAND_BYTES = 2 ** 31 - 2 ** 16     # the row GEMM's 16-row fast path needs A operands below 2 GiB
 _COND_BYTES = 8 << 30                    # cap of the per-flow conditioning buffer [rows, 2 * n_channels * n_layers]
+_TRAIN_ACT_BYTES = 8 << 30               # cap of what the backward of one flow holds (see WaveGlow._train_chunk)
 
 
 class _WN(nn.Module):
@@ -96,9 +104,30 @@ def fold_weight_norm_keys(state_dict: dict) -> dict:
     return out
 
 
+def unfold_weight_norm_keys(state_dict: dict, prefixes) -> dict:
+    """the inverse direction for a model with weight norm applied: for every conv named in `prefixes` the keys become
+    <name>weight_g / <name>weight_v (a folded <name>weight gives g = the rows' norms, v = the weight; the parametrization
+    form is renamed); every other key unchanged"""
+    out = {}
+    for k, v in state_dict.items():
+        base = next((p for p in prefixes if k.startswith(p)), None)
+        leaf = k[len(base):] if base else None
+        if leaf == "weight":
+            v = v.float()
+            out[base + "weight_g"] = v.reshape(v.shape[0], -1).norm(dim=1).reshape(-1, 1, 1)
+            out[base + "weight_v"] = v
+        elif leaf == "parametrizations.weight.original0":
+            out[base + "weight_g"] = v
+        elif leaf == "parametrizations.weight.original1":
+            out[base + "weight_v"] = v
+        else:
+            out[k] = v
+    return out
+
+
 class WaveGlow(nn.Module):
-    """WaveGlow(n_mel_channels, n_flows, n_group, n_early_every, n_early_size, WN_config) of glow.py:178-205, inference
-    only.  state_dict keys are those of a reference model after remove_weightnorm (upsample.weight / .bias,
+    """WaveGlow(n_mel_channels, n_flows, n_group, n_early_every, n_early_size, WN_config) of glow.py:178-205.
+    state_dict keys are those of a reference model after remove_weightnorm (upsample.weight / .bias,
     WN.{k}.start / in_layers.{i} / cond_layer / res_skip_layers.{i} / end .weight / .bias, convinv.{k}.conv.weight);
     load_state_dict also takes the weight-normed keys (.weight_g / .weight_v) and folds them.
 
@@ -126,6 +155,14 @@ class WaveGlow(nn.Module):
     forward((mel, audio)) -> (z, log_s_list, log_det_W_list) as glow.py:207-249 (full lengths; log_det_W_list[k] =
     B * Tg * log|det W_k|, glow.py:100) for WaveGlowLoss; noise_from_z(z) -> the tuple `noise` of infer, so that
     infer(mel, lens, sigma=1.0, noise=noise_from_z(z)) returns the analysed audio.
+
+    Training (self.training and grad mode on; eval mode is untouched): nll_loss(mel, audio, lens=None, sigma=1.0) -> the
+    `loss` of analyze as a scalar with a grad_fn, and forward((mel, audio)) -> the same tuple with a grad_fn; backward()
+    fills .grad of every parameter through the HIP backward pass (no atomics: two identical steps give identical bits;
+    with host lengths no device -> host synchronisation).  apply_weight_norm() / remove_weight_norm() switch start,
+    in_layers, cond_layer and res_skip_layers between weight_g / weight_v (a reference training checkpoint's keys) and
+    the folded weight; load_state_dict takes either form in either state.  torch.optim.Adam on parameters() is the
+    reference's optimizer.  fp32 only, one GPU.
 
     Deliberate differences from the reference's forward: log|det W| where torch.logdet is NaN for a negative
     determinant; with ragged lengths every sum and the normalisation run over an item's own valid samples (the
@@ -157,6 +194,9 @@ class WaveGlow(nn.Module):
         self.n_remaining_channels = n_rem
         self._folded = None
         self._folded_key = None
+        self._weight_normed = False
+        self._train_chunk_items = None     # items per chunk of the training step (None: from the memory caps)
+        self._train_events = None          # a dict here receives the training step's device events (see _run)
 
     @property
     def noise_shapes(self):
@@ -166,7 +206,47 @@ class WaveGlow(nn.Module):
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         self._folded = None
-        return super().load_state_dict(fold_weight_norm_keys(state_dict), strict=strict, assign=assign)
+        if self._weight_normed:
+            state_dict = unfold_weight_norm_keys(state_dict, [n + "." for n, _ in self._normed_convs()])
+        else:
+            state_dict = fold_weight_norm_keys(state_dict)
+        return super().load_state_dict(state_dict, strict=strict, assign=assign)
+
+    # ---- weight norm as trainable parameters (glow.py:105-151: start, in_layers, cond_layer, res_skip_layers) --------
+    def _normed_convs(self):
+        for k, wn in enumerate(self.WN):
+            yield f"WN.{k}.start", wn.start
+            for i, m in enumerate(wn.in_layers):
+                yield f"WN.{k}.in_layers.{i}", m
+            yield f"WN.{k}.cond_layer", wn.cond_layer
+            for i, m in enumerate(wn.res_skip_layers):
+                yield f"WN.{k}.res_skip_layers.{i}", m
+
+    def apply_weight_norm(self) -> "WaveGlow":
+        """every conv the reference weight-norms gets weight_g [Cout, 1, 1] (the rows' norms) and weight_v (the weight)
+        in place of weight, with the reference's names: state_dict() then has a reference training checkpoint's keys.
+        `end`, `upsample` and the 1x1 mixes stay plain."""
+        if self._weight_normed:
+            return self
+        for _, m in self._normed_convs():
+            w = m.weight.detach()
+            g = w.reshape(w.shape[0], -1).norm(dim=1).reshape(-1, 1, 1)
+            del m._parameters["weight"]
+            m.register_parameter("weight_g", nn.Parameter(g.clone()))
+            m.register_parameter("weight_v", nn.Parameter(w.clone()))
+        self._weight_normed, self._folded = True, None
+        return self
+
+    def remove_weight_norm(self) -> "WaveGlow":
+        """back to the folded form: weight = weight_g * weight_v / ||weight_v||"""
+        if not self._weight_normed:
+            return self
+        for _, m in self._normed_convs():
+            w = fold_weight_norm(m.weight_v.detach().float(), m.weight_g.detach().float())
+            del m._parameters["weight_g"], m._parameters["weight_v"]
+            m.register_parameter("weight", nn.Parameter(w))
+        self._weight_normed, self._folded = False, None
+        return self
 
     # ---- weights in the kernels' layout, folded once (again only when a parameter changed) -------------------------
     def _key(self):
@@ -181,34 +261,79 @@ class WaveGlow(nn.Module):
         W[:, :, :Cin] = w.detach().float().permute(2, 0, 1)
         return W
 
+    def _weight_names(self):
+        """the folded-form parameter names, in the order of the autograd node's weight arguments"""
+        names = ["upsample.weight", "upsample.bias"]
+        L = self.WN[0].n_layers
+        for k in range(self.n_flows):
+            p = f"WN.{k}."
+            convs = (["start", "cond_layer"] + [f"in_layers.{i}" for i in range(L)]
+                     + [f"res_skip_layers.{i}" for i in range(L)] + ["end"])
+            for n in convs:
+                names += [p + n + ".weight", p + n + ".bias"]
+            names.append(f"convinv.{k}.conv.weight")
+        return names
+
+    @staticmethod
+    def _conv_weight(m: nn.Module) -> torch.Tensor:
+        """the conv's weight, folded from weight_g / weight_v where weight norm is applied (plain torch ops: autograd
+        carries a gradient of the folded weight on to g and v)"""
+        if "weight_g" in m._parameters:
+            return fold_weight_norm(m.weight_v.float(), m.weight_g.float())
+        return m.weight
+
+    def _weights(self):
+        out = []
+        for n in self._weight_names():
+            mod, leaf = n.rsplit(".", 1)
+            m = self.get_submodule(mod)
+            out.append(self._conv_weight(m) if leaf == "weight" else m.bias)
+        return out
+
     def _fold(self):
         key = self._key()
         if self._folded is not None and self._folded_key == key:
             return self._folded
+        W = {n: t.detach() for n, t in zip(self._weight_names(), self._weights())}
+        invs, logdets = [], []
+        for k in range(self.n_flows):
+            w = W[f"convinv.{k}.conv.weight"]
+            W64 = w[:, :, 0].double().cpu()
+            invs.append(torch.linalg.inv(W64).float().to(w.device).contiguous())
+            logdets.append(float(torch.linalg.slogdet(W64)[1]))
+        f = self._pack(W, invs, torch.tensor(logdets, dtype=torch.float64).to(self.upsample.weight.device))
+        self._folded, self._folded_key = f, key
+        return f
+
+    def _pack(self, W: dict, invs, logdet: torch.Tensor) -> dict:
+        """folded weights by name (fp32, reference layouts) + W_k^-1 per flow + log|det W_k| [n_flows] float64 -> the
+        kernels' layouts"""
         n_mel, ng = self.n_mel_channels, self.n_group
+        L = self.WN[0].n_layers
         ldm = ops.round_up(n_mel, 4)
         f = {"ldm": ldm, "ldk": ops.round_up(n_mel * ng, 4)}
-        f["up"] = (pack_polyphase(self.upsample.weight.detach().float(), HOP, 0, 0, ldm).contiguous(),
-                   f32c(self.upsample.bias.detach()).repeat(HOP))
-        flows, logdets = [], []
-        for wn, inv in zip(self.WN, self.convinv):
-            c = inv.conv.weight.shape[0]
-            W64 = inv.conv.weight.detach()[:, :, 0].double().cpu()
-            Winv = torch.linalg.inv(W64).float().to(inv.conv.weight.device)
-            logdets.append(float(torch.linalg.slogdet(W64)[1]))
+        f["up"] = (pack_polyphase(W["upsample.weight"].float(), HOP, 0, 0, ldm).contiguous(),
+                   f32c(W["upsample.bias"]).repeat(HOP))
+        flows = []
+        for k in range(self.n_flows):
+            p = f"WN.{k}."
+            mix = W[f"convinv.{k}.conv.weight"]
+
+            def wb(n, gemm=False, ldk=None):
+                w = W[p + n + ".weight"]
+                return (self._gemm_weight(w, ldk) if gemm else f32c(w[:, :, 0]), f32c(W[p + n + ".bias"]))
             flows.append({
-                "c": c,
-                "start": (f32c(wn.start.weight.detach()[:, :, 0]), f32c(wn.start.bias.detach())),
-                "cond": (self._gemm_weight(wn.cond_layer.weight, f["ldk"]), f32c(wn.cond_layer.bias.detach())),
-                "in": [(self._gemm_weight(m.weight), f32c(m.bias.detach())) for m in wn.in_layers],
-                "rs": [(self._gemm_weight(m.weight), f32c(m.bias.detach())) for m in wn.res_skip_layers],
-                "end": (f32c(wn.end.weight.detach()[:, :, 0]), f32c(wn.end.bias.detach())),
-                "inv": Winv.contiguous(),
-                "mix": f32c(inv.conv.weight.detach()[:, :, 0]),
+                "c": mix.shape[0],
+                "start": wb("start"),
+                "cond": wb("cond_layer", True, f["ldk"]),
+                "in": [wb(f"in_layers.{i}", True) for i in range(L)],
+                "rs": [wb(f"res_skip_layers.{i}", True) for i in range(L)],
+                "end": wb("end"),
+                "inv": invs[k],
+                "mix": f32c(mix[:, :, 0]),
             })
         f["flows"] = flows
-        f["logdet"] = torch.tensor(logdets, dtype=torch.float64).to(self.upsample.weight.device)
-        self._folded, self._folded_key = f, key
+        f["logdet"] = logdet
         return f
 
     def _noise_arg(self, noise, B: int, Tg: int, dev) -> Optional[list]:
@@ -277,7 +402,7 @@ class WaveGlow(nn.Module):
             return e1.record
         return timed
 
-    def _conditioning(self, f, mel, lens_d, lens_g, timed) -> torch.Tensor:
+    def _conditioning(self, f, mel, lens_d, lens_g, timed, keep_xm: bool = False):
         """upsample: one polyphase row GEMM over the mel frames, [B*T, HOP*n_mel] = channels-last [B*T*HOP, n_mel],
         then grouped into the conditioning rows [R, ldk]"""
         B, n_mel, T = mel.shape
@@ -296,8 +421,10 @@ class WaveGlow(nn.Module):
         ci = torch.empty(B * Tg, ldk, device=dev, dtype=torch.float32)
         check(lib.radmmm_wg_group_cond(ptr(up), T * HOP * n_mel, ptr(ci), ldk, ptr(lens_g), B, Tg, n_mel, ng, s),
               "wg_group_cond")
-        del up, xm
         done()
+        if keep_xm:                     # the training step: the masked mel rows are the upsample's weight-gradient operand
+            return ci, xm
+        del up, xm
         return ci
 
     def _wn_buffers(self, R: int, dev):
@@ -312,11 +439,16 @@ class WaveGlow(nn.Module):
     def _wn(self, f, fk, X, col0: int, nh: int, ci, bufs, lens_g, R: int, Tg: int, timed) -> torch.Tensor:
         """the WN of one flow on the untouched half X[:, col0 : col0 + nh], the same launches in both directions: start,
         cond_layer for all layers, then per layer the dilated in_layer GEMM, the gate, the res_skip GEMM and the
-        residual / skip update.  Returns the skip sum S [R, C], the input of `end`."""
+        residual / skip update.  Returns the skip sum S [R, C], the input of `end`.  With bufs["layers"] (the training
+        step's recomputation) layer i's input H_i, in_layer output A_i and gated acts_i stay in buffers of their own:
+        one copy of H per layer more, the same values."""
         wn0 = self.WN[0]
         C, L, ksz = wn0.n_channels, wn0.n_layers, wn0.kernel_size
         ng, ldk = self.n_group, f["ldk"]
         cond, H, S, acts, A, rs = (bufs[n] for n in ("cond", "H", "S", "acts", "A", "rs"))
+        layers = bufs.get("layers")
+        if layers is not None:
+            H = layers[0]["H"]
         s = stream()
         Ws, bs = fk["start"]
         done = timed("start")
@@ -329,6 +461,8 @@ class WaveGlow(nn.Module):
                 K=self.n_mel_channels * ng, taps=1, T=Tg, lens=lens_g, bias=bc)
         done()
         for i in range(L):
+            if layers is not None:
+                A, acts = layers[i]["A"], layers[i]["acts"]
             Wi, bi = fk["in"][i]
             done = timed("in_layers")
             rowgemm(A=H, lda=C, B=Wi, ldb=C, b_tap_stride=Wi.stride(0), C=A, ldc=2 * C, M=R, N=2 * C, K=C, taps=ksz,
@@ -345,6 +479,8 @@ class WaveGlow(nn.Module):
                     taps=1, T=Tg, lens=lens_g, bias=br)
             done()
             done = timed("res_skip_update")
+            if layers is not None and not last:
+                H = layers[i + 1]["H"].copy_(H)
             check(lib.radmmm_wg_res_skip(ptr(rs), 2 * C, ptr(H), C, ptr(S), C, C, int(i == 0), int(last),
                                          ptr(lens_g), R, Tg, s), "wg_res_skip")
             done()
@@ -403,16 +539,18 @@ class WaveGlow(nn.Module):
             raise ValueError(f"audio must be [B, T * {HOP}] = {(B, T * HOP)}, got {tuple(audio.shape)}")
         return f32c(mel), f32c(audio)
 
-    def _analyze_run(self, mel, audio, lens_d, want_log_s: bool = False, events: Optional[dict] = None):
+    def _analyze_run(self, mel, audio, lens_d, want_log_s: bool = False, events: Optional[dict] = None, f=None,
+                     snaps=None, Bc=None):
         """mel [B, n_mel, T], audio [B, T*HOP] fp32 on the device, lens_d int32 [B] on the device (frames) ->
         (z rows [B*Tg, n_group], parts [B, 2] float64 = (sum z^2, sum log_s) per item, the per-flow log_s rows
-        [B*Tg, n_half_k] or None).  Chunked over items as _run; events as there."""
+        [B*Tg, n_half_k] or None).  Chunked over items as _run; events as there.  f: the packed weights (default: the
+        cached fold); snaps [n_flows, B*Tg, n_group]: receives the rows as they enter each flow (the training step)."""
         B, _, T = mel.shape
         dev = mel.device
         ng = self.n_group
         Tg = T * (HOP // ng)
-        f = self._fold()
-        Bc = self._chunk_items(f, Tg)
+        f = f or self._fold()
+        Bc = Bc or self._chunk_items(f, Tg)
         X = torch.empty(B * Tg, ng, device=dev, dtype=torch.float32)
         ls = torch.empty(B * Tg, device=dev, dtype=torch.float32)
         parts = torch.empty(B, 2, device=dev, dtype=torch.float64)
@@ -423,10 +561,11 @@ class WaveGlow(nn.Module):
             b1 = min(B, b0 + Bc)
             r0, r1 = b0 * Tg, b1 * Tg
             self._analyze_chunk(f, mel[b0:b1], audio[b0:b1], lens_d[b0:b1], X[r0:r1], ls[r0:r1], parts[b0:b1],
-                                None if logs is None else [t[r0:r1] for t in logs], events if b1 == B else None)
+                                None if logs is None else [t[r0:r1] for t in logs], events if b1 == B else None,
+                                None if snaps is None else snaps[:, r0:r1])
         return X, parts, logs
 
-    def _analyze_chunk(self, f, mel, audio, lens_d, X, ls, parts, logs, events) -> None:
+    def _analyze_chunk(self, f, mel, audio, lens_d, X, ls, parts, logs, events, snaps=None) -> None:
         B, _, T = mel.shape
         ng = self.n_group
         per = HOP // ng
@@ -448,6 +587,8 @@ class WaveGlow(nn.Module):
             fk = f["flows"][k]
             assert fk["c"] == c
             nh, col0 = c // 2, ng - c
+            if snaps is not None:
+                snaps[k].copy_(X)
             done = timed("mix_fwd")
             check(lib.radmmm_wg_mix_fwd(ptr(X), ng, col0, c, ptr(fk["mix"]), ptr(lens_g), R, Tg, s), "wg_mix_fwd")
             done()
@@ -462,6 +603,115 @@ class WaveGlow(nn.Module):
         done = timed("nll_parts")
         check(lib.radmmm_wg_nll_parts(ptr(X), ng, ng, ptr(ls), ptr(lens_g), B, Tg, ptr(parts), s), "wg_nll_parts")
         done()
+
+    def _backward_chunk(self, f, mel, lens_d, snaps, dX, g_ls, events) -> dict:
+        """the backward pass of _analyze_chunk for the items of one chunk.  snaps [n_flows, R, n_group]: the rows as they
+        entered each flow; dX [R, n_group]: the gradient of the final rows z on ALL columns (consumed: it becomes the
+        gradient of the grouped audio, which nobody asks for); g_ls[k]: the gradient of flow k's log_s, one value [1] or
+        rows [R, n_half_k].  Returns the gradients of the folded weights by name, reference layouts, WITHOUT the log-det
+        terms of the mixes.  Every gradient row at or past an item's length is kept at 0."""
+        B, n_mel, T = mel.shape
+        dev = mel.device
+        ng = self.n_group
+        per = HOP // ng
+        Tg, R = T * per, B * T * per
+        wn0 = self.WN[0]
+        C, L, ksz = wn0.n_channels, wn0.n_layers, wn0.kernel_size
+        ldk, cols = f["ldk"], n_mel * ng
+        lens_g = lens_d * per
+        s = stream()
+        timed = self._timer(events, R)
+        ci, xm = self._conditioning(f, mel, lens_d, lens_g, timed, keep_xm=True)
+
+        def empty(*shape):
+            return torch.empty(*shape, device=dev, dtype=torch.float32)
+        bufs = {"cond": empty(R, 2 * C * L), "S": empty(R, C), "rs": empty(R, 2 * C), "H": None, "A": None, "acts": None,
+                "layers": [{"H": empty(R, C), "A": empty(R, 2 * C), "acts": empty(R, C)} for _ in range(L)]}
+        dcond = empty(R, 2 * C * L)          # d cond; its column slice i is also d A_i, the GY of in_layer i
+        GHS = empty(R, 2 * C)                # [d H_{i+1} | d S]: the A operand of the res_skip data gradient
+        dacts, dO, Xp = empty(R, C), empty(R, ng), empty(R, ng)
+        dci, dci_prev = empty(R, ldk), None
+        out = {}
+        for k in reversed(range(self.n_flows)):
+            fk = f["flows"][k]
+            c = fk["c"]
+            nh, col0 = c // 2, ng - c
+            p = f"WN.{k}."
+            # recompute: the mixed rows and the WN on them, the launches (and bits) of the forward
+            done = timed("bwd_recompute")
+            Xp.copy_(snaps[k])
+            check(lib.radmmm_wg_mix_fwd(ptr(Xp), ng, col0, c, ptr(fk["mix"]), ptr(lens_g), R, Tg, s), "wg_mix_fwd")
+            S = self._wn(f, fk, Xp, col0, nh, ci, bufs, lens_g, R, Tg, lambda name: (lambda: None))
+            done()
+            We, be = fk["end"]
+            done = timed("bwd_coupling")
+            gl = g_ls[k]
+            check(lib.radmmm_wg_coupling_bwd(ptr(S), C, ptr(We), ptr(be), ptr(Xp), ng, ptr(dX), ng, col0, nh, C, ptr(gl),
+                                             0 if gl.dim() == 1 else nh, ptr(dO), ptr(GHS[:, C:]), 2 * C, ptr(lens_g), R,
+                                             Tg, s), "wg_coupling_bwd")
+            out[p + "end.weight"] = _outer_reduce(dO, 2 * nh, 2 * nh, S, C, C, lens_g, R, Tg)[:, :, None]
+            out[p + "end.bias"] = _outer_reduce(None, 0, 1, dO, 2 * nh, 2 * nh, lens_g, R, Tg)[0]
+            done()
+            for i in reversed(range(L)):
+                last = i == L - 1
+                lay = bufs["layers"][i]
+                Wi, _ = fk["in"][i]
+                Wr, _ = fk["rs"][i]
+                G, Mr = (GHS[:, C:], C) if last else (GHS, 2 * C)
+                done = timed("bwd_res_skip")
+                rowgemm(A=G, lda=2 * C, B=Wr, ldb=C, b_layout=1, C=dacts, ldc=C, M=R, N=C, K=Mr, T=Tg, lens=lens_g)
+                out[p + f"res_skip_layers.{i}.weight"] = _wgrad(G, 2 * C, Mr, lay["acts"], C, C, R, Tg)[0][:, :, None]
+                out[p + f"res_skip_layers.{i}.bias"] = _colsum(G, 2 * C, R, Mr)
+                done()
+                done = timed("bwd_gate")
+                dA = dcond[:, 2 * C * i:]
+                check(lib.radmmm_wg_gate_bwd(ptr(lay["A"]), 2 * C, ptr(bufs["cond"]), 2 * C * L, 2 * C * i, ptr(dacts), C,
+                                             ptr(dA), 2 * C * L, C, ptr(lens_g), R, Tg, s), "wg_gate_bwd")
+                done()
+                done = timed("bwd_in_layers")
+                out[p + f"in_layers.{i}.weight"] = _wgrad(dA, 2 * C * L, 2 * C, lay["H"], C, C, R, Tg, lens_g, ksz, 2 ** i,
+                                                         1).permute(1, 2, 0)
+                # d H_i = d H_{i+1} + the data gradient of the dilated conv (taps flipped: sign -1), in place in GHS
+                rowgemm(A=dA, lda=2 * C * L, B=Wi, ldb=C, b_tap_stride=Wi.stride(0), b_layout=1, C=GHS, ldc=2 * C, M=R,
+                        N=C, K=2 * C, taps=ksz, dil=2 ** i, sign=-1, T=Tg, lens=lens_g, a_mask_mode=0,
+                        add=None if last else GHS, ldadd=2 * C, postmask=1)
+                done()
+            done = timed("bwd_start")
+            Ws, _ = fk["start"]
+            out[p + "start.weight"] = _outer_reduce(Xp[:, col0:], ng, nh, GHS, 2 * C, C, lens_g, R, Tg).t()[:, :, None]
+            out[p + "start.bias"] = _outer_reduce(None, 0, 1, GHS, 2 * C, C, lens_g, R, Tg)[0]
+            check(lib.radmmm_wg_start_bwd(ptr(GHS), 2 * C, ptr(Ws.t().contiguous()), ptr(dX), ng, col0, nh, C, ptr(lens_g),
+                                          R, Tg, s), "wg_start_bwd")
+            done()
+            done = timed("bwd_cond_layer")
+            Wc, _ = fk["cond"]
+            bsum = _colsum(dcond, 2 * C * L, R, 2 * C * L)     # cond_layer's bias and, slice i, in_layer i's
+            out[p + "cond_layer.bias"] = bsum
+            for i in range(L):
+                out[p + f"in_layers.{i}.bias"] = bsum[2 * C * i:2 * C * (i + 1)]
+            out[p + "cond_layer.weight"] = _wgrad(dcond, 2 * C * L, 2 * C * L, ci, ldk, cols, R, Tg)[0][:, :, None]
+            rowgemm(A=dcond, lda=2 * C * L, B=Wc, ldb=ldk, b_layout=1, C=dci, ldc=ldk, M=R, N=cols, K=2 * C * L, T=Tg,
+                    lens=lens_g, add=dci_prev, ldadd=ldk)
+            dci, dci_prev = (dci_prev if dci_prev is not None else empty(R, ldk)), dci
+            done()
+            done = timed("bwd_mix")
+            out[f"convinv.{k}.conv.weight"] = _outer_reduce(dX[:, col0:], ng, c, snaps[k][:, col0:], ng, c, lens_g, R,
+                                                            Tg)[:, :, None]
+            check(lib.radmmm_wg_mix_fwd(ptr(dX), ng, col0, c, ptr(fk["mix"].t().contiguous()), ptr(lens_g), R, Tg, s),
+                  "wg_mix_fwd")
+            done()
+        # the conditioning: rows -> channels-last gradient of the upsampled mel -> the polyphase GEMM's weight gradient
+        done = timed("bwd_upsample")
+        dup = empty(B * T, HOP * n_mel)
+        check(lib.radmmm_wg_ungroup_cond(ptr(dci_prev), ldk, ptr(dup), T * HOP * n_mel, ptr(lens_g), B, Tg, n_mel, ng, s),
+              "wg_ungroup_cond")
+        taps = f["up"][0].shape[0]
+        P = _wgrad(dup, HOP * n_mel, HOP * n_mel, xm, f["ldm"], n_mel, B * T, T, lens_d, taps, 1, 1)
+        j = torch.arange(UPSAMPLE_KERNEL, device=dev)          # the inverse of pack_polyphase (padding 0, offset 0)
+        out["upsample.weight"] = P.view(taps, HOP, n_mel, n_mel)[taps // 2 - j // HOP, j % HOP].permute(2, 1, 0)
+        out["upsample.bias"] = _colsum(dup, HOP * n_mel, B * T, HOP * n_mel).view(HOP, n_mel).sum(0)
+        done()
+        return out
 
     @fp32_region
     def analyze(self, mel: torch.Tensor, audio: torch.Tensor, lens=None, sigma: float = 1.0) -> dict:
@@ -478,10 +728,41 @@ class WaveGlow(nn.Module):
         return {"z": X.view(B, Tg, ng).transpose(1, 2).contiguous(), "log_s_sum": log_s_sum, "log_det_W": logdet,
                 "n_groups": n_groups, "nll": num / (n_groups * ng), "loss": num.sum() / (n_groups.sum() * ng)}
 
+    # ---- training: the same forward under one autograd node whose backward is the HIP path -------------------------
+    def _train_active(self) -> bool:
+        return self.training and torch.is_grad_enabled()
+
+    @fp32_region
+    def nll_loss(self, mel: torch.Tensor, audio: torch.Tensor, lens=None, sigma: float = 1.0) -> torch.Tensor:
+        """analyze(...)["loss"] as a scalar; in training mode with grad enabled it carries a grad_fn, and backward()
+        fills .grad of every parameter (mel and audio get none).  With host lengths the step never waits for the
+        device."""
+        if not self._train_active():
+            return self.analyze(mel, audio, lens, sigma)["loss"]
+        mel, audio = self._args_fwd(mel, audio)
+        lens_d, _ = _lens_arg(lens, mel.shape[0], mel.shape[2], mel.device)
+        return _WaveGlowFn.apply(self, mel.detach(), audio.detach(), lens_d, float(sigma), True, *self._weights())
+
+    def _train_chunk(self, f, Tg: int) -> int:
+        """items per chunk of a training step: the caps of _chunk_items, the conditioning gradient [rows, 2 C L] as a GEMM
+        A operand, and _TRAIN_ACT_BYTES for what the backward of ONE flow holds per row (cond and its gradient, H_i / A_i /
+        acts_i of every layer, the skip / res_skip / gradient rows, the conditioning rows and their two gradient copies)"""
+        if self._train_chunk_items:
+            return int(self._train_chunk_items)
+        wn = self.WN[0]
+        C, L = wn.n_channels, wn.n_layers
+        per_row = 4 * (8 * C * L + 8 * C + 3 * f["ldk"] + 3 * self.n_group + 8)
+        rows_cap = min(_A_OPERAND_BYTES // (8 * C * L), _TRAIN_ACT_BYTES // per_row)
+        return max(1, min(self._chunk_items(f, Tg), rows_cap // Tg))
+
     @fp32_region
     def forward(self, forward_input):
         mel, audio = forward_input
         mel, audio = self._args_fwd(mel, audio)
+        if self._train_active():
+            lens_d, _ = _lens_arg(None, mel.shape[0], mel.shape[2], mel.device)
+            out = _WaveGlowFn.apply(self, mel.detach(), audio.detach(), lens_d, 1.0, False, *self._weights())
+            return out[0], list(out[1:-1]), list(out[-1].unbind(0))
         B, _, T = mel.shape
         ng = self.n_group
         Tg = T * (HOP // ng)
@@ -503,6 +784,120 @@ class WaveGlow(nn.Module):
             out.append(z[:, lo - self.n_early_size:lo])
             lo -= self.n_early_size
         return tuple(t.contiguous() for t in out)
+
+
+def _outer_reduce(A, lda, M, Bm, ldb, N, lens_g, R, Tg) -> torch.Tensor:
+    """out [M, N] = sum over the valid rows of A[r, :M]^T B[r, :N] (A None: column sums [1, N]); views into wider rows"""
+    M = M if A is not None else 1
+    out = torch.empty(M, N, device=Bm.device, dtype=torch.float32)
+    scratch = torch.empty(int(lib.radmmm_wg_outer_reduce_scratch_floats(R, M, N)), device=Bm.device, dtype=torch.float32)
+    check(lib.radmmm_wg_outer_reduce(ptr(A), lda, M, ptr(Bm), ldb, N, ptr(out), ptr(scratch), ptr(lens_g), R, Tg,
+                                     stream()), "wg_outer_reduce")
+    return out
+
+
+def _colsum(X, ld, R, cols) -> torch.Tensor:
+    out = torch.empty(cols, device=X.device, dtype=torch.float32)
+    scratch = torch.empty(int(lib.radmmm_colsum_scratch_floats(R, cols)), device=X.device, dtype=torch.float32)
+    check(lib.radmmm_colsum(ptr(X), ld, ptr(out), ptr(scratch), R, cols, 0, 1, None, 1, 1, 0, stream()), "colsum")
+    return out
+
+
+def _wgrad(GY, ldgy, Mc, X, ldx, Nc, R, T, lens=None, taps=1, dil=1, x_mask_mode=0) -> torch.Tensor:
+    """[taps, Mc, Nc] = sum_r GY[r, :Mc]^T Xm[r + (tap - taps // 2) * dil, :Nc]: split-K slabs added in slab order"""
+    S = ops.pick_splits(-(-Mc // 128) * -(-Nc // 128) * taps, R)
+    P = torch.empty(S, taps, Mc, Nc, device=X.device, dtype=torch.float32)
+    wgrad(GY=GY, ldgy=ldgy, X=X, ldx=ldx, P=P, ldp=Nc, split_stride=P.stride(0), R=R, Mc=Mc, Nc=Nc, taps=taps, dil=dil,
+          T=T, lens=lens, x_mask_mode=x_mask_mode, splits=S)
+    return P.sum(0) if S > 1 else P[0]
+
+
+def inv_logdet(mixes) -> Tuple[list, torch.Tensor]:
+    """[c_k, c_k] fp32 matrices on the device -> ([W_k^-1 fp32], log|det W_k| [n] float64) from one launch"""
+    dev = mixes[0].device
+    cs = [int(w.shape[0]) for w in mixes]
+    Wp = torch.cat([f32c(w).reshape(-1) for w in mixes])
+    Wi = torch.empty_like(Wp)
+    logdet = torch.empty(len(cs), device=dev, dtype=torch.float64)
+    check(lib.radmmm_wg_inv_logdet(ptr(Wp), (ctypes.c_int32 * len(cs))(*cs), len(cs), ptr(Wi), ptr(logdet), stream()),
+          "wg_inv_logdet")
+    offs = [0]
+    for c in cs:
+        offs.append(offs[-1] + c * c)
+    return [Wi[offs[k]:offs[k + 1]].view(cs[k], cs[k]) for k in range(len(cs))], logdet
+
+
+class _WaveGlowFn(torch.autograd.Function):
+    """WaveGlow.forward / nll_loss as one autograd node.  Inputs: the module, mel, audio, lens (device int32, frames),
+    sigma, fused, then the folded weights in WaveGlow._weight_names() order (reference layouts).  fused: the output is the
+    ragged loss of analyze(); else (z [B, n_group, Tg], log_s per flow [B, n_half_k, Tg], B * Tg * log|det W_k|
+    [n_flows] float64).  The forward keeps the rows as they enter each flow (32 bytes per row and flow); the backward
+    walks the flows from last to first, recomputes one flow's WN into per-layer buffers and back-propagates through it
+    (DESIGN 4.19)."""
+
+    @staticmethod
+    def forward(ctx, model, mel, audio, lens_d, sigma, fused, *weights):
+        B, _, T = mel.shape
+        ng = model.n_group
+        per = HOP // ng
+        Tg = T * per
+        dev = mel.device
+        W = dict(zip(model._weight_names(), weights))
+        invs, logdet = inv_logdet([W[f"convinv.{k}.conv.weight"][:, :, 0] for k in range(model.n_flows)])
+        f = model._pack(W, invs, logdet)
+        Bc = model._train_chunk(f, Tg)
+        snaps = torch.empty(model.n_flows, B * Tg, ng, device=dev, dtype=torch.float32)
+        X, parts, logs = model._analyze_run(mel, audio, lens_d, want_log_s=not fused, events=model._train_events, f=f,
+                                             snaps=snaps, Bc=Bc)
+        ctx.model, ctx.f, ctx.sigma, ctx.fused, ctx.Bc = model, f, sigma, fused, Bc
+        ctx.save_for_backward(mel, audio, lens_d, snaps, X)
+        if fused:
+            n_groups = lens_d.long() * per
+            num = parts[:, 0] / (2.0 * sigma ** 2) - parts[:, 1] - n_groups * logdet.sum()
+            return num.sum() / (n_groups.sum() * ng)
+        z = X.view(B, Tg, ng).transpose(1, 2).contiguous()
+        log_s = [t.view(B, Tg, -1).transpose(1, 2).contiguous() for t in logs]
+        return (z, *log_s, logdet * (B * Tg))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        model, f, sigma = ctx.model, ctx.f, ctx.sigma
+        mel, audio, lens_d, snaps, X = ctx.saved_tensors
+        B, _, T = mel.shape
+        ng = model.n_group
+        per = HOP // ng
+        Tg = T * per
+        dev = mel.device
+        nhs = [fk["c"] // 2 for fk in f["flows"]]
+        if ctx.fused:
+            # loss = (sum z^2 / (2 sigma^2) - sum log_s - sum_b n_b sum_k logdet_k) / N, N = sum_b n_b * n_group
+            g = grads[0].double()
+            N = (lens_d.long().sum() * (per * ng)).double()
+            dX = X * (g / (sigma ** 2 * N)).float()
+            g_ls = [(-g / N).float().reshape(1)] * model.n_flows
+            g_logdet = (-g / ng).float().expand(model.n_flows)
+        else:
+            gz, gl = grads[0], grads[1:-1]
+            dX = (torch.zeros_like(X) if gz is None
+                  else gz.float().transpose(1, 2).reshape(B * Tg, ng).contiguous().clone())
+            g_ls = [torch.zeros(B * Tg, nh, device=dev) if t is None
+                    else t.float().transpose(1, 2).reshape(B * Tg, nh).contiguous() for t, nh in zip(gl, nhs)]
+            g_logdet = (torch.zeros(model.n_flows, device=dev) if grads[-1] is None
+                        else (grads[-1].double() * (B * Tg)).float())
+        total = None
+        for b0 in range(0, B, ctx.Bc):                 # a fixed order: the chunks' gradients are added as they come
+            b1 = min(B, b0 + ctx.Bc)
+            r0, r1 = b0 * Tg, b1 * Tg
+            part = model._backward_chunk(f, mel[b0:b1], lens_d[b0:b1], snaps[:, r0:r1], dX[r0:r1],
+                                         [t if t.shape[0] == 1 else t[r0:r1] for t in g_ls],
+                                         model._train_events if b1 == B else None)
+            total = part if total is None else {n: total[n] + part[n] for n in total}
+        Wn = dict(zip(model._weight_names(), ctx.needs_input_grad[6:]))
+        for k in range(model.n_flows):                 # the log-det terms: d log|det W| / dW = W^-T
+            n = f"convinv.{k}.conv.weight"
+            total[n] = total[n] + (g_logdet[k] * f["flows"][k]["inv"].t())[:, :, None]
+        return (None,) * 6 + tuple(total[n] if need else None for n, need in Wn.items())
 
 
 class WaveGlowLoss(nn.Module):

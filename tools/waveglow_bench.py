@@ -2,6 +2,7 @@
 """Batched WaveGlow benchmark (rad_mmm_amd/waveglow.py, csrc/waveglow.hip): one JSON line.
 
     python tools/waveglow_bench.py [--batch 32] [--frames 800] [--iters 3] [--warmup 1] [--analyze]
+    python tools/waveglow_bench.py --train [--batch 32] [--frames 800] [--iters 3] [--warmup 1]
 
 The shipped config (12 flows, 8 layers, 256 channels, n_group 8, 80 mels), random weights from a seed, every item at
 full length: device milliseconds of WaveGlow.infer (device events around the whole call, median after warm-up), audio
@@ -9,7 +10,12 @@ seconds per second at 22050 Hz, the time of each launch family (events around ev
 chunk of items only), and the in_layers row GEMMs' fraction of the fp32-MFMA peak (157.3 TFLOPS on
 paper, MI355X).  --analyze adds the other direction in the same run and at the same shape: WaveGlow.analyze on seeded
 audio, timed the same way, under "analyze" in the same JSON line with the ratio analyze / infer and the time of the
-launch families only that direction has (group_audio, mix_fwd, end_coupling_fwd, nll_parts)."""
+launch families only that direction has (group_audio, mix_fwd, end_coupling_fwd, nll_parts).
+
+--train times one training step instead, WaveGlow.nll_loss + backward in training mode with weight norm applied, at the
+reference's training shape (batch 12, segments of 16000 samples = 62 frames) and at --batch / --frames: device
+milliseconds per step, the ratio to analyze at the same shape in the same run, and the step's launch families (the
+forward's, and bwd_* for the backward: bwd_recompute is the WN run again per flow; the last chunk of items only)."""
 import argparse
 import json
 import os
@@ -45,6 +51,52 @@ def seeded_state(model, seed):
     return sd
 
 
+def timed_ms(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return float(np.median(ts)), ts
+
+
+def train_bench(model, args, dev):
+    from rad_mmm_amd.waveglow import HOP
+    model.apply_weight_norm()
+    shapes = []
+    for B, T in ((12, 62), (args.batch, args.frames)):
+        mel = (torch.randn(B, 80, T, generator=torch.Generator().manual_seed(6)) - 2.0).to(dev)
+        audio = (0.3 * torch.randn(B, T * HOP, generator=torch.Generator().manual_seed(7))).to(dev)
+        lens = [T] * B
+
+        def step():
+            model.zero_grad(set_to_none=True)
+            with torch.enable_grad():
+                model.nll_loss(mel, audio, lens).backward()
+        model.eval()
+        ms_a, ta = timed_ms(lambda: model.analyze(mel, audio, lens), args.iters, args.warmup)
+        model.train()
+        ms, ts = timed_ms(step, args.iters, args.warmup)
+        model._train_events = events = {}
+        step()
+        torch.cuda.synchronize()
+        model._train_events = None
+        rows_chunk = events.pop("rows")
+        fam = {k: sum(a.elapsed_time(b) for a, b in v) for k, v in events.items()}
+        shapes.append({"batch": B, "frames": T, "rows": B * T * HOP // 8, "step_ms": ms, "all_ms": ts,
+                       "analyze_ms": ms_a, "analyze_all_ms": ta, "ratio_to_analyze": ms / ms_a,
+                       "last_chunk_rows": rows_chunk, "last_chunk_family_ms": fam,
+                       "peak_memory_gib": torch.cuda.max_memory_allocated() / 2 ** 30})
+        torch.cuda.reset_peak_memory_stats()
+    print(json.dumps({"metric": "waveglow_train_step_ms", "shapes": shapes}))
+
+
 @torch.no_grad()
 def main():
     ap = argparse.ArgumentParser()
@@ -54,6 +106,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--once", action="store_true", help="one untimed call only (for a kernel trace)")
     ap.add_argument("--analyze", action="store_true", help="also time WaveGlow.analyze (audio -> latent) at the same shape")
+    ap.add_argument("--train", action="store_true", help="time one training step (nll_loss + backward) instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("waveglow_bench needs an MI355X")
@@ -62,6 +115,8 @@ def main():
     model = WaveGlow(**SHIPPED)
     model.load_state_dict(seeded_state(model, 5))
     model = model.to(dev).eval()
+    if args.train:
+        return train_bench(model, args, dev)
     B, T = args.batch, args.frames
     mel = (torch.randn(B, 80, T, generator=torch.Generator().manual_seed(6)) - 2.0).to(dev)
     lens = [T] * B

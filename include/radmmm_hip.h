@@ -705,6 +705,25 @@ int radmmm_wg_end_coupling(const float* S, int lds, const float* Wend, const flo
 int radmmm_wg_ungroup(const float* X, int ldx, int col0, int n_group, float* audio, int64_t lda, const int32_t* lens,
                       int B, int Tg, radmmm_stream_t stream);
 
+/* The 16-bit GEMM modes of WaveGlow.infer ("h3": three f16 products, "f16": one): cond_layer, the in_layers and the
+ * res_skip layers run on radmmm_rowgemm_h3, and these three write that GEMM's A operand -- the RADMMM_SPLIT_F16 pair of
+ * the value with scale 1, [rows][ldp] halves, bit-identical to radmmm_split_f16 of the fp32 value -- in the pass that
+ * computes the value.  The fp32 outputs are bit-identical to the twin's.  Rows at or past an item's length and the padding
+ * columns C .. ldp are zeros in both halves; nothing is read in those rows.  C % 8 == 0, ldp % 8 == 0, ldp >= C, 16-byte
+ * aligned pair arrays; the lo array may be NULL (it is not written then: the one-product GEMM takes the hi array for both
+ * pointers).  Everything else as the twin.  Additive entry points of ABI 4.
+ *   wg_start_split     wg_start: H fp32 and its pair Hh / Hl
+ *   wg_gate_split      wg_gate: the pair yh / yl only (no fp32 copy of the gated activations exists in these modes)
+ *   wg_res_skip_split  wg_res_skip: H (updated in place) and S fp32, and the updated H's pair; with last != 0 only S is
+ *                      written (H, Hh, Hl may be NULL) */
+int radmmm_wg_start_split(const float* X, int ldx, int col0, int n_half, const float* W, const float* bias, float* H,
+                          int ldh, void* Hh, void* Hl, int ldp, int C, const int32_t* lens, int rows, int T,
+                          radmmm_stream_t stream);
+int radmmm_wg_gate_split(const float* a, int lda, const float* cond, int ldcond, int cond_off, void* yh, void* yl, int ldp,
+                         int C, const int32_t* lens, int rows, int T, radmmm_stream_t stream);
+int radmmm_wg_res_skip_split(const float* rs, int ldrs, float* H, int ldh, float* S, int lds, void* Hh, void* Hl, int ldp,
+                             int C, int first, int last, const int32_t* lens, int rows, int T, radmmm_stream_t stream);
+
 /* The other direction of the same flow (glow.py:207-249 WaveGlow.forward: audio -> latent z and the terms of its
  * likelihood), same conventions; the WN between the mix and the coupling is the launch sequence of the inverse
  * direction (wg_start reads the mixed values).  Additive entry points of ABI 4.

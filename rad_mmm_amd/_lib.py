@@ -218,6 +218,9 @@ def _load() -> C.CDLL:
         "radmmm_wg_start": [p, i, i, i, p, p, p, i, i, p, i, i, p],
         "radmmm_wg_gate": [p, i, p, i, i, p, i, i, p, i, i, p],
         "radmmm_wg_res_skip": [p, i, p, i, p, i, i, i, i, p, i, i, p],
+        "radmmm_wg_start_split": [p, i, i, i, p, p, p, i, p, p, i, i, p, i, i, p],
+        "radmmm_wg_gate_split": [p, i, p, i, i, p, p, i, i, p, i, i, p],
+        "radmmm_wg_res_skip_split": [p, i, p, i, p, i, p, p, i, i, i, i, p, i, i, p],
         "radmmm_wg_end_coupling": [p, i, p, p, p, p, i, i, i, i, p, i, i, p],
         "radmmm_wg_ungroup": [p, i, i, i, p, i64, p, i, i, p],
         "radmmm_wg_group_audio": [p, i64, p, i, i, p, i, i, p],

@@ -31,6 +31,8 @@ constexpr int TILE_H = BM * PITCH;              // halves per operand tile
 constexpr int SMEM_BYTES = 2 * 4 * TILE_H * 2;  // 80 KiB (>= 64 KiB needed by the epilogue stage)
 constexpr int OOB = 0x7fffffff;
 
+// ONE: nprod = 1, Ah.Bh only -- the lo tiles are neither loaded nor staged (Al / Bl are not read)
+template <bool ONE>
 __global__ __launch_bounds__(256, 2) void rowgemm_h3_kernel(const radmmm_rowgemm_h3_desc q, const int a_bytes,
                                                              const int b_bytes) {
   extern __shared__ __attribute__((aligned(16))) _Float16 smh[];
@@ -88,15 +90,15 @@ __global__ __launch_bounds__(256, 2) void rowgemm_h3_kernel(const radmmm_rowgemm
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       R.v[0][i] = __builtin_amdgcn_raw_buffer_load_b128(rAh, a_voff[i], so_a, 0);
-      R.v[1][i] = __builtin_amdgcn_raw_buffer_load_b128(rAl, a_voff[i], so_a, 0);
+      if (!ONE) R.v[1][i] = __builtin_amdgcn_raw_buffer_load_b128(rAl, a_voff[i], so_a, 0);
       R.v[2][i] = __builtin_amdgcn_raw_buffer_load_b128(rBh, b_voff[i], so_b, 0);
-      R.v[3][i] = __builtin_amdgcn_raw_buffer_load_b128(rBl, b_voff[i], so_b, 0);
+      if (!ONE) R.v[3][i] = __builtin_amdgcn_raw_buffer_load_b128(rBl, b_voff[i], so_b, 0);
     }
   };
   auto store_tiles = [&](int buf, const Regs& R) __attribute__((always_inline)) {
     _Float16* base = smh + buf * 4 * TILE_H;
 #pragma unroll
-    for (int o = 0; o < 4; ++o)
+    for (int o = 0; o < 4; o += ONE ? 2 : 1)
 #pragma unroll
       for (int i = 0; i < 2; ++i)
         *reinterpret_cast<u32x4*>(base + o * TILE_H + (s_row + 64 * i) * PITCH + s_chunk * 8) = R.v[o][i];
@@ -129,16 +131,18 @@ __global__ __launch_bounds__(256, 2) void rowgemm_h3_kernel(const radmmm_rowgemm
         const int ro = (wm * 64 + t * 32) * PITCH + kb * 16 + f_off;
         const int co = (wn * 64 + t * 32) * PITCH + kb * 16 + f_off;
         ah[t] = *reinterpret_cast<const f16x8*>(base + 0 * TILE_H + ro);
-        al[t] = *reinterpret_cast<const f16x8*>(base + 1 * TILE_H + ro);
+        if (!ONE) al[t] = *reinterpret_cast<const f16x8*>(base + 1 * TILE_H + ro);
         bh[t] = *reinterpret_cast<const f16x8*>(base + 2 * TILE_H + co);
-        bl[t] = *reinterpret_cast<const f16x8*>(base + 3 * TILE_H + co);
+        if (!ONE) bl[t] = *reinterpret_cast<const f16x8*>(base + 3 * TILE_H + co);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+          if (!ONE) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+          }
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
         }
     }
@@ -236,18 +240,25 @@ extern "C" int radmmm_rowgemm_h3(const radmmm_rowgemm_h3_desc* d, radmmm_stream_
   if (!takes_narrow_kernel(*d))
     return radmmm::launch_rowgemm_h3w(*d, static_cast<hipStream_t>(stream), (int)a_bytes, (int)b_bytes);
   static int once = [] {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rowgemm_h3_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    if (e != hipSuccess) {
-      radmmm::set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return -2;
+    for (const void* fn : {reinterpret_cast<const void*>(rowgemm_h3_kernel<false>),
+                           reinterpret_cast<const void*>(rowgemm_h3_kernel<true>)}) {
+      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+      if (e != hipSuccess) {
+        radmmm::set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
+        return -2;
+      }
     }
     return 0;
   }();
   if (once) return once;
   const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
-  hipLaunchKernelGGL(rowgemm_h3_kernel, dim3(ntm * ntn), dim3(256), SMEM_BYTES, static_cast<hipStream_t>(stream), *d,
-                     (int)a_bytes, (int)b_bytes);
+  // nprod 1 must not touch Al / Bl: a caller without lo halves passes the hi arrays for both pointers
+  if (d->nprod == 1)
+    hipLaunchKernelGGL(rowgemm_h3_kernel<true>, dim3(ntm * ntn), dim3(256), SMEM_BYTES, static_cast<hipStream_t>(stream),
+                       *d, (int)a_bytes, (int)b_bytes);
+  else
+    hipLaunchKernelGGL(rowgemm_h3_kernel<false>, dim3(ntm * ntn), dim3(256), SMEM_BYTES, static_cast<hipStream_t>(stream),
+                       *d, (int)a_bytes, (int)b_bytes);
   const int rc = radmmm::check_launch("rowgemm_h3");
   if (rc || !p.colsum_out) return rc;
   RADMMM_REQUIRE(p.C, "rowgemm_h3: colsum_out on this kernel sums C afterwards: C must not be NULL");

@@ -58,6 +58,23 @@ __device__ __forceinline__ float store_split4_fmt(void* hi_, void* lo_, OffT ele
   return amax;
 }
 
+// 8 consecutive columns (col % 8 == 0) of one row in the f16 pair format, one 16-byte store per array: the arithmetic of
+// store_split4_fmt with fmt 0 (the same bits), for producers that write a GEMM operand in the pass that computes it.
+// lo_ may be NULL (single-product mode: only the hi array is consumed).  ld in halves, ld % 8 == 0.
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void store_split8_f16(void* hi_, void* lo_, long long elem_off_row, int col, float s,
+                                                 const float (&x)[8]) {
+  f16x8_t hi, lo;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float t = clamp_f16(x[e] * s);
+    hi[e] = (_Float16)t;
+    lo[e] = (_Float16)(t - (float)hi[e]);
+  }
+  *reinterpret_cast<f16x8_t*>(static_cast<_Float16*>(hi_) + elem_off_row + col) = hi;
+  if (lo_) *reinterpret_cast<f16x8_t*>(static_cast<_Float16*>(lo_) + elem_off_row + col) = lo;
+}
+
 // one element (generic / tail paths)
 __device__ __forceinline__ float store_split1_fmt(void* hi_, void* lo_, long long elem_off_row, int col, int fmt, float x8_mul,
                                                   float s, float x, void* lo16_ = nullptr) {

@@ -12,6 +12,8 @@
 //   radmmm_wg_start         WN.start: n_half (<= 8) -> C channels, K far below a GEMM tile
 //   radmmm_wg_gate          tanh(a[:, :C] + cond[:, off:off+C]) * sigmoid(a[:, C:] + cond[:, off+C:off+2C])
 //   radmmm_wg_res_skip      audio += rs[:, :C]; skip (+)= rs[:, C:]   (last layer: skip += rs[:, :C] only)
+//   radmmm_wg_start_split / wg_gate_split / wg_res_skip_split   the three above for the 16-bit GEMM modes: they also
+//                           write the next GEMM's split f16 operand (hi, lo) in the same pass
 //   radmmm_wg_end_coupling  WN.end (C -> 2 n_half) + audio_1 = (audio_1 - b) * exp(-s) + the inverse 1x1 mix, in place
 //   radmmm_wg_ungroup       audio rows -> [B][Tg*n_group] samples, zeros past each length
 // and the other direction (glow.py:207-249 WaveGlow.forward: audio -> latent, with the terms of its likelihood), which
@@ -24,6 +26,7 @@
 // every output element is summed in an order that depends on its own row alone, so an item in a batch is bit-identical
 // to the item alone as far as these kernels go (wg_nll_parts: on the item's own rows alone, in a fixed order).
 #include "common.h"
+#include "split_pack.h"
 
 namespace {
 
@@ -166,6 +169,136 @@ __global__ __launch_bounds__(256) void res_skip_kernel(const float* __restrict__
     }
     if (!last) *hp = h;
     *sp = s;
+  }
+}
+
+// ---- the same three kernels for the 16-bit GEMM modes ("h3" / "f16" of WaveGlow.infer) --------------------------------
+// Each writes the split operand of the GEMM that follows (split_pack.h: hi = fp16(x), lo = fp16(x - hi), scale 1; the
+// bits of radmmm_split_f16 of the fp32 value) in the pass that computes the value, instead of a pass of its own over
+// [rows][C].  A thread owns 8 columns of a row: two float4 per fp32 array, one 16-byte store per half array.  The pair
+// arrays are [rows][ldp] halves; the padding columns C <= c < ldp and the rows at or past an item's length are written
+// as zeros in both halves, and nothing is read there (a select, as in the twins above).  Pl == NULL: the lo half is not
+// written (single-product mode).  The fp32 arithmetic is the twin's, operation for operation: the same bits.
+
+__device__ __forceinline__ void zero8(float (&v)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = 0.f;
+}
+
+__device__ __forceinline__ void store8(float* p, const float (&v)[8]) {
+  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+
+__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
+  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
+// start_kernel + the pair of H
+__global__ __launch_bounds__(256) void start_split_kernel(const float* __restrict__ X, int ldx, int col0, int nh,
+                                                          const float* __restrict__ W, const float* __restrict__ bias,
+                                                          float* __restrict__ H, int ldh, void* __restrict__ Ph,
+                                                          void* __restrict__ Pl, int ldp, int C,
+                                                          const int32_t* __restrict__ lens, long long rows, int T) {
+  const int q = ldp >> 3;
+  const long long total = rows * q;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / q;
+    const int c = (int)(i - r * q) * 8;
+    float o[8];
+    zero8(o);
+    if (c < C) {
+      const int b = (int)(r / T), t = (int)(r - (long long)b * T);
+      if (!lens || t < lens[b]) {
+        const float* xr = X + r * ldx + col0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float acc = bias ? bias[c + e] : 0.f;
+          const float* w = W + (long long)(c + e) * nh;
+          for (int k = 0; k < nh; ++k) acc = fmaf(w[k], xr[k], acc);
+          o[e] = acc;
+        }
+      }
+      store8(H + r * ldh + c, o);
+    }
+    radmmm::store_split8_f16(Ph, Pl, r * ldp, c, 1.f, o);
+  }
+}
+
+// gate_kernel, its result as a pair only
+__global__ __launch_bounds__(256) void gate_split_kernel(const float* __restrict__ a, int lda,
+                                                         const float* __restrict__ cond, int ldcond, int off,
+                                                         void* __restrict__ Ph, void* __restrict__ Pl, int ldp, int C,
+                                                         const int32_t* __restrict__ lens, long long rows, int T) {
+  const int q = ldp >> 3;
+  const long long total = rows * q;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / q;
+    const int c = (int)(i - r * q) * 8;
+    float o[8];
+    zero8(o);
+    if (c < C) {
+      const int b = (int)(r / T), t = (int)(r - (long long)b * T);
+      if (!lens || t < lens[b]) {
+        float ta[8], sa[8], tc[8], sc[8];
+        const float* ar = a + r * lda + c;
+        const float* cr = cond + r * ldcond + off + c;
+        load8(ar, ta);
+        load8(ar + C, sa);
+        load8(cr, tc);
+        load8(cr + C, sc);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = gate1(ta[e], tc[e], sa[e], sc[e]);
+      }
+    }
+    radmmm::store_split8_f16(Ph, Pl, r * ldp, c, 1.f, o);
+  }
+}
+
+// res_skip_kernel + the pair of the updated H (not last; with last nothing but S is written)
+__global__ __launch_bounds__(256) void res_skip_split_kernel(const float* __restrict__ rs, int ldrs,
+                                                             float* __restrict__ H, int ldh, float* __restrict__ S,
+                                                             int lds, void* __restrict__ Ph, void* __restrict__ Pl,
+                                                             int ldp, int C, int first, int last,
+                                                             const int32_t* __restrict__ lens, long long rows, int T) {
+  const int q = (last ? C : ldp) >> 3;
+  const long long total = rows * q;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / q;
+    const int c = (int)(i - r * q) * 8;
+    float h[8], s[8];
+    zero8(h);
+    zero8(s);
+    if (c < C) {
+      const int b = (int)(r / T), t = (int)(r - (long long)b * T);
+      float* sp = S + r * lds + c;
+      if (!lens || t < lens[b]) {
+        const float* rr = rs + r * ldrs + c;
+        float x[8];
+        if (!first) load8(sp, s);
+        if (last) {
+          load8(rr, x);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) s[e] = s[e] + x[e];
+        } else {
+          load8(H + r * ldh + c, h);
+          load8(rr, x);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) h[e] = h[e] + x[e];
+          load8(rr + C, x);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) s[e] = s[e] + x[e];
+        }
+      }
+      if (!last) store8(H + r * ldh + c, h);
+      store8(sp, s);
+    }
+    if (!last) radmmm::store_split8_f16(Ph, Pl, r * ldp, c, 1.f, h);
   }
 }
 
@@ -489,6 +622,54 @@ extern "C" int radmmm_wg_res_skip(const float* rs, int ldrs, float* H, int ldh, 
   hipLaunchKernelGGL(res_skip_kernel, dim3(grid_for((long long)rows * (C / 4), 256)), dim3(256), 0, ST(stream), rs, ldrs,
                      H, ldh, S, lds, C, first, last, lens, (long long)rows, T);
   return radmmm::check_launch("wg_res_skip");
+}
+
+extern "C" int radmmm_wg_start_split(const float* X, int ldx, int col0, int n_half, const float* W, const float* bias,
+                                     float* H, int ldh, void* Hh, void* Hl, int ldp, int C, const int32_t* lens,
+                                     int rows, int T, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(X && W && H && Hh, "wg_start_split: null pointer");
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && C > 0 && C % 8 == 0 && ldh % 4 == 0 && ldh >= C && ldp % 8 == 0 &&
+                     ldp >= C && n_half >= 1 && n_half <= START_MAX_NH && col0 >= 0 && col0 + n_half <= ldx,
+                 "wg_start_split: bad dims (rows=%d T=%d C=%d ldh=%d ldp=%d n_half=%d col0=%d ldx=%d; C, ldp %% 8 == 0)",
+                 rows, T, C, ldh, ldp, n_half, col0, ldx);
+  RADMMM_REQUIRE(radmmm::aligned16(H) && radmmm::aligned16(Hh) && radmmm::aligned16(Hl),
+                 "wg_start_split: H / Hh / Hl must be 16B aligned");
+  hipLaunchKernelGGL(start_split_kernel, dim3(grid_for((long long)rows * (ldp / 8), 256)), dim3(256), 0, ST(stream), X,
+                     ldx, col0, n_half, W, bias, H, ldh, Hh, Hl, ldp, C, lens, (long long)rows, T);
+  return radmmm::check_launch("wg_start_split");
+}
+
+extern "C" int radmmm_wg_gate_split(const float* a, int lda, const float* cond, int ldcond, int cond_off, void* yh,
+                                    void* yl, int ldp, int C, const int32_t* lens, int rows, int T,
+                                    radmmm_stream_t stream) {
+  RADMMM_REQUIRE(a && cond && yh, "wg_gate_split: null pointer");
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && C > 0 && C % 8 == 0 && lda % 4 == 0 && lda >= 2 * C &&
+                     ldcond % 4 == 0 && cond_off >= 0 && cond_off % 4 == 0 && cond_off + 2 * C <= ldcond &&
+                     ldp % 8 == 0 && ldp >= C,
+                 "wg_gate_split: bad dims (rows=%d T=%d C=%d lda=%d ldcond=%d cond_off=%d ldp=%d; C, ldp %% 8 == 0)", rows,
+                 T, C, lda, ldcond, cond_off, ldp);
+  RADMMM_REQUIRE(radmmm::aligned16(a) && radmmm::aligned16(cond) && radmmm::aligned16(yh) && radmmm::aligned16(yl),
+                 "wg_gate_split: a / cond / yh / yl must be 16B aligned");
+  hipLaunchKernelGGL(gate_split_kernel, dim3(grid_for((long long)rows * (ldp / 8), 256)), dim3(256), 0, ST(stream), a,
+                     lda, cond, ldcond, cond_off, yh, yl, ldp, C, lens, (long long)rows, T);
+  return radmmm::check_launch("wg_gate_split");
+}
+
+extern "C" int radmmm_wg_res_skip_split(const float* rs, int ldrs, float* H, int ldh, float* S, int lds, void* Hh,
+                                        void* Hl, int ldp, int C, int first, int last, const int32_t* lens, int rows,
+                                        int T, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(rs && S && (last || (H && Hh)), "wg_res_skip_split: null pointer");
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && C > 0 && C % 8 == 0 && ldrs % 4 == 0 &&
+                     ldrs >= (last ? C : 2 * C) && lds % 4 == 0 && lds >= C &&
+                     (last || (ldh % 4 == 0 && ldh >= C && ldp % 8 == 0 && ldp >= C)),
+                 "wg_res_skip_split: bad dims (rows=%d T=%d C=%d ldrs=%d ldh=%d lds=%d ldp=%d last=%d; C, ldp %% 8 == 0)",
+                 rows, T, C, ldrs, ldh, lds, ldp, last);
+  RADMMM_REQUIRE(radmmm::aligned16(rs) && radmmm::aligned16(S) &&
+                     (last || (radmmm::aligned16(H) && radmmm::aligned16(Hh) && radmmm::aligned16(Hl))),
+                 "wg_res_skip_split: rs / H / S / Hh / Hl must be 16B aligned");
+  hipLaunchKernelGGL(res_skip_split_kernel, dim3(grid_for((long long)rows * ((last ? C : ldp) / 8), 256)), dim3(256), 0,
+                     ST(stream), rs, ldrs, H, ldh, S, lds, Hh, Hl, ldp, C, first, last, lens, (long long)rows, T);
+  return radmmm::check_launch("wg_res_skip_split");
 }
 
 extern "C" int radmmm_wg_end_coupling(const float* S, int lds, const float* Wend, const float* bend, const float* Winv,

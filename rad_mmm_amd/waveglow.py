@@ -18,6 +18,11 @@ layers, the 3-tap in_layers with dilation 2^i, the 1x1 res_skip layers.  Everyth
 start, the gate on a conditioning slice, the residual / skip update, end + inverse coupling + inverse 1x1 mix, the
 noise columns, un-grouping) is a kernel of csrc/waveglow.hip.
 
+That is precision "fp32", the default.  With WaveGlow.precision "h3" or "f16" infer runs cond_layer, the in_layers and the
+res_skip layers on radmmm_rowgemm_h3 instead (fp16 operands, fp32 accumulation; three split products or one), and
+wg_start_split / wg_gate_split / wg_res_skip_split write those GEMMs' fp16 operands in the pass that computes the value
+(WaveGlow._wn_split); everything else, and every other entry point of this module, stays as described here.
+
 The other direction, audio -> latent (glow.py:207-249 WaveGlow.forward, :43-59 WaveGlowLoss), runs the same WN launches
 on the untouched half: the audio enters the rows with all n_group columns live (wg_group_audio), each flow is the forward
 1x1 mix (wg_mix_fwd), the WN, and the forward coupling with the row's sum of log_s (wg_end_coupling_fwd); an early
@@ -41,7 +46,7 @@ import torch
 from torch import nn
 
 from . import ops
-from ._lib import RadmmmError, check, f32c, fp32_region, lib, ptr, rowgemm, stream, wgrad
+from ._lib import RadmmmError, check, f32c, fp32_region, lib, ptr, rowgemm, rowgemm_h3, stream, wgrad
 from .vocoder import Denoiser, _lens_arg, _to_device, fold_weight_norm, pack_polyphase
 
 UPSAMPLE_KERNEL = 1024     # glow.py:183-186: hard-coded in the reference
@@ -49,6 +54,7 @@ HOP = 256
 _A_OPERAND_BYTES = 2 ** 31 - 2 ** 16     # the row GEMM's 16-row fast path needs A operands below 2 GiB
 _COND_BYTES = 8 << 30                    # cap of the per-flow conditioning buffer [rows, 2 * n_channels * n_layers]
 _TRAIN_ACT_BYTES = 8 << 30               # cap of what the backward of one flow holds (see WaveGlow._train_chunk)
+PRECISIONS = ("fp32", "h3", "f16")       # WaveGlow.precision: how infer runs the three WN GEMM families
 
 
 class _WN(nn.Module):
@@ -131,7 +137,7 @@ class WaveGlow(nn.Module):
     WN.{k}.start / in_layers.{i} / cond_layer / res_skip_layers.{i} / end .weight / .bias, convinv.{k}.conv.weight);
     load_state_dict also takes the weight-normed keys (.weight_g / .weight_v) and folds them.
 
-    infer(mel [B, n_mel, T], lens=None, sigma=1.0, noise=None) -> audio [B, T * 256], exactly 0 at and past
+    infer(mel [B, n_mel, T], lens=None, sigma=1.0, noise=None, precision=None) -> audio [B, T * 256], exactly 0 at and past
     lens[b] * 256.  lens: lengths in mel frames, a host list / CPU tensor (no device -> host synchronisation) or a
     device int32 tensor.
 
@@ -143,6 +149,17 @@ class WaveGlow(nn.Module):
                                                     == 0), so noise[1] belongs to the largest such k
     Column g of every draw belongs to samples g*n_group .. g*n_group + n_group - 1; columns at or past an item's length
     are ignored.  Item b alone at T = lens[b] with noise[:][b:b+1, :, :lens[b] * 256 / n_group] gives the same audio.
+
+    precision ("fp32", the default, "h3" or "f16"; the attribute `precision`, or per call infer(..., precision=)): how
+    the mel -> audio direction runs the three WN GEMM families cond_layer, in_layers and res_skip_layers.  "fp32": the
+    exact fp32 MFMA.  The other two run them on the f16 matrix cores (radmmm_rowgemm_h3, fp32 accumulation) with every
+    operand element x of these GEMMs stored as fp16 values of s * x, s a power of two per tensor class (ops.W_SCALE for
+    weights, 1 for activations): "f16" takes hi = fp16(s x) alone, half-precision vocoding as the reference's
+    inference.py --is_fp16 offers it; "h3" takes the pair hi, lo = fp16(s x - hi) and sums hi.hi + hi.lo + lo.hi, which
+    keeps fp32-class accuracy.  Everything else stays fp32 in every mode: the upsample, start, the gate, the residual
+    stream H (an fp32 master copy; only its GEMM-operand copy is 16-bit), the skip sum, end, the coupling, the inverse
+    mix and the flow variable.  Both need n_channels % 32 == 0 and (n_mel_channels * n_group) % 32 == 0, the GEMM's
+    K % 32.  analyze, nll_loss, forward and training ignore the mode.
 
     analyze(mel [B, n_mel, T], audio [B, T * 256], lens=None, sigma=1.0) -> dict, everything on the device:
         z          [B, n_group, Tg] fp32   the reference's layout (early outputs first), exactly 0 past each length
@@ -192,6 +209,7 @@ class WaveGlow(nn.Module):
             self.convinv.append(_Invertible1x1Conv(n_rem))
             self.WN.append(_WN(n_half, n_mel_channels * n_group, **WN_config))
         self.n_remaining_channels = n_rem
+        self.precision = "fp32"
         self._folded = None
         self._folded_key = None
         self._weight_normed = False
@@ -349,16 +367,29 @@ class WaveGlow(nn.Module):
             out.append(f32c(z.to(dev)))
         return out
 
+    def _precision(self, precision: Optional[str] = None) -> str:
+        """the mode of a call (None: the attribute), checked: a known name, and for the 16-bit modes the GEMM's K % 32"""
+        mode = self.precision if precision is None else precision
+        if mode not in PRECISIONS:
+            raise ValueError(f"precision {mode!r}: one of {PRECISIONS}")
+        if mode != "fp32":
+            C, K = self.WN[0].n_channels, self.n_mel_channels * self.n_group
+            if C % 32 or K % 32:
+                raise ValueError(f"precision {mode!r} needs n_channels % 32 == 0 and (n_mel_channels * n_group) % 32 == 0 "
+                                 f"(the f16 GEMM's K % 32 == 0); got n_channels {C}, n_mel_channels * n_group {K}")
+        return mode
+
     @fp32_region
-    def infer(self, mel: torch.Tensor, lens=None, sigma: float = 1.0, noise: Optional[Sequence[torch.Tensor]] = None
-              ) -> torch.Tensor:
+    def infer(self, mel: torch.Tensor, lens=None, sigma: float = 1.0, noise: Optional[Sequence[torch.Tensor]] = None,
+              precision: Optional[str] = None) -> torch.Tensor:
+        mode = self._precision(precision)
         if not mel.is_cuda:
             raise RadmmmError("WaveGlow needs a GPU tensor (there is no CPU path)")
         if mel.dim() != 3 or mel.shape[1] != self.n_mel_channels:
             raise ValueError(f"mel must be [B, {self.n_mel_channels}, T], got {tuple(mel.shape)}")
         B, _, T = mel.shape
         lens_d, _ = _lens_arg(lens, B, T, mel.device)
-        return self._run(f32c(mel), lens_d, float(sigma), noise)
+        return self._run(f32c(mel), lens_d, float(sigma), noise, precision=mode)
 
     def _chunk_items(self, f, Tg: int) -> int:
         """items per chunk: every GEMM A operand stays below 2 GiB and the conditioning buffer below its cap (items
@@ -369,11 +400,12 @@ class WaveGlow(nn.Module):
         return max(1, rows_cap // Tg)
 
     def _run(self, mel: torch.Tensor, lens_d: torch.Tensor, sigma: float, noise=None,
-             events: Optional[dict] = None) -> torch.Tensor:
+             events: Optional[dict] = None, precision: Optional[str] = None) -> torch.Tensor:
         """mel [B, n_mel, T] fp32 on the device, lens_d int32 [B] on the device (frames).  Items are processed in chunks
         that keep every GEMM operand below 2 GiB (items are independent, so the chunking changes no value).
         events: a dict that receives (start, end) device events per launch family of the LAST chunk, and its row count
-        under "rows" (timing)."""
+        under "rows" (timing).  precision: as infer."""
+        mode = self._precision(precision)
         B, _, T = mel.shape
         dev = mel.device
         per = HOP // self.n_group
@@ -385,7 +417,7 @@ class WaveGlow(nn.Module):
         for b0 in range(0, B, Bc):
             b1 = min(B, b0 + Bc)
             self._run_chunk(f, mel[b0:b1], lens_d[b0:b1], sigma, None if noise is None else [z[b0:b1] for z in noise],
-                            audio[b0:b1], events if b1 == B else None)
+                            audio[b0:b1], events if b1 == B else None, mode)
         return audio
 
     @staticmethod
@@ -486,7 +518,96 @@ class WaveGlow(nn.Module):
             done()
         return S
 
-    def _run_chunk(self, f, mel, lens_d, sigma, noise, audio, events) -> None:
+    # ---- the 16-bit GEMM modes of infer ("h3" / "f16") -----------------------------------------------------------------
+    @staticmethod
+    def _split_weights(f, mode: str) -> list:
+        """per flow the fp16 operands of the three GEMM families: the packed fp32 weights [taps, Cout, K] times
+        ops.W_SCALE as the pair (hi, lo) for "h3", hi alone (lo None) for "f16".  Split once per fold and mode and kept
+        inside the fold `f`, so they are dropped with it."""
+        cache = f.setdefault("split", {})
+        if mode not in cache:
+            def sp(W):
+                taps, Cout, K = W.shape
+                hi, lo = ops.split_f16(W.view(taps * Cout, K), K, ops.W_SCALE, K, ops.NPROD[mode])
+                return hi.view(taps, Cout, K), (lo.view(taps, Cout, K) if mode == "h3" else None)
+            cache[mode] = [{"cond": sp(fk["cond"][0]), "in": [sp(W) for W, _ in fk["in"]],
+                            "rs": [sp(W) for W, _ in fk["rs"]]} for fk in f["flows"]]
+        return cache[mode]
+
+    def _wn_split_buffers(self, R: int, dev, mode: str):
+        wn0 = self.WN[0]
+        C, L = wn0.n_channels, wn0.n_layers
+
+        def empty(*shape, dtype=torch.float32):
+            return torch.empty(*shape, device=dev, dtype=dtype)
+
+        def half():
+            return empty(R, C, dtype=torch.float16)
+        lo = mode == "h3"
+        return {"cond": empty(R, 2 * C * L), "H": empty(R, C), "S": empty(R, C), "A": empty(R, 2 * C),
+                "rs": empty(R, 2 * C), "Hh": half(), "Hl": half() if lo else None, "acts_h": half(),
+                "acts_l": half() if lo else None}
+
+    def _wn_split(self, f, fk, sw, X, col0: int, nh: int, cih, cil, bufs, lens_g, R: int, Tg: int, timed,
+                  mode: str) -> torch.Tensor:
+        """_wn for infer's 16-bit modes: the three GEMM families on radmmm_rowgemm_h3 (nprod 3 for "h3", 1 for "f16"),
+        their A operands written as split fp16 copies by the kernels that produce the values (wg_start_split,
+        wg_gate_split, wg_res_skip_split; cih / cil: the split conditioning rows).  The GEMMs' outputs, H, S and
+        everything outside this function stay fp32.  With "f16" no lo half exists: the GEMM gets the hi array for both
+        pointers and reads only that."""
+        wn0 = self.WN[0]
+        C, L, ksz = wn0.n_channels, wn0.n_layers, wn0.kernel_size
+        ng, ldk = self.n_group, f["ldk"]
+        cond, H, S, A, rs = (bufs[n] for n in ("cond", "H", "S", "A", "rs"))
+        Hh, Hl, ah, al = (bufs[n] for n in ("Hh", "Hl", "acts_h", "acts_l"))
+        npr = ops.NPROD[mode]
+        inv_ws = 1.0 / ops.W_SCALE
+
+        def gemm(Ah, Al, lda, W, **kw):
+            Wh, Wl = W
+            rowgemm_h3(Ah=Ah, Al=Al if Al is not None else Ah, lda_h=lda, Bh=Wh, Bl=Wl if Wl is not None else Wh,
+                       ldb_h=Wh.shape[2], b_tap_stride_h=Wh.stride(0), acc_scale=inv_ws, nprod=npr, M=R, T=Tg,
+                       lens=lens_g, **kw)
+        s = stream()
+        Ws, bs = fk["start"]
+        done = timed("start")
+        check(lib.radmmm_wg_start_split(ptr(X), ng, col0, nh, ptr(Ws), ptr(bs), ptr(H), C, ptr(Hh), ptr(Hl), C, C,
+                                        ptr(lens_g), R, Tg, s), "wg_start_split")
+        done()
+        done = timed("cond_layer")
+        # In row slices whose output [rows][2 C L] stays below 2 GiB: the GEMM's direct epilogue addresses its arrays with
+        # 32-bit byte offsets and a larger launch falls back to the general one (measured at 307 200 rows x 4096 columns,
+        # one-product mode: 11.7 ms per launch against 2.8 ms for its three slices, DESIGN 4.19).  A 1x1 conv without a
+        # mask: no row needs another row or its item's length, so any row boundary will do.
+        step = max(128, ((2 ** 31 - 1) // (8 * C * L) - 64) // 128 * 128)
+        Wch, Wcl = sw["cond"]
+        for r0 in range(0, R, step):
+            r1 = min(R, r0 + step)
+            rowgemm_h3(Ah=cih[r0:r1], Al=(cil if cil is not None else cih)[r0:r1], lda_h=ldk, Bh=Wch,
+                       Bl=Wcl if Wcl is not None else Wch, ldb_h=ldk, acc_scale=inv_ws, nprod=npr, C=cond[r0:r1],
+                       ldc=2 * C * L, M=r1 - r0, N=2 * C * L, K=self.n_mel_channels * ng, taps=1, T=r1 - r0,
+                       bias=fk["cond"][1])
+        done()
+        for i in range(L):
+            done = timed("in_layers")
+            gemm(Hh, Hl, C, sw["in"][i], C=A, ldc=2 * C, N=2 * C, K=C, taps=ksz, dil=2 ** i, a_mask_mode=1,
+                 bias=fk["in"][i][1])
+            done()
+            done = timed("gate")
+            check(lib.radmmm_wg_gate_split(ptr(A), 2 * C, ptr(cond), 2 * C * L, 2 * C * i, ptr(ah), ptr(al), C, C,
+                                           ptr(lens_g), R, Tg, s), "wg_gate_split")
+            done()
+            last = i == L - 1
+            done = timed("res_skip_gemm")
+            gemm(ah, al, C, sw["rs"][i], C=rs, ldc=2 * C, N=C if last else 2 * C, K=C, taps=1, bias=fk["rs"][i][1])
+            done()
+            done = timed("res_skip_update")
+            check(lib.radmmm_wg_res_skip_split(ptr(rs), 2 * C, ptr(H), C, ptr(S), C, ptr(Hh), ptr(Hl), C, C, int(i == 0),
+                                               int(last), ptr(lens_g), R, Tg, s), "wg_res_skip_split")
+            done()
+        return S
+
+    def _run_chunk(self, f, mel, lens_d, sigma, noise, audio, events, mode: str = "fp32") -> None:
         B, n_mel, T = mel.shape
         dev = mel.device
         ng = self.n_group
@@ -509,12 +630,25 @@ class WaveGlow(nn.Module):
             check(lib.radmmm_wg_noise_rows(ptr(z), sigma, ptr(X), ng, col0, ch, ptr(lens_g), B, Tg, s), "wg_noise_rows")
 
         attach(c, ng - c)
-        bufs = self._wn_buffers(R, dev)
+        if mode == "fp32":
+            bufs = self._wn_buffers(R, dev)
+        else:
+            sw = self._split_weights(f, mode)
+            bufs = self._wn_split_buffers(R, dev, mode)
+            done = timed("split_cond")      # the conditioning rows feed every flow's cond_layer GEMM: one split pass
+            cih, cil = ops.split_f16(ci, f["ldk"], 1.0, f["ldk"], ops.NPROD[mode])
+            done()
+            del ci
+            if mode == "f16":
+                cil = None
         for k in reversed(range(self.n_flows)):
             fk = f["flows"][k]
             assert fk["c"] == c
             nh, col0 = c // 2, ng - c
-            S = self._wn(f, fk, X, col0, nh, ci, bufs, lens_g, R, Tg, timed)
+            if mode == "fp32":
+                S = self._wn(f, fk, X, col0, nh, ci, bufs, lens_g, R, Tg, timed)
+            else:
+                S = self._wn_split(f, fk, sw[k], X, col0, nh, cih, cil, bufs, lens_g, R, Tg, timed, mode)
             We, be = fk["end"]
             done = timed("end_coupling")
             check(lib.radmmm_wg_end_coupling(ptr(S), C, ptr(We), ptr(be), ptr(fk["inv"]), ptr(X), ng, col0, nh, C,
@@ -924,6 +1058,9 @@ class WaveGlowDenoiser(Denoiser):
     audio_processing.py the HiFi-GAN denoiser uses are the same transform (reflect pad, window-sum-square division,
     filter_length / 2 trimmed at both ends), so everything but the bias is vocoder.Denoiser's.
 
+    The bias spectrum is always computed on the fp32 path, whatever waveglow.precision says (88 frames, once per model):
+    one denoiser serves a model in every mode.
+
     forward(audio [B, S], strength=0.1, lens=None) -> [B, 1, (S // hop) * hop]; lens in samples."""
 
     def __init__(self, waveglow: WaveGlow, filter_length=1024, n_overlap=4, win_length=1024, mode="zeros"):
@@ -932,7 +1069,7 @@ class WaveGlowDenoiser(Denoiser):
     def _bias(self, dev):
         if self.bias_spec is None or self.bias_spec.device != dev:
             wg = self.generator
-            audio = wg.infer(torch.zeros(1, wg.n_mel_channels, 88, device=dev), sigma=0.0)
+            audio = wg.infer(torch.zeros(1, wg.n_mel_channels, 88, device=dev), sigma=0.0, precision="fp32")
             spec = self._spectrum(audio, None, torch.ones(1, dtype=torch.int32, device=dev), 1)
             mag = torch.empty(self.cutoff, device=dev, dtype=torch.float32)
             check(lib.radmmm_voc_spec_bins(ptr(spec), self.ldk, 1, self.cutoff, None, 0.0, ptr(mag), stream()),
@@ -943,18 +1080,19 @@ class WaveGlowDenoiser(Denoiser):
 
 @fp32_region
 def vocode_waveglow(model: WaveGlow, denoiser: Optional[WaveGlowDenoiser], mels: torch.Tensor, out_lens,
-                    sigma: float = 0.667, strength: float = 0.001, normalize: bool = True
-                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+                    sigma: float = 0.667, strength: float = 0.001, normalize: bool = True,
+                    precision: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """mels [B, n_mel, T] + lengths in frames -> (audio [B, T*256] zero padded, sample lengths [B] int64 on the host
     when out_lens was on the host, else on the device).  The waveglow branch of get_audio_for_mels
     (vocoder_utils.py:49-58) for a whole batch: infer at `sigma`, denoiser at `strength`, and with normalize each item
-    divided by max|audio| over its own samples."""
+    divided by max|audio| over its own samples.  precision: as WaveGlow.infer (None: model.precision)."""
+    mode = model._precision(precision)
     if not mels.is_cuda:
         raise RadmmmError("vocode_waveglow needs GPU tensors (there is no CPU path)")
     B, _, T = mels.shape
     dev = mels.device
     lens_d, host = _lens_arg(out_lens, B, T, dev)
-    audio = model._run(f32c(mels), lens_d, float(sigma))
+    audio = model._run(f32c(mels), lens_d, float(sigma), precision=mode)
     s_lens = host * HOP if host is not None else lens_d.long() * HOP
     if denoiser is not None:
         audio = denoiser(audio, strength, s_lens)[:, 0]
@@ -975,7 +1113,8 @@ def config_of_module(m) -> dict:
 
 
 def load_waveglow_vocoder(checkpoint_path: str, config_path: Optional[str] = None,
-                          device: Union[str, torch.device] = "cuda", allow_pickled_module: bool = False):
+                          device: Union[str, torch.device] = "cuda", allow_pickled_module: bool = False,
+                          precision: str = "fp32"):
     """load_waveglow_vocoder of vocoders/vocoder_utils.py:134-143.  Two checkpoint formats:
       * a plain file {'state_dict': ..., 'waveglow_config': {...}} (see INTEGRATION.md for the one-line conversion);
         without 'waveglow_config' the config JSON's "waveglow_config" section is used;
@@ -984,7 +1123,8 @@ def load_waveglow_vocoder(checkpoint_path: str, config_path: Optional[str] = Non
         the reference's glow.py on sys.path (this package never imports it); its state_dict and attributes are
         copied out.
     The file is read with torch's restricted unpickler first; a file that this refuses is fully unpickled only when the
-    caller opted in.  Returns (waveglow, denoiser) on `device`, in eval mode."""
+    caller opted in.  Returns (waveglow, denoiser) on `device`, in eval mode.  precision: the model's `precision`
+    attribute ("fp32", "h3" or "f16", see WaveGlow); a mode the config cannot run raises ValueError here."""
     try:
         ck = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
     except pickle.UnpicklingError as e:
@@ -1006,6 +1146,7 @@ def load_waveglow_vocoder(checkpoint_path: str, config_path: Optional[str] = Non
             cfg = json.load(fh)
         cfg = cfg.get("waveglow_config", cfg)
     model = WaveGlow(**cfg)
+    model.precision = model._precision(precision)
     model.load_state_dict(sd)
     model = model.to(device).eval()
     den = WaveGlowDenoiser(model).to(device).eval()

@@ -2,6 +2,7 @@
 """Batched WaveGlow benchmark (rad_mmm_amd/waveglow.py, csrc/waveglow.hip): one JSON line.
 
     python tools/waveglow_bench.py [--batch 32] [--frames 800] [--iters 3] [--warmup 1] [--analyze]
+                                   [--precision {fp32,h3,f16}]
     python tools/waveglow_bench.py --train [--batch 32] [--frames 800] [--iters 3] [--warmup 1]
 
 The shipped config (12 flows, 8 layers, 256 channels, n_group 8, 80 mels), random weights from a seed, every item at
@@ -10,7 +11,10 @@ seconds per second at 22050 Hz, the time of each launch family (events around ev
 chunk of items only), and the in_layers row GEMMs' fraction of the fp32-MFMA peak (157.3 TFLOPS on
 paper, MI355X).  --analyze adds the other direction in the same run and at the same shape: WaveGlow.analyze on seeded
 audio, timed the same way, under "analyze" in the same JSON line with the ratio analyze / infer and the time of the
-launch families only that direction has (group_audio, mix_fwd, end_coupling_fwd, nll_parts).
+launch families only that direction has (group_audio, mix_fwd, end_coupling_fwd, nll_parts).  --precision h3 / f16 times
+infer in that mode (WaveGlow.precision: the three WN GEMM families on the f16 matrix cores; split_cond is the one split
+pass over the conditioning rows) and adds the relative L2 distance of its output to the fp32 mode's on the same noise;
+the in_layers fraction stays relative to the fp32-MFMA peak in every mode, so that the modes compare on one scale.
 
 --train times one training step instead, WaveGlow.nll_loss + backward in training mode with weight norm applied, at the
 reference's training shape (batch 12, segments of 16000 samples = 62 frames) and at --batch / --frames: device
@@ -107,6 +111,7 @@ def main():
     ap.add_argument("--once", action="store_true", help="one untimed call only (for a kernel trace)")
     ap.add_argument("--analyze", action="store_true", help="also time WaveGlow.analyze (audio -> latent) at the same shape")
     ap.add_argument("--train", action="store_true", help="time one training step (nll_loss + backward) instead")
+    ap.add_argument("--precision", choices=("fp32", "h3", "f16"), default="fp32", help="WaveGlow.precision of infer")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("waveglow_bench needs an MI355X")
@@ -115,6 +120,7 @@ def main():
     model = WaveGlow(**SHIPPED)
     model.load_state_dict(seeded_state(model, 5))
     model = model.to(dev).eval()
+    model.precision = args.precision
     if args.train:
         return train_bench(model, args, dev)
     B, T = args.batch, args.frames
@@ -148,10 +154,18 @@ def main():
     flop_in = 2.0 * 3 * C * 2 * C                       # per row and launch
     in_tflops = flop_in * n_in * rows_chunk / (fam["in_layers"] * 1e-3) / 1e12 if fam["in_layers"] else 0.0
     audio_s = B * T * HOP / 22050.0
-    out = {"metric": "waveglow_infer_ms", "batch": B, "frames": T, "device_ms": ms, "all_ms": ts,
+    out = {"metric": "waveglow_infer_ms", "precision": args.precision, "batch": B, "frames": T, "device_ms": ms,
+           "all_ms": ts,
            "audio_seconds": audio_s, "audio_seconds_per_second": audio_s / (ms * 1e-3),
            "last_chunk_family_ms": fam, "last_chunk_rows": rows_chunk, "rows": B * T * HOP // 8,
            "in_layers_tflops": in_tflops, "in_layers_frac_of_fp32_mfma_peak": in_tflops * 1e12 / FP32_MFMA_PEAK}
+    if args.precision != "fp32":
+        gen = torch.Generator(device=dev).manual_seed(11)
+        noise = [torch.randn(B, ch, T * HOP // 8, device=dev, generator=gen) for ch in model.noise_shapes]
+        ref = model.infer(mel, lens, sigma=0.667, noise=noise, precision="fp32").double()
+        got = model.infer(mel, lens, sigma=0.667, noise=noise).double()
+        out["rel_l2_vs_fp32"] = float((got - ref).norm() / ref.norm())
+        del ref, got, noise
     if args.analyze:
         audio = (0.3 * torch.randn(B, T * HOP, generator=torch.Generator().manual_seed(7))).to(dev)
         for _ in range(args.warmup):

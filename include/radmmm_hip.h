@@ -785,6 +785,27 @@ int radmmm_wg_inv_logdet(const float* W, const int32_t* cs, int n, float* Winv, 
 int radmmm_wg_ungroup_cond(const float* rows, int ldr, float* up, int64_t up_item_stride, const int32_t* lens, int B,
                            int Tg, int n_mel, int n_group, radmmm_stream_t stream);
 
+/* Training on the f16 matrix cores (WaveGlow.train_precision "h3"): the two gradient producers of that backward pass also
+ * write, in the pass that computes the value, the RADMMM_SPLIT_F16 pair of scale * value -- the A operand of the data
+ * gradient (radmmm_rowgemm_h3) and the GY operand of the weight gradient (radmmm_wgrad_rm).  The conventions of the
+ * forward *_split kernels: [rows][ldp] halves, 8 columns per thread and one 16-byte store per half array; the pair is
+ * bit-identical to radmmm_split_f16(the fp32 output, scale); the fp32 outputs are bit-identical to the twin's; rows at or
+ * past an item's length are zeros in both halves and nothing is read there.  A row of the pair is `pcols` columns wide:
+ * the values, then zeros up to pcols (pcols == the value count: nothing else is written, so the pair may be a column
+ * slice of a wider [rows][ldp] buffer, as the fp32 output may).  C, ldp, pcols % 8 == 0, pcols <= ldp, 16-byte aligned
+ * pair arrays.  scale: a power of two (the gradient scale); sat_flag: optional device int, OR-ed with bit 0 when
+ * |scale * value| > 60000 was clamped (radmmm_split_opts.sat_flag): the only atomic, every result is bitwise repeatable.
+ * Everything else as the twin.  Additive entry points of ABI 4.
+ *   wg_coupling_bwd_split  wg_coupling_bwd + the pair dSh / dSl of scale * dS (C values per row, C <= pcols)
+ *   wg_gate_bwd_split      wg_gate_bwd + the pair dAh / dAl of scale * dA (2 C values per row, 2 C <= pcols) */
+int radmmm_wg_coupling_bwd_split(const float* S, int lds, const float* Wend, const float* bend, const float* Xs, int ldxs,
+                                 float* dX, int ldx, int col0, int n_half, int C, const float* g_ls, int ldg, float* dO,
+                                 float* dS, int ldds, void* dSh, void* dSl, int ldp, int pcols, float scale,
+                                 int32_t* sat_flag, const int32_t* lens, int rows, int T, radmmm_stream_t stream);
+int radmmm_wg_gate_bwd_split(const float* a, int lda, const float* cond, int ldcond, int cond_off, const float* g, int ldg,
+                             float* dA, int ldda, void* dAh, void* dAl, int ldp, int pcols, int C, float scale,
+                             int32_t* sat_flag, const int32_t* lens, int rows, int T, radmmm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Batched synthesis glue (TTSModel.sample_full / reconstruct_from_batch_attributes, tts_lightning_modules.py:286-437).
  * Additive entry points of ABI 4.  No floating-point atomics: every result is bitwise repeatable.

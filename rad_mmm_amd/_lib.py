@@ -229,6 +229,8 @@ def _load() -> C.CDLL:
         "radmmm_wg_nll_parts": [p, i, i, p, p, i, i, p, p],
         "radmmm_wg_coupling_bwd": [p, i, p, p, p, i, p, i, i, i, i, p, i, p, p, i, p, i, i, p],
         "radmmm_wg_gate_bwd": [p, i, p, i, i, p, i, p, i, i, p, i, i, p],
+        "radmmm_wg_coupling_bwd_split": [p, i, p, p, p, i, p, i, i, i, i, p, i, p, p, i, p, p, i, i, f, p, p, i, i, p],
+        "radmmm_wg_gate_bwd_split": [p, i, p, i, i, p, i, p, i, p, p, i, i, i, f, p, p, i, i, p],
         "radmmm_wg_start_bwd": [p, i, p, p, i, i, i, i, p, i, i, p],
         "radmmm_wg_outer_reduce": [p, i, i, p, i, i, p, p, p, i, i, p],
         "radmmm_wg_inv_logdet": [p, p, i, p, p, p],

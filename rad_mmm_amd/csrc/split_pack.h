@@ -75,6 +75,16 @@ __device__ __forceinline__ void store_split8_f16(void* hi_, void* lo_, long long
   if (lo_) *reinterpret_cast<f16x8_t*>(static_cast<_Float16*>(lo_) + elem_off_row + col) = lo;
 }
 
+// the same for a producer that reports saturation: returns max |s * x| of the 8 values (raise_sat_flag's argument)
+__device__ __forceinline__ float store_split8_f16_amax(void* hi_, void* lo_, long long elem_off_row, int col, float s,
+                                                       const float (&x)[8]) {
+  float amax = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(x[e] * s));
+  store_split8_f16(hi_, lo_, elem_off_row, col, s, x);
+  return amax;
+}
+
 // one element (generic / tail paths)
 __device__ __forceinline__ float store_split1_fmt(void* hi_, void* lo_, long long elem_off_row, int col, int fmt, float x8_mul,
                                                   float s, float x, void* lo16_ = nullptr) {

@@ -912,6 +912,122 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__
   }
 }
 
+// ---- the two gradient producers of train_precision "h3" ---------------------------------------------------------------
+// coupling_bwd_kernel / gate_bwd_kernel that also write the split f16 pair of scale * value (split_pack.h: the bits of
+// radmmm_split_f16 of the fp32 output) in the pass that computes it: the A operand of the data-gradient GEMM and the GY
+// operand of the weight gradient.  The conventions of the forward *_split kernels: a thread owns 8 columns of a row, one
+// 16-byte store per half array; rows at or past an item's length and the padding columns up to pcols are zeros in both
+// halves; the fp32 arithmetic is the twin's, operation for operation.  max |scale * value| is tracked per lane and the
+// saturation flag is raised once per wave after the loop (raise_sat_flag): the only atomic, and nothing reads it here.
+
+template <int NO>
+__global__ __launch_bounds__(256) void coupling_bwd_split_kernel(
+    const float* __restrict__ S, int lds, const float* __restrict__ Wend, const float* __restrict__ bend,
+    const float* __restrict__ Xs, int ldxs, float* __restrict__ dX, int ldx, int col0, int C,
+    const float* __restrict__ gls, int ldg, float* __restrict__ dO, float* __restrict__ dS, int ldds,
+    void* __restrict__ Ph, void* __restrict__ Pl, int ldp, int pcols, float scale, int* __restrict__ sat_flag,
+    const int32_t* __restrict__ lens, long long rows, int T) {
+  extern __shared__ __align__(16) float sh[];
+  float* w = sh;                    // [NO][C]
+  float* be = sh + NO * C;          // [NO]
+  for (int i = threadIdx.x; i < NO * C; i += blockDim.x) w[i] = Wend[i];
+  for (int i = threadIdx.x; i < NO; i += blockDim.x) be[i] = bend ? bend[i] : 0.f;
+  __syncthreads();
+  constexpr int NH = NO / 2;
+  const int sub = threadIdx.x & 15, rloc = threadIdx.x >> 4;
+  float sat = 0.f;
+  for (long long r0 = blockIdx.x * 16LL; r0 < rows; r0 += gridDim.x * 16LL) {
+    const long long r = r0 + rloc;
+    const bool valid = row_valid(r, rows, lens, T);
+    float acc[NO];
+    end_dot<NO>(S, lds, w, C, r, valid, sub, acc);
+    float d[NO];
+#pragma unroll
+    for (int o = 0; o < NO; ++o) d[o] = 0.f;
+    if (valid) {
+      const float* x1 = Xs + r * ldxs + col0 + NH;
+      const float* g1 = dX + r * ldx + col0 + NH;
+#pragma unroll
+      for (int k = 0; k < NH; ++k) {
+        const float e = expf(acc[NH + k] + be[NH + k]);
+        const float g = g1[k];
+        d[k] = g;
+        d[NH + k] = fmaf(g * e, x1[k], ldg ? gls[r * ldg + k] : gls[0]);
+      }
+    }
+    if (r < rows) {
+      float* dsr = dS + r * ldds;
+      for (int c = sub * 8; c < pcols; c += 128) {
+        float v[8];
+        zero8(v);
+        if (c < C) {
+#pragma unroll
+          for (int o = 0; o < NO; ++o) {
+            float ww[8];
+            load8(w + o * C + c, ww);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = fmaf(ww[e], d[o], v[e]);
+          }
+          store8(dsr + c, v);
+        }
+        sat = fmaxf(sat, radmmm::store_split8_f16_amax(Ph, Pl, r * ldp, c, scale, v));
+      }
+    }
+    __syncthreads();   // every lane of a row has read dX1' before lane 0 overwrites it (uniform trip count: r0 is per block)
+    if (sub == 0 && r < rows) {
+      float* g1 = dX + r * ldx + col0 + NH;
+#pragma unroll
+      for (int k = 0; k < NH; ++k) g1[k] = valid ? d[k] * expf(acc[NH + k] + be[NH + k]) : 0.f;
+#pragma unroll
+      for (int o = 0; o < NO; ++o) dO[r * NO + o] = d[o];
+    }
+  }
+  radmmm::raise_sat_flag(sat_flag, sat);
+}
+
+// thread i of a row: 8 columns c of the C gate channels (dt -> columns c, ds -> columns C + c of dA and of the pair), or,
+// past them, 8 padding columns of the pair
+__global__ __launch_bounds__(256) void gate_bwd_split_kernel(
+    const float* __restrict__ a, int lda, const float* __restrict__ cond, int ldcond, int off,
+    const float* __restrict__ g, int ldg, float* __restrict__ dA, int ldda, void* __restrict__ Ph,
+    void* __restrict__ Pl, int ldp, int pcols, int C, float scale, int* __restrict__ sat_flag,
+    const int32_t* __restrict__ lens, long long rows, int T) {
+  const int qc = C >> 3, q = qc + ((pcols - 2 * C) >> 3);
+  const long long total = rows * q;
+  float sat = 0.f;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / q;
+    const int j = (int)(i - r * q);
+    float dt[8], ds[8];
+    zero8(dt);
+    zero8(ds);
+    if (j < qc) {
+      const int c = j * 8;
+      if (row_valid(r, rows, lens, T)) {
+        float ta[8], sa[8], tc[8], sc[8], gv[8];
+        const float* ar = a + r * lda + c;
+        const float* cr = cond + r * ldcond + off + c;
+        load8(ar, ta);
+        load8(ar + C, sa);
+        load8(cr, tc);
+        load8(cr + C, sc);
+        load8(g + r * ldg + c, gv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) gate_bwd1(ta[e], tc[e], sa[e], sc[e], gv[e], dt[e], ds[e]);
+      }
+      float* dr = dA + r * ldda + c;
+      store8(dr, dt);
+      store8(dr + C, ds);
+      sat = fmaxf(sat, radmmm::store_split8_f16_amax(Ph, Pl, r * ldp, c, scale, dt));
+      sat = fmaxf(sat, radmmm::store_split8_f16_amax(Ph, Pl, r * ldp, C + c, scale, ds));
+    } else {
+      radmmm::store_split8_f16(Ph, Pl, r * ldp, 2 * C + (j - qc) * 8, scale, dt);
+    }
+  }
+  radmmm::raise_sat_flag(sat_flag, sat);
+}
+
 // dX[r, col0 + i] += sum_c Wt[i*C + c] * dH[r, c], i < NH (Wt = the start weight transposed, in LDS): end_dot's sum
 template <int NH>
 __global__ __launch_bounds__(256) void start_bwd_kernel(const float* __restrict__ dH, int ldh,
@@ -1091,6 +1207,61 @@ extern "C" int radmmm_wg_gate_bwd(const float* a, int lda, const float* cond, in
   hipLaunchKernelGGL(gate_bwd_kernel, dim3(grid_for((long long)rows * (C / 4), 256)), dim3(256), 0, ST(stream), a, lda,
                      cond, ldcond, cond_off, g, ldg, dA, ldda, C, lens, (long long)rows, T);
   return radmmm::check_launch("wg_gate_bwd");
+}
+
+extern "C" int radmmm_wg_coupling_bwd_split(const float* S, int lds, const float* Wend, const float* bend, const float* Xs,
+                                            int ldxs, float* dX, int ldx, int col0, int n_half, int C, const float* g_ls,
+                                            int ldg, float* dO, float* dS, int ldds, void* dSh, void* dSl, int ldp,
+                                            int pcols, float scale, int32_t* sat_flag, const int32_t* lens, int rows,
+                                            int T, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(S && Wend && Xs && dX && g_ls && dO && dS && dSh && dSl, "wg_coupling_bwd_split: null pointer");
+  const int NO = 2 * n_half;
+  const long long smem_twin = ((long long)NO * C + NO * NO + NO) * 4;   // the limit of the forward kernels
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && C > 0 && C % 8 == 0 && lds % 4 == 0 && lds >= C &&
+                     ldds % 4 == 0 && ldds >= C && n_half >= 1 && n_half <= 4 && col0 >= 0 && col0 + NO <= ldx &&
+                     col0 + NO <= ldxs && (ldg == 0 || ldg >= n_half) && smem_twin <= 32768 && ldp % 8 == 0 &&
+                     pcols % 8 == 0 && pcols >= C && ldp >= pcols,
+                 "wg_coupling_bwd_split: bad dims (rows=%d T=%d C=%d lds=%d ldds=%d n_half=%d col0=%d ldx=%d ldxs=%d ldg=%d "
+                 "ldp=%d pcols=%d; C, ldp, pcols %% 8 == 0, C <= pcols <= ldp)",
+                 rows, T, C, lds, ldds, n_half, col0, ldx, ldxs, ldg, ldp, pcols);
+  RADMMM_REQUIRE(radmmm::aligned16(S) && radmmm::aligned16(Wend) && radmmm::aligned16(dS) && radmmm::aligned16(dSh) &&
+                     radmmm::aligned16(dSl),
+                 "wg_coupling_bwd_split: S / Wend / dS / dSh / dSl must be 16B aligned");
+  const size_t smem = ((size_t)NO * C + NO) * 4;
+  const dim3 grid(grid_for(((long long)rows + 15) / 16, 1)), block(256);
+#define WG_CPL_BWD_SPLIT(NOV)                                                                                          \
+  hipLaunchKernelGGL(coupling_bwd_split_kernel<NOV>, grid, block, smem, ST(stream), S, lds, Wend, bend, Xs, ldxs, dX, \
+                     ldx, col0, C, g_ls, ldg, dO, dS, ldds, dSh, dSl, ldp, pcols, scale, sat_flag, lens,              \
+                     (long long)rows, T)
+  switch (NO) {
+    case 2: WG_CPL_BWD_SPLIT(2); break;
+    case 4: WG_CPL_BWD_SPLIT(4); break;
+    case 6: WG_CPL_BWD_SPLIT(6); break;
+    default: WG_CPL_BWD_SPLIT(8); break;
+  }
+#undef WG_CPL_BWD_SPLIT
+  return radmmm::check_launch("wg_coupling_bwd_split");
+}
+
+extern "C" int radmmm_wg_gate_bwd_split(const float* a, int lda, const float* cond, int ldcond, int cond_off,
+                                        const float* g, int ldg, float* dA, int ldda, void* dAh, void* dAl, int ldp,
+                                        int pcols, int C, float scale, int32_t* sat_flag, const int32_t* lens, int rows,
+                                        int T, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(a && cond && g && dA && dAh && dAl, "wg_gate_bwd_split: null pointer");
+  RADMMM_REQUIRE(rows > 0 && T > 0 && rows % T == 0 && C > 0 && C % 8 == 0 && lda % 4 == 0 && lda >= 2 * C &&
+                     ldcond % 4 == 0 && cond_off >= 0 && cond_off % 4 == 0 && cond_off + 2 * C <= ldcond &&
+                     ldg % 4 == 0 && ldg >= C && ldda % 4 == 0 && ldda >= 2 * C && ldp % 8 == 0 && pcols % 8 == 0 &&
+                     pcols >= 2 * C && ldp >= pcols,
+                 "wg_gate_bwd_split: bad dims (rows=%d T=%d C=%d lda=%d ldcond=%d cond_off=%d ldg=%d ldda=%d ldp=%d "
+                 "pcols=%d; C, ldp, pcols %% 8 == 0, 2 C <= pcols <= ldp)",
+                 rows, T, C, lda, ldcond, cond_off, ldg, ldda, ldp, pcols);
+  RADMMM_REQUIRE(radmmm::aligned16(a) && radmmm::aligned16(cond) && radmmm::aligned16(g) && radmmm::aligned16(dA) &&
+                     radmmm::aligned16(dAh) && radmmm::aligned16(dAl),
+                 "wg_gate_bwd_split: a / cond / g / dA / dAh / dAl must be 16B aligned");
+  hipLaunchKernelGGL(gate_bwd_split_kernel, dim3(grid_for((long long)rows * ((pcols - C) / 8), 256)), dim3(256), 0,
+                     ST(stream), a, lda, cond, ldcond, cond_off, g, ldg, dA, ldda, dAh, dAl, ldp, pcols, C, scale,
+                     sat_flag, lens, (long long)rows, T);
+  return radmmm::check_launch("wg_gate_bwd_split");
 }
 
 extern "C" int radmmm_wg_start_bwd(const float* dH, int ldh, const float* Wt, float* dX, int ldx, int col0, int n_half,

@@ -33,12 +33,16 @@ Training (train.py:62-152 of that vocoder): in training mode nll_loss and forwar
 (_WaveGlowFn) whose backward walks the flows from last to first, runs one flow's WN again into per-layer buffers and
 back-propagates through it with row GEMMs (b_layout 1), radmmm_wgrad_f32, radmmm_colsum and the wg_*_bwd kernels;
 apply_weight_norm / remove_weight_norm switch between the reference's weight_g / weight_v parameters and the folded
-form.  Eval mode records no graph and runs exactly the launches above.
+form.  Eval mode records no graph and runs exactly the launches above.  With WaveGlow.train_precision "h3" the step runs
+the three GEMM families of every pass on the f16 matrix cores instead (_wn_split for the forward and the recomputation,
+_backward_chunk_h3: radmmm_rowgemm_h3 / radmmm_wgrad_rm on pairs that wg_coupling_bwd_split, wg_gate_bwd_split and the
+GEMM epilogues write times a power-of-two gradient scale).
 """
 from __future__ import annotations
 
 import ctypes
 import json
+import math
 import pickle
 from typing import Optional, Sequence, Tuple, Union
 
@@ -55,6 +59,17 @@ _A_OPERAND_BYTES = 2 ** 31 - 2 ** 16     # the row GEMM's 16-row fast path needs
 _COND_BYTES = 8 << 30                    # cap of the per-flow conditioning buffer [rows, 2 * n_channels * n_layers]
 _TRAIN_ACT_BYTES = 8 << 30               # cap of what the backward of one flow holds (see WaveGlow._train_chunk)
 PRECISIONS = ("fp32", "h3", "f16")       # WaveGlow.precision: how infer runs the three WN GEMM families
+TRAIN_PRECISIONS = ("fp32", "h3")        # WaveGlow.train_precision: how the training step runs them
+_WGRAD_RM_ITEMS = 1024                   # radmmm_wgrad_rm: items per launch
+
+
+def auto_grad_scale(n_samples: int) -> float:
+    """the automatic gradient scale of train_precision "h3": the smallest power of two at or above the batch's padded
+    sample count B * T * 256, computed on the host.  A per-sample-normalised loss (nll_loss, WaveGlowLoss) seeds the
+    backward pass with z / (sigma^2 N), N <= n_samples, so the scaled seed is z / sigma^2 times 1 .. 2 at equal lengths:
+    of order 1, with fp16's 16 octaves up to 65504 above it and 14 octaves of normals plus 10 of subnormals below
+    (DESIGN 4.19)."""
+    return float(2 ** max(0, (max(1, int(n_samples)) - 1).bit_length()))
 
 
 class _WN(nn.Module):
@@ -179,7 +194,18 @@ class WaveGlow(nn.Module):
     with host lengths no device -> host synchronisation).  apply_weight_norm() / remove_weight_norm() switch start,
     in_layers, cond_layer and res_skip_layers between weight_g / weight_v (a reference training checkpoint's keys) and
     the folded weight; load_state_dict takes either form in either state.  torch.optim.Adam on parameters() is the
-    reference's optimizer.  fp32 only, one GPU.
+    reference's optimizer.  One GPU.
+
+    train_precision ("fp32", the default, or "h3"; the attribute, or per call nll_loss(..., precision=)): how a training
+    step runs cond_layer, the in_layers and the res_skip layers.  "h3" runs them on the f16 matrix cores with three split
+    products in every pass -- forward, the backward's recomputation, data gradients (radmmm_rowgemm_h3 against transposed
+    split weights) and weight gradients (radmmm_wgrad_rm) -- while every master array, start / end, the coupling, the
+    mixes, the likelihood, the upsample and the bias sums stay fp32.  Gradients enter the fp16 pairs times grad_scale:
+    None (auto_grad_scale: the power of two at or above the padded sample count B * T * 256, computed on the host; it
+    assumes a per-sample-normalised loss such as nll_loss or WaveGlowLoss) or a power of two; .grad holds the true values.
+    grad_saturated() reads (and clears) the device flag a clamped pair raises; nothing else waits for the device.  It
+    needs what infer's "h3" needs and at least 32 group steps per padded item.  "f16" (one product) is not built.  Eval
+    mode, no_grad and `precision` (infer's switch) are not affected by it, nor it by them.
 
     Deliberate differences from the reference's forward: log|det W| where torch.logdet is NaN for a negative
     determinant; with ragged lengths every sum and the normalisation run over an item's own valid samples (the
@@ -210,6 +236,9 @@ class WaveGlow(nn.Module):
             self.WN.append(_WN(n_half, n_mel_channels * n_group, **WN_config))
         self.n_remaining_channels = n_rem
         self.precision = "fp32"
+        self.train_precision = "fp32"
+        self.grad_scale = None             # train_precision "h3": None (auto_grad_scale) or a power of two
+        self._sat_flag = None              # device int32 [1]: OR-ed by the split producers of an "h3" backward pass
         self._folded = None
         self._folded_key = None
         self._weight_normed = False
@@ -379,6 +408,46 @@ class WaveGlow(nn.Module):
                                  f"(the f16 GEMM's K % 32 == 0); got n_channels {C}, n_mel_channels * n_group {K}")
         return mode
 
+    def _train_precision(self, precision: Optional[str] = None, mel: Optional[torch.Tensor] = None) -> str:
+        """the mode of a training step (None: the attribute), checked like _precision: a known name, and for "h3" the
+        GEMM's K % 32, a valid grad_scale and, given the batch, radmmm_wgrad_rm's T >= 32 group steps per padded item
+        (the mode keeps no fp32 copy of its operands to fall back on)"""
+        mode = self.train_precision if precision is None else precision
+        if mode not in TRAIN_PRECISIONS:
+            raise ValueError(f"train_precision {mode!r}: one of {TRAIN_PRECISIONS}"
+                             + (" (one-product \"f16\" training is not built)" if mode == "f16" else ""))
+        if mode == "h3":
+            C, K = self.WN[0].n_channels, self.n_mel_channels * self.n_group
+            if C % 32 or K % 32:
+                raise ValueError(f"train_precision 'h3' needs n_channels % 32 == 0 and (n_mel_channels * n_group) % 32 == 0 "
+                                 f"(the f16 GEMM's K % 32 == 0); got n_channels {C}, n_mel_channels * n_group {K}")
+            self._g_scale(1)
+            if mel is not None and mel.dim() == 3:
+                Tg = mel.shape[2] * (HOP // self.n_group)
+                if Tg < 32:
+                    raise ValueError(f"train_precision 'h3' needs at least 32 group steps per padded item (the weight "
+                                     f"gradient's K step); got {Tg}")
+        return mode
+
+    def _g_scale(self, n_samples: int) -> float:
+        """the gradient scale of an "h3" step over n_samples = B * T * 256 padded samples"""
+        if self.grad_scale is None:
+            return auto_grad_scale(n_samples)
+        g = float(self.grad_scale)
+        if not (g > 0.0 and math.isfinite(g) and math.frexp(g)[0] == 0.5):
+            raise ValueError(f"grad_scale {self.grad_scale!r} (train_precision 'h3'): None or a power of two")
+        return g
+
+    def grad_saturated(self) -> bool:
+        """True when a split producer of an "h3" backward pass clamped a scaled gradient at fp16's range since the last
+        call (the device flag word is read here and cleared: the only place that waits for the device).  Then lower
+        grad_scale; the fp32 gradient arrays never carry the scale."""
+        if self._sat_flag is None:
+            return False
+        hit = bool(int(self._sat_flag.item()) & 1)
+        self._sat_flag.zero_()
+        return hit
+
     @fp32_region
     def infer(self, mel: torch.Tensor, lens=None, sigma: float = 1.0, noise: Optional[Sequence[torch.Tensor]] = None,
               precision: Optional[str] = None) -> torch.Tensor:
@@ -534,6 +603,21 @@ class WaveGlow(nn.Module):
                             "rs": [sp(W) for W, _ in fk["rs"]]} for fk in f["flows"]]
         return cache[mode]
 
+    @staticmethod
+    def _split_weights_t(f) -> list:
+        """per flow the transposed "h3" pairs [taps, K, Cout] of _split_weights: the K-contiguous B operands of the data
+        gradients (radmmm_rowgemm_h3 has no b_layout 1).  Made once per step and kept inside `f` like the pairs they are
+        made from.  One radmmm_split_f16 and one radmmm_transpose_f16_pair launch per tensor: 2 L + 1 tensors per flow,
+        2 * 12 * 17 = 408 launches on the shipped config (radmmm_transpose_f16_pair_multi takes the 8-bit format only)."""
+        if "split_t" not in f:
+            def tp(W):
+                Wh, Wl = W
+                _, Cout, K = Wh.shape
+                return ops.transpose_split(Wh, Wl, Cout, K, Cout)
+            f["split_t"] = [{"cond": tp(sw["cond"]), "in": [tp(W) for W in sw["in"]], "rs": [tp(W) for W in sw["rs"]]}
+                            for sw in WaveGlow._split_weights(f, "h3")]
+        return f["split_t"]
+
     def _wn_split_buffers(self, R: int, dev, mode: str):
         wn0 = self.WN[0]
         C, L = wn0.n_channels, wn0.n_layers
@@ -560,6 +644,9 @@ class WaveGlow(nn.Module):
         ng, ldk = self.n_group, f["ldk"]
         cond, H, S, A, rs = (bufs[n] for n in ("cond", "H", "S", "A", "rs"))
         Hh, Hl, ah, al = (bufs[n] for n in ("Hh", "Hl", "acts_h", "acts_l"))
+        layers = bufs.get("layers")     # the training step's recomputation: per layer the pair of H_i, A_i, the pair of acts_i
+        if layers is not None:
+            Hh, Hl = layers[0]["Hh"], layers[0]["Hl"]
         npr = ops.NPROD[mode]
         inv_ws = 1.0 / ops.W_SCALE
 
@@ -589,6 +676,8 @@ class WaveGlow(nn.Module):
                        bias=fk["cond"][1])
         done()
         for i in range(L):
+            if layers is not None:
+                A, ah, al = layers[i]["A"], layers[i]["acts_h"], layers[i]["acts_l"]
             done = timed("in_layers")
             gemm(Hh, Hl, C, sw["in"][i], C=A, ldc=2 * C, N=2 * C, K=C, taps=ksz, dil=2 ** i, a_mask_mode=1,
                  bias=fk["in"][i][1])
@@ -602,6 +691,8 @@ class WaveGlow(nn.Module):
             gemm(ah, al, C, sw["rs"][i], C=rs, ldc=2 * C, N=C if last else 2 * C, K=C, taps=1, bias=fk["rs"][i][1])
             done()
             done = timed("res_skip_update")
+            if layers is not None and not last:     # H_{i+1}'s pair goes to the next layer's buffers; fp32 H in place
+                Hh, Hl = layers[i + 1]["Hh"], layers[i + 1]["Hl"]
             check(lib.radmmm_wg_res_skip_split(ptr(rs), 2 * C, ptr(H), C, ptr(S), C, ptr(Hh), ptr(Hl), C, C, int(i == 0),
                                                int(last), ptr(lens_g), R, Tg, s), "wg_res_skip_split")
             done()
@@ -674,11 +765,12 @@ class WaveGlow(nn.Module):
         return f32c(mel), f32c(audio)
 
     def _analyze_run(self, mel, audio, lens_d, want_log_s: bool = False, events: Optional[dict] = None, f=None,
-                     snaps=None, Bc=None):
+                     snaps=None, Bc=None, mode: str = "fp32"):
         """mel [B, n_mel, T], audio [B, T*HOP] fp32 on the device, lens_d int32 [B] on the device (frames) ->
         (z rows [B*Tg, n_group], parts [B, 2] float64 = (sum z^2, sum log_s) per item, the per-flow log_s rows
         [B*Tg, n_half_k] or None).  Chunked over items as _run; events as there.  f: the packed weights (default: the
-        cached fold); snaps [n_flows, B*Tg, n_group]: receives the rows as they enter each flow (the training step)."""
+        cached fold); snaps [n_flows, B*Tg, n_group]: receives the rows as they enter each flow (the training step).
+        mode "h3" (the training step under train_precision "h3"): the WN through _wn_split."""
         B, _, T = mel.shape
         dev = mel.device
         ng = self.n_group
@@ -696,10 +788,10 @@ class WaveGlow(nn.Module):
             r0, r1 = b0 * Tg, b1 * Tg
             self._analyze_chunk(f, mel[b0:b1], audio[b0:b1], lens_d[b0:b1], X[r0:r1], ls[r0:r1], parts[b0:b1],
                                 None if logs is None else [t[r0:r1] for t in logs], events if b1 == B else None,
-                                None if snaps is None else snaps[:, r0:r1])
+                                None if snaps is None else snaps[:, r0:r1], mode)
         return X, parts, logs
 
-    def _analyze_chunk(self, f, mel, audio, lens_d, X, ls, parts, logs, events, snaps=None) -> None:
+    def _analyze_chunk(self, f, mel, audio, lens_d, X, ls, parts, logs, events, snaps=None, mode: str = "fp32") -> None:
         B, _, T = mel.shape
         ng = self.n_group
         per = HOP // ng
@@ -713,7 +805,15 @@ class WaveGlow(nn.Module):
         check(lib.radmmm_wg_group_audio(ptr(audio), audio.stride(0), ptr(X), ng, ng, ptr(lens_g), B, Tg, s),
               "wg_group_audio")
         done()
-        bufs = self._wn_buffers(R, mel.device)
+        if mode == "fp32":
+            bufs = self._wn_buffers(R, mel.device)
+        else:
+            sw = self._split_weights(f, mode)
+            bufs = self._wn_split_buffers(R, mel.device, mode)
+            done = timed("split_cond")      # one split pass over the conditioning rows for every flow's cond_layer GEMM
+            cih, cil = ops.split_f16(ci, f["ldk"], 1.0, f["ldk"], ops.NPROD[mode])
+            done()
+            del ci
         c = ng
         for k in range(self.n_flows):
             if k % self.n_early_every == 0 and k > 0:
@@ -726,7 +826,10 @@ class WaveGlow(nn.Module):
             done = timed("mix_fwd")
             check(lib.radmmm_wg_mix_fwd(ptr(X), ng, col0, c, ptr(fk["mix"]), ptr(lens_g), R, Tg, s), "wg_mix_fwd")
             done()
-            S = self._wn(f, fk, X, col0, nh, ci, bufs, lens_g, R, Tg, timed)
+            if mode == "fp32":
+                S = self._wn(f, fk, X, col0, nh, ci, bufs, lens_g, R, Tg, timed)
+            else:
+                S = self._wn_split(f, fk, sw[k], X, col0, nh, cih, cil, bufs, lens_g, R, Tg, timed, mode)
             We, be = fk["end"]
             done = timed("end_coupling_fwd")
             check(lib.radmmm_wg_end_coupling_fwd(ptr(S), C, ptr(We), ptr(be), ptr(X), ng, col0, nh, C, ptr(ls),
@@ -737,6 +840,21 @@ class WaveGlow(nn.Module):
         done = timed("nll_parts")
         check(lib.radmmm_wg_nll_parts(ptr(X), ng, ng, ptr(ls), ptr(lens_g), B, Tg, ptr(parts), s), "wg_nll_parts")
         done()
+
+    def _upsample_grads(self, f, dci, xm, lens_d, lens_g, B: int, T: int, out: dict) -> None:
+        """the conditioning's gradient rows dci [R, ldk] -> channels-last gradient of the upsampled mel -> the polyphase
+        GEMM's weight gradient against the masked mel rows xm, and the bias; into out (both training precisions: fp32)"""
+        n_mel, ng = self.n_mel_channels, self.n_group
+        Tg = T * (HOP // ng)
+        dev = dci.device
+        dup = torch.empty(B * T, HOP * n_mel, device=dev, dtype=torch.float32)
+        check(lib.radmmm_wg_ungroup_cond(ptr(dci), f["ldk"], ptr(dup), T * HOP * n_mel, ptr(lens_g), B, Tg, n_mel, ng,
+                                         stream()), "wg_ungroup_cond")
+        taps = f["up"][0].shape[0]
+        P = _wgrad(dup, HOP * n_mel, HOP * n_mel, xm, f["ldm"], n_mel, B * T, T, lens_d, taps, 1, 1)
+        j = torch.arange(UPSAMPLE_KERNEL, device=dev)          # the inverse of pack_polyphase (padding 0, offset 0)
+        out["upsample.weight"] = P.view(taps, HOP, n_mel, n_mel)[taps // 2 - j // HOP, j % HOP].permute(2, 1, 0)
+        out["upsample.bias"] = _colsum(dup, HOP * n_mel, B * T, HOP * n_mel).view(HOP, n_mel).sum(0)
 
     def _backward_chunk(self, f, mel, lens_d, snaps, dX, g_ls, events) -> dict:
         """the backward pass of _analyze_chunk for the items of one chunk.  snaps [n_flows, R, n_group]: the rows as they
@@ -834,16 +952,142 @@ class WaveGlow(nn.Module):
             check(lib.radmmm_wg_mix_fwd(ptr(dX), ng, col0, c, ptr(fk["mix"].t().contiguous()), ptr(lens_g), R, Tg, s),
                   "wg_mix_fwd")
             done()
-        # the conditioning: rows -> channels-last gradient of the upsampled mel -> the polyphase GEMM's weight gradient
         done = timed("bwd_upsample")
-        dup = empty(B * T, HOP * n_mel)
-        check(lib.radmmm_wg_ungroup_cond(ptr(dci_prev), ldk, ptr(dup), T * HOP * n_mel, ptr(lens_g), B, Tg, n_mel, ng, s),
-              "wg_ungroup_cond")
-        taps = f["up"][0].shape[0]
-        P = _wgrad(dup, HOP * n_mel, HOP * n_mel, xm, f["ldm"], n_mel, B * T, T, lens_d, taps, 1, 1)
-        j = torch.arange(UPSAMPLE_KERNEL, device=dev)          # the inverse of pack_polyphase (padding 0, offset 0)
-        out["upsample.weight"] = P.view(taps, HOP, n_mel, n_mel)[taps // 2 - j // HOP, j % HOP].permute(2, 1, 0)
-        out["upsample.bias"] = _colsum(dup, HOP * n_mel, B * T, HOP * n_mel).view(HOP, n_mel).sum(0)
+        self._upsample_grads(f, dci_prev, xm, lens_d, lens_g, B, T, out)
+        done()
+        return out
+
+    def _backward_chunk_h3(self, f, mel, lens_d, snaps, dX, g_ls, events, g_scale: float) -> dict:
+        """_backward_chunk under train_precision "h3": the data and weight gradients of cond_layer, the in_layers and the
+        res_skip layers on the f16 matrix cores with three products (radmmm_rowgemm_h3 against the transposed split
+        weights, radmmm_wgrad_rm on row-major pairs), the recomputation through _wn_split into per-layer pair buffers.
+        Every fp32 array holds the true values, as in _backward_chunk; only the gradient pairs carry g_scale (written by
+        wg_coupling_bwd_split, wg_gate_bwd_split and the in_layer data gradient's Ch / Cl), and acc_scale takes it and
+        ops.W_SCALE out again.  start / end, the coupling, the mixes, every bias column sum and the upsample stay fp32."""
+        B, n_mel, T = mel.shape
+        dev = mel.device
+        ng = self.n_group
+        per = HOP // ng
+        Tg, R = T * per, B * T * per
+        wn0 = self.WN[0]
+        C, L, ksz = wn0.n_channels, wn0.n_layers, wn0.kernel_size
+        ldk, cols = f["ldk"], n_mel * ng
+        lens_g = lens_d * per
+        s = stream()
+        timed = self._timer(events, R)
+        if self._sat_flag is None or self._sat_flag.device != dev:
+            self._sat_flag = torch.zeros(1, device=dev, dtype=torch.int32)
+        flag = self._sat_flag
+        sw, swt = self._split_weights(f, "h3"), self._split_weights_t(f)
+        inv_g, inv_gw = 1.0 / g_scale, 1.0 / (g_scale * ops.W_SCALE)
+        ci, xm = self._conditioning(f, mel, lens_d, lens_g, timed, keep_xm=True)
+        done = timed("split_cond")
+        cih, cil = ops.split_f16(ci, ldk, 1.0, ldk, 3)
+        done()
+        del ci
+
+        def empty(*shape, dtype=torch.float32):
+            return torch.empty(*shape, device=dev, dtype=dtype)
+
+        def pair(n):
+            return empty(R, n, dtype=torch.float16), empty(R, n, dtype=torch.float16)
+
+        def wgrad_rm(gy, x, Mc, Nc, lens=None, taps=1, dil=1):
+            P = ops.wgrad_rm_slabs(gy, x, B, Tg, Mc, Nc, taps, dil, inv_g, lens)
+            return P.sum(0) if P.shape[0] > 1 else P[0]
+
+        def layer():
+            Hh, Hl = pair(C)
+            ah, al = pair(C)
+            return {"Hh": Hh, "Hl": Hl, "A": empty(R, 2 * C), "acts_h": ah, "acts_l": al}
+        bufs = {"cond": empty(R, 2 * C * L), "H": empty(R, C), "S": empty(R, C), "rs": empty(R, 2 * C), "A": None,
+                "Hh": None, "Hl": None, "acts_h": None, "acts_l": None, "layers": [layer() for _ in range(L)]}
+        dcond = empty(R, 2 * C * L)          # d cond, fp32: the bias column sums read it
+        dch, dcl = pair(2 * C * L)           # its scaled pair; column slice i is the GY / A operand of in_layer i
+        GHS = empty(R, 2 * C)                # [d H_{i+1} | d S], fp32
+        Gh, Gl = pair(2 * C)                 # its scaled pair: the A operand of the res_skip data gradient
+        dacts, dO, Xp = empty(R, C), empty(R, ng), empty(R, ng)
+        dci, dci_prev = empty(R, ldk), None
+        out = {}
+        for k in reversed(range(self.n_flows)):
+            fk = f["flows"][k]
+            c = fk["c"]
+            nh, col0 = c // 2, ng - c
+            p = f"WN.{k}."
+            # recompute: the mixed rows and the WN on them, the launches (and bits) of this mode's forward
+            done = timed("bwd_recompute")
+            Xp.copy_(snaps[k])
+            check(lib.radmmm_wg_mix_fwd(ptr(Xp), ng, col0, c, ptr(fk["mix"]), ptr(lens_g), R, Tg, s), "wg_mix_fwd")
+            S = self._wn_split(f, fk, sw[k], Xp, col0, nh, cih, cil, bufs, lens_g, R, Tg, lambda name: (lambda: None),
+                               "h3")
+            done()
+            We, be = fk["end"]
+            done = timed("bwd_coupling")
+            gl = g_ls[k]
+            check(lib.radmmm_wg_coupling_bwd_split(ptr(S), C, ptr(We), ptr(be), ptr(Xp), ng, ptr(dX), ng, col0, nh, C,
+                                                   ptr(gl), 0 if gl.dim() == 1 else nh, ptr(dO), ptr(GHS[:, C:]), 2 * C,
+                                                   ptr(Gh[:, C:]), ptr(Gl[:, C:]), 2 * C, C, g_scale, ptr(flag),
+                                                   ptr(lens_g), R, Tg, s), "wg_coupling_bwd_split")
+            out[p + "end.weight"] = _outer_reduce(dO, 2 * nh, 2 * nh, S, C, C, lens_g, R, Tg)[:, :, None]
+            out[p + "end.bias"] = _outer_reduce(None, 0, 1, dO, 2 * nh, 2 * nh, lens_g, R, Tg)[0]
+            done()
+            for i in reversed(range(L)):
+                last = i == L - 1
+                lay = bufs["layers"][i]
+                G, Mr = (GHS[:, C:], C) if last else (GHS, 2 * C)
+                Gp = (Gh[:, C:], Gl[:, C:]) if last else (Gh, Gl)
+                done = timed("bwd_res_skip")
+                Th, Tl = swt[k]["rs"][i]
+                rowgemm_h3(Ah=Gp[0], Al=Gp[1], lda_h=2 * C, Bh=Th, Bl=Tl, ldb_h=Mr, acc_scale=inv_gw, nprod=3, C=dacts,
+                           ldc=C, M=R, N=C, K=Mr, T=Tg, lens=lens_g)
+                out[p + f"res_skip_layers.{i}.weight"] = wgrad_rm(Gp, (lay["acts_h"], lay["acts_l"]), Mr, C)[0][:, :, None]
+                out[p + f"res_skip_layers.{i}.bias"] = _colsum(G, 2 * C, R, Mr)
+                done()
+                done = timed("bwd_gate")
+                dA = dcond[:, 2 * C * i:]
+                dAp = (dch[:, 2 * C * i:], dcl[:, 2 * C * i:])
+                check(lib.radmmm_wg_gate_bwd_split(ptr(lay["A"]), 2 * C, ptr(bufs["cond"]), 2 * C * L, 2 * C * i,
+                                                   ptr(dacts), C, ptr(dA), 2 * C * L, ptr(dAp[0]), ptr(dAp[1]), 2 * C * L,
+                                                   2 * C, C, g_scale, ptr(flag), ptr(lens_g), R, Tg, s),
+                      "wg_gate_bwd_split")
+                done()
+                done = timed("bwd_in_layers")
+                out[p + f"in_layers.{i}.weight"] = wgrad_rm(dAp, (lay["Hh"], lay["Hl"]), 2 * C, C, lens_g, ksz,
+                                                            2 ** i).permute(1, 2, 0)
+                # d H_i = d H_{i+1} + the data gradient of the dilated conv (taps flipped: sign -1), fp32 in place in GHS
+                # and as the scaled pair in the left half of the [dH | dS] pair
+                Th, Tl = swt[k]["in"][i]
+                rowgemm_h3(Ah=dAp[0], Al=dAp[1], lda_h=2 * C * L, Bh=Th, Bl=Tl, ldb_h=2 * C, b_tap_stride_h=Th.stride(0),
+                           acc_scale=inv_gw, nprod=3, C=GHS, ldc=2 * C, M=R, N=C, K=2 * C, taps=ksz, dil=2 ** i, sign=-1,
+                           T=Tg, lens=lens_g, a_mask_mode=0, add=None if last else GHS, ldadd=2 * C, postmask=1, Ch=Gh,
+                           Cl=Gl, ldch=2 * C, ch_scale=g_scale, sat_flag=flag)
+                done()
+            done = timed("bwd_start")
+            Ws, _ = fk["start"]
+            out[p + "start.weight"] = _outer_reduce(Xp[:, col0:], ng, nh, GHS, 2 * C, C, lens_g, R, Tg).t()[:, :, None]
+            out[p + "start.bias"] = _outer_reduce(None, 0, 1, GHS, 2 * C, C, lens_g, R, Tg)[0]
+            check(lib.radmmm_wg_start_bwd(ptr(GHS), 2 * C, ptr(Ws.t().contiguous()), ptr(dX), ng, col0, nh, C, ptr(lens_g),
+                                          R, Tg, s), "wg_start_bwd")
+            done()
+            done = timed("bwd_cond_layer")
+            bsum = _colsum(dcond, 2 * C * L, R, 2 * C * L)     # cond_layer's bias and, slice i, in_layer i's
+            out[p + "cond_layer.bias"] = bsum
+            for i in range(L):
+                out[p + f"in_layers.{i}.bias"] = bsum[2 * C * i:2 * C * (i + 1)]
+            out[p + "cond_layer.weight"] = wgrad_rm((dch, dcl), (cih, cil), 2 * C * L, cols)[0][:, :, None]
+            Th, Tl = swt[k]["cond"]
+            rowgemm_h3(Ah=dch, Al=dcl, lda_h=2 * C * L, Bh=Th, Bl=Tl, ldb_h=2 * C * L, acc_scale=inv_gw, nprod=3, C=dci,
+                       ldc=ldk, M=R, N=cols, K=2 * C * L, T=Tg, lens=lens_g, add=dci_prev, ldadd=ldk)
+            dci, dci_prev = (dci_prev if dci_prev is not None else empty(R, ldk)), dci
+            done()
+            done = timed("bwd_mix")
+            out[f"convinv.{k}.conv.weight"] = _outer_reduce(dX[:, col0:], ng, c, snaps[k][:, col0:], ng, c, lens_g, R,
+                                                            Tg)[:, :, None]
+            check(lib.radmmm_wg_mix_fwd(ptr(dX), ng, col0, c, ptr(fk["mix"].t().contiguous()), ptr(lens_g), R, Tg, s),
+                  "wg_mix_fwd")
+            done()
+        done = timed("bwd_upsample")
+        self._upsample_grads(f, dci_prev, xm, lens_d, lens_g, B, T, out)
         done()
         return out
 
@@ -867,35 +1111,48 @@ class WaveGlow(nn.Module):
         return self.training and torch.is_grad_enabled()
 
     @fp32_region
-    def nll_loss(self, mel: torch.Tensor, audio: torch.Tensor, lens=None, sigma: float = 1.0) -> torch.Tensor:
+    def nll_loss(self, mel: torch.Tensor, audio: torch.Tensor, lens=None, sigma: float = 1.0,
+                 precision: Optional[str] = None) -> torch.Tensor:
         """analyze(...)["loss"] as a scalar; in training mode with grad enabled it carries a grad_fn, and backward()
         fills .grad of every parameter (mel and audio get none).  With host lengths the step never waits for the
-        device."""
+        device.  precision: the step's train_precision (None: the attribute); outside a training step the name is
+        checked and the fp32 path runs."""
         if not self._train_active():
+            if precision is not None:
+                self._train_precision(precision)
             return self.analyze(mel, audio, lens, sigma)["loss"]
+        mode = self._train_precision(precision, mel)
         mel, audio = self._args_fwd(mel, audio)
         lens_d, _ = _lens_arg(lens, mel.shape[0], mel.shape[2], mel.device)
-        return _WaveGlowFn.apply(self, mel.detach(), audio.detach(), lens_d, float(sigma), True, *self._weights())
+        return _WaveGlowFn.apply(self, mel.detach(), audio.detach(), lens_d, float(sigma), True, mode, *self._weights())
 
-    def _train_chunk(self, f, Tg: int) -> int:
+    def _train_chunk(self, f, Tg: int, mode: str = "fp32") -> int:
         """items per chunk of a training step: the caps of _chunk_items, the conditioning gradient [rows, 2 C L] as a GEMM
         A operand, and _TRAIN_ACT_BYTES for what the backward of ONE flow holds per row (cond and its gradient, H_i / A_i /
-        acts_i of every layer, the skip / res_skip / gradient rows, the conditioning rows and their two gradient copies)"""
+        acts_i of every layer, the skip / res_skip / gradient rows, the conditioning rows and their two gradient copies).
+        "h3": the fp16 pairs of H_i / acts_i / the conditioning rows take the bytes of the fp32 arrays they replace; the
+        pairs of the conditioning gradient [rows, 2 C L] and of [dH | dS] and the one fp32 H come on top; every pair
+        operand is half its fp32 twin's bytes, so the 2 GiB operand caps above cover radmmm_rowgemm_h3 and
+        radmmm_wgrad_rm, whose 1024 items per launch cap the chunk as well."""
         if self._train_chunk_items:
             return int(self._train_chunk_items)
         wn = self.WN[0]
         C, L = wn.n_channels, wn.n_layers
         per_row = 4 * (8 * C * L + 8 * C + 3 * f["ldk"] + 3 * self.n_group + 8)
+        if mode == "h3":
+            per_row += 4 * (2 * C * L + 3 * C)
         rows_cap = min(_A_OPERAND_BYTES // (8 * C * L), _TRAIN_ACT_BYTES // per_row)
-        return max(1, min(self._chunk_items(f, Tg), rows_cap // Tg))
+        items = max(1, min(self._chunk_items(f, Tg), rows_cap // Tg))
+        return min(items, _WGRAD_RM_ITEMS) if mode == "h3" else items
 
     @fp32_region
     def forward(self, forward_input):
         mel, audio = forward_input
+        mode = self._train_precision(None, mel) if self._train_active() else "fp32"
         mel, audio = self._args_fwd(mel, audio)
         if self._train_active():
             lens_d, _ = _lens_arg(None, mel.shape[0], mel.shape[2], mel.device)
-            out = _WaveGlowFn.apply(self, mel.detach(), audio.detach(), lens_d, 1.0, False, *self._weights())
+            out = _WaveGlowFn.apply(self, mel.detach(), audio.detach(), lens_d, 1.0, False, mode, *self._weights())
             return out[0], list(out[1:-1]), list(out[-1].unbind(0))
         B, _, T = mel.shape
         ng = self.n_group
@@ -963,14 +1220,15 @@ def inv_logdet(mixes) -> Tuple[list, torch.Tensor]:
 
 class _WaveGlowFn(torch.autograd.Function):
     """WaveGlow.forward / nll_loss as one autograd node.  Inputs: the module, mel, audio, lens (device int32, frames),
-    sigma, fused, then the folded weights in WaveGlow._weight_names() order (reference layouts).  fused: the output is the
+    sigma, fused, mode (the step's train_precision), then the folded weights in WaveGlow._weight_names() order (reference
+    layouts).  fused: the output is the
     ragged loss of analyze(); else (z [B, n_group, Tg], log_s per flow [B, n_half_k, Tg], B * Tg * log|det W_k|
     [n_flows] float64).  The forward keeps the rows as they enter each flow (32 bytes per row and flow); the backward
     walks the flows from last to first, recomputes one flow's WN into per-layer buffers and back-propagates through it
     (DESIGN 4.19)."""
 
     @staticmethod
-    def forward(ctx, model, mel, audio, lens_d, sigma, fused, *weights):
+    def forward(ctx, model, mel, audio, lens_d, sigma, fused, mode, *weights):
         B, _, T = mel.shape
         ng = model.n_group
         per = HOP // ng
@@ -979,11 +1237,13 @@ class _WaveGlowFn(torch.autograd.Function):
         W = dict(zip(model._weight_names(), weights))
         invs, logdet = inv_logdet([W[f"convinv.{k}.conv.weight"][:, :, 0] for k in range(model.n_flows)])
         f = model._pack(W, invs, logdet)
-        Bc = model._train_chunk(f, Tg)
+        Bc = model._train_chunk(f, Tg, mode)
         snaps = torch.empty(model.n_flows, B * Tg, ng, device=dev, dtype=torch.float32)
         X, parts, logs = model._analyze_run(mel, audio, lens_d, want_log_s=not fused, events=model._train_events, f=f,
-                                             snaps=snaps, Bc=Bc)
-        ctx.model, ctx.f, ctx.sigma, ctx.fused, ctx.Bc = model, f, sigma, fused, Bc
+                                             snaps=snaps, Bc=Bc, mode=mode)
+        ctx.model, ctx.f, ctx.sigma, ctx.fused, ctx.Bc, ctx.mode = model, f, sigma, fused, Bc, mode
+        if mode == "h3":          # a power of two from the padded sample count alone: no device value is read for it
+            ctx.g_scale = model._g_scale(B * T * HOP)
         ctx.save_for_backward(mel, audio, lens_d, snaps, X)
         if fused:
             n_groups = lens_d.long() * per
@@ -1023,15 +1283,16 @@ class _WaveGlowFn(torch.autograd.Function):
         for b0 in range(0, B, ctx.Bc):                 # a fixed order: the chunks' gradients are added as they come
             b1 = min(B, b0 + ctx.Bc)
             r0, r1 = b0 * Tg, b1 * Tg
-            part = model._backward_chunk(f, mel[b0:b1], lens_d[b0:b1], snaps[:, r0:r1], dX[r0:r1],
-                                         [t if t.shape[0] == 1 else t[r0:r1] for t in g_ls],
-                                         model._train_events if b1 == B else None)
+            args = (f, mel[b0:b1], lens_d[b0:b1], snaps[:, r0:r1], dX[r0:r1],
+                    [t if t.shape[0] == 1 else t[r0:r1] for t in g_ls], model._train_events if b1 == B else None)
+            part = (model._backward_chunk(*args) if ctx.mode == "fp32"
+                    else model._backward_chunk_h3(*args, g_scale=ctx.g_scale))
             total = part if total is None else {n: total[n] + part[n] for n in total}
-        Wn = dict(zip(model._weight_names(), ctx.needs_input_grad[6:]))
+        Wn = dict(zip(model._weight_names(), ctx.needs_input_grad[7:]))
         for k in range(model.n_flows):                 # the log-det terms: d log|det W| / dW = W^-T
             n = f"convinv.{k}.conv.weight"
             total[n] = total[n] + (g_logdet[k] * f["flows"][k]["inv"].t())[:, :, None]
-        return (None,) * 6 + tuple(total[n] if need else None for n, need in Wn.items())
+        return (None,) * 7 + tuple(total[n] if need else None for n, need in Wn.items())
 
 
 class WaveGlowLoss(nn.Module):

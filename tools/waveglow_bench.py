@@ -3,7 +3,8 @@
 
     python tools/waveglow_bench.py [--batch 32] [--frames 800] [--iters 3] [--warmup 1] [--analyze]
                                    [--precision {fp32,h3,f16}]
-    python tools/waveglow_bench.py --train [--batch 32] [--frames 800] [--iters 3] [--warmup 1]
+    python tools/waveglow_bench.py --train [--train-precision {fp32,h3}] [--batch 32] [--frames 800] [--iters 3]
+                                   [--warmup 1]
 
 The shipped config (12 flows, 8 layers, 256 channels, n_group 8, 80 mels), random weights from a seed, every item at
 full length: device milliseconds of WaveGlow.infer (device events around the whole call, median after warm-up), audio
@@ -19,7 +20,10 @@ the in_layers fraction stays relative to the fp32-MFMA peak in every mode, so th
 --train times one training step instead, WaveGlow.nll_loss + backward in training mode with weight norm applied, at the
 reference's training shape (batch 12, segments of 16000 samples = 62 frames) and at --batch / --frames: device
 milliseconds per step, the ratio to analyze at the same shape in the same run, and the step's launch families (the
-forward's, and bwd_* for the backward: bwd_recompute is the WN run again per flow; the last chunk of items only)."""
+forward's, and bwd_* for the backward: bwd_recompute is the WN run again per flow; the last chunk of items only).
+--train-precision h3 runs the step under WaveGlow.train_precision "h3" (the three WN GEMM families of every pass on the
+f16 matrix cores, three products; the same families are timed, plus split_cond) and reports grad_saturated() after the
+timed steps; compare it with an fp32 run of the same session."""
 import argparse
 import json
 import os
@@ -73,6 +77,7 @@ def timed_ms(fn, iters, warmup):
 def train_bench(model, args, dev):
     from rad_mmm_amd.waveglow import HOP
     model.apply_weight_norm()
+    model.train_precision = args.train_precision
     shapes = []
     for B, T in ((12, 62), (args.batch, args.frames)):
         mel = (torch.randn(B, 80, T, generator=torch.Generator().manual_seed(6)) - 2.0).to(dev)
@@ -98,7 +103,8 @@ def train_bench(model, args, dev):
                        "last_chunk_rows": rows_chunk, "last_chunk_family_ms": fam,
                        "peak_memory_gib": torch.cuda.max_memory_allocated() / 2 ** 30})
         torch.cuda.reset_peak_memory_stats()
-    print(json.dumps({"metric": "waveglow_train_step_ms", "shapes": shapes}))
+    print(json.dumps({"metric": "waveglow_train_step_ms", "train_precision": args.train_precision,
+                      "grad_saturated": model.grad_saturated(), "shapes": shapes}))
 
 
 @torch.no_grad()
@@ -112,6 +118,8 @@ def main():
     ap.add_argument("--analyze", action="store_true", help="also time WaveGlow.analyze (audio -> latent) at the same shape")
     ap.add_argument("--train", action="store_true", help="time one training step (nll_loss + backward) instead")
     ap.add_argument("--precision", choices=("fp32", "h3", "f16"), default="fp32", help="WaveGlow.precision of infer")
+    ap.add_argument("--train-precision", choices=("fp32", "h3"), default="fp32",
+                    help="WaveGlow.train_precision of the --train step")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("waveglow_bench needs an MI355X")

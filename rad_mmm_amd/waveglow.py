@@ -396,16 +396,20 @@ class WaveGlow(nn.Module):
             out.append(f32c(z.to(dev)))
         return out
 
+    def _check_f16_gemm_k(self, what: str) -> None:
+        """the shapes a 16-bit mode needs: K % 32 of the three GEMM families; `what` names the mode in the message"""
+        C, K = self.WN[0].n_channels, self.n_mel_channels * self.n_group
+        if C % 32 or K % 32:
+            raise ValueError(f"{what} needs n_channels % 32 == 0 and (n_mel_channels * n_group) % 32 == 0 "
+                             f"(the f16 GEMM's K % 32 == 0); got n_channels {C}, n_mel_channels * n_group {K}")
+
     def _precision(self, precision: Optional[str] = None) -> str:
         """the mode of a call (None: the attribute), checked: a known name, and for the 16-bit modes the GEMM's K % 32"""
         mode = self.precision if precision is None else precision
         if mode not in PRECISIONS:
             raise ValueError(f"precision {mode!r}: one of {PRECISIONS}")
         if mode != "fp32":
-            C, K = self.WN[0].n_channels, self.n_mel_channels * self.n_group
-            if C % 32 or K % 32:
-                raise ValueError(f"precision {mode!r} needs n_channels % 32 == 0 and (n_mel_channels * n_group) % 32 == 0 "
-                                 f"(the f16 GEMM's K % 32 == 0); got n_channels {C}, n_mel_channels * n_group {K}")
+            self._check_f16_gemm_k(f"precision {mode!r}")
         return mode
 
     def _train_precision(self, precision: Optional[str] = None, mel: Optional[torch.Tensor] = None) -> str:
@@ -417,10 +421,7 @@ class WaveGlow(nn.Module):
             raise ValueError(f"train_precision {mode!r}: one of {TRAIN_PRECISIONS}"
                              + (" (one-product \"f16\" training is not built)" if mode == "f16" else ""))
         if mode == "h3":
-            C, K = self.WN[0].n_channels, self.n_mel_channels * self.n_group
-            if C % 32 or K % 32:
-                raise ValueError(f"train_precision 'h3' needs n_channels % 32 == 0 and (n_mel_channels * n_group) % 32 == 0 "
-                                 f"(the f16 GEMM's K % 32 == 0); got n_channels {C}, n_mel_channels * n_group {K}")
+            self._check_f16_gemm_k("train_precision 'h3'")
             self._g_scale(1)
             if mel is not None and mel.dim() == 3:
                 Tg = mel.shape[2] * (HOP // self.n_group)

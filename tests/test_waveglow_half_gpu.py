@@ -348,6 +348,24 @@ def test_fp32_is_the_default_path(tiny):
     assert torch.equal(m.infer(tiny["mel"], tiny["lens"], precision=None, **kw), plain)
 
 
+@pytest.mark.parametrize("mode", ("fp32",) + MODES)
+def test_infer_event_families(tiny, mode):
+    """the per-family device event lists tools/waveglow_bench.py reads, which also witness the launch structure: one
+    (start, end) pair per bracketed launch family and flow / layer, counted from the config (one chunk)"""
+    m, cfg = tiny["model"], tiny["cfg"]
+    F, L = cfg["n_flows"], cfg["WN_config"]["n_layers"]
+    B, _, T = tiny["mel"].shape
+    events = {}
+    m._run(tiny["mel"], torch.tensor(tiny["lens"], dtype=torch.int32, device=DEV), tiny["sigma"], tiny["noise"], events,
+           precision=mode)
+    assert events.pop("rows") == B * T * HOP // cfg["n_group"]
+    want = {"upsample": 1, "start": F, "cond_layer": F, "in_layers": F * L, "gate": F * L, "res_skip_gemm": F * L,
+            "res_skip_update": F * L, "end_coupling": F, "ungroup": 1}
+    if mode != "fp32":
+        want["split_cond"] = 1                          # one split pass over the conditioning rows for all flows
+    assert {k: len(v) for k, v in events.items()} == want
+
+
 def test_split_weights_are_cached_with_the_fold(tiny):
     m = tiny["model"]
     _infer(tiny, "h3")

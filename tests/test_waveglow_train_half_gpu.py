@@ -432,6 +432,28 @@ def test_the_mode_is_really_taken(tiny, ragged):
     assert torch.equal(lossh, loss) and _same_bits(gradsh, grads)
 
 
+@pytest.mark.parametrize("mode", ["fp32", "h3"])
+def test_train_step_event_families(tiny, mode):
+    """the per-family device event lists of one step (tools/waveglow_bench.py --train reads them), counted from the
+    config: the forward's families once per flow / layer (the recomputation is not timed by family), the backward's
+    bwd_* families, the conditioning in both passes (one chunk)"""
+    cfg, m, mel, audio = tiny[2], tiny[4], tiny[5], tiny[6]
+    F, L = cfg["n_flows"], cfg["WN_config"]["n_layers"]
+    m._train_events = events = {}
+    try:
+        _step(m, mel, audio, precision=mode)
+    finally:
+        m._train_events = None
+    assert events.pop("rows") == mel.shape[0] * mel.shape[2] * HOP // cfg["n_group"]
+    want = {"upsample": 2, "group_audio": 1, "mix_fwd": F, "start": F, "cond_layer": F, "in_layers": F * L, "gate": F * L,
+            "res_skip_gemm": F * L, "res_skip_update": F * L, "end_coupling_fwd": F, "nll_parts": 1,
+            "bwd_recompute": F, "bwd_coupling": F, "bwd_start": F, "bwd_cond_layer": F, "bwd_mix": F,
+            "bwd_res_skip": F * L, "bwd_gate": F * L, "bwd_in_layers": F * L, "bwd_upsample": 1}
+    if mode == "h3":
+        want["split_cond"] = 2                          # the conditioning rows are split in the forward and in the backward
+    assert {k: len(v) for k, v in events.items()} == want
+
+
 def test_h3_chunked_step(tiny, ragged):
     m = tiny[4]
     mel, audio, loss, grads, _, _ = ragged

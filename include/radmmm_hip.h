@@ -52,6 +52,12 @@ enum { RADMMM_SCALE_TANH = 0, RADMMM_SCALE_EXP = 1, RADMMM_SCALE_SIGMOID = 2, RA
  *   RADMMM_SPLIT_X8B  the same with the two 32-byte halves swapped [ lo8 | hi8 ]                     (B role, weights)
  * e4m3 = OCP FP8 E4M3, round to nearest even, saturated at +-448.  A block-scaled FP8 MFMA of an X8A fragment with an
  * X8B fragment yields Ah.Bl + Al.Bh (radmmm_rowgemm_h3 with nprod = 2).
+ * Non-finite inputs: +-Inf is clamped like any large value (+-60000, flag bit 0, and bit 1 with level 6 in an 8-bit format).
+ * NaN is NOT propagated and NOT reported: the clamp (v_med3_f32) turns it into -60000, so every store path -- the 4-wide and
+ * the 1-wide store of csrc/split_pack.h and the GEMM epilogues' pair store -- writes hi = 0xfb53 (-60000), lo = 0,
+ * hi8 = 0xfe (-448), lo8 = 0, and raises no flag bit (the flag's amax ignores NaN, as fmaxf does).  A caller that must see
+ * a NaN again passes it on by other means (radmmm_weightnorm_bwd's `poison`).  tests/_split_ref.py is the host model of
+ * these formats; tests/test_hip_split_direct.py holds the producers to it bit for bit.
  * ------------------------------------------------------------------------------------ */
 #define RADMMM_SPLIT_F16 0
 #define RADMMM_SPLIT_X8A 1

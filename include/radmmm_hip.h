@@ -183,6 +183,19 @@ typedef struct {
 
 int radmmm_rowgemm_h3(const radmmm_rowgemm_h3_desc* d, radmmm_stream_t stream);
 int64_t radmmm_rowgemm_h3_colsum_scratch_floats(int M, int N);
+/* Additive entry point of ABI 4, read-only: which kernel the calling thread's last radmmm_rowgemm_h3 launch took, as
+ * RADMMM_H3_KERNEL_CODE(family, products, mb, epilogue kind); 0 = no launch yet on this thread.  family: the 128 x 128
+ * kernel (NARROW; mb reads 4, the kind 0), the per-tap wide kernel rowgemm_h3d, the shared-window kernel rowgemm_win or
+ * the one-tap kernel rowgemm_one.  products: 1, 2 or 3 (nprod 0 reads as 3).  mb: tile height / 32 (4 .. 8).  kind: 0 the
+ * generic LDS-parking epilogue, 1 PLAIN (C), 2 SPLIT (C + Ch / Cl), 3 RES (C + C2), 4 DGRAD (C + split copy, times act').
+ * It is recorded where the launch decision is made (one thread-local store on the host per launch), also when the launch
+ * itself then fails.  Tests use it to make sure a shape reached the kernel they mean to test. */
+#define RADMMM_H3_FAMILY_NARROW 1
+#define RADMMM_H3_FAMILY_H3D 2
+#define RADMMM_H3_FAMILY_WIN 3
+#define RADMMM_H3_FAMILY_ONE 4
+#define RADMMM_H3_KERNEL_CODE(family, nprod, mb, ek) ((family) * 1000 + (nprod) * 100 + (mb) * 10 + (ek))
+int radmmm_rowgemm_h3_last_kernel(void);
 /* Deferred column sums (ABI 3): a launch with colsum_scratch set and colsum_out == NULL leaves its per-row-tile partial rows
  * in colsum_scratch ([rows][N] floats, rows = the value returned here) and the caller adds them up later -- several launches'
  * finals in one radmmm_colsum_final_multi call.  Returns 0 when this descriptor would take a kernel that cannot leave

@@ -195,6 +195,7 @@ def _load() -> C.CDLL:
         "radmmm_ctc_monotonic": [p, p, p, p, p, p, i, i, i, p],
         "radmmm_lstm_bwd": [p, p, p, p, p, p, p, p, i, i, i, p, p],
         "radmmm_lstm_last_path": [i],
+        "radmmm_rowgemm_h3_last_kernel": [],
         "radmmm_wgrad_h3": [p, p, p, p, p, p, i, i, i, p, i, i64, i, i, i, i, i, f, i, p],
         "radmmm_weightnorm_fwd_h3": [p, p, p, p, p, i, i, i, i, i, i, i, f, so, p],
         "radmmm_transpose_f16_pair": [p, p, i, i64, p, p, i, i64, i, i, i, i, i, p],
@@ -328,6 +329,20 @@ def rowgemm_h3(**kw) -> None:
         LAUNCH_EVENTS.append((e0, e1))
         return
     _rowgemm_h3(kw)
+
+
+H3_NARROW, H3_H3D, H3_WIN, H3_ONE = 1, 2, 3, 4
+EK_GENERIC, EK_PLAIN, EK_SPLIT, EK_RES, EK_DGRAD = 0, 1, 2, 3, 4
+
+
+def h3_kernel_code(family: int, nprod: int, mb: int, ek: int) -> int:
+    """RADMMM_H3_KERNEL_CODE of include/radmmm_hip.h"""
+    return family * 1000 + nprod * 100 + mb * 10 + ek
+
+
+def rowgemm_h3_last_kernel() -> int:
+    """which kernel this thread's last rowgemm_h3 launch took (radmmm_rowgemm_h3_last_kernel; 0: none yet)"""
+    return int(lib.radmmm_rowgemm_h3_last_kernel())
 
 
 def rowgemm_h3_colsum_rows(**kw) -> int:

@@ -21,6 +21,8 @@ int launch_wgrad16(const radmmm_wgrad_desc& d, hipStream_t stream);
 // rowgemm_h3w.hip: wide-tile (32*MB x 256, one workgroup per CU) split-f16 conv GEMM
 int launch_rowgemm_h3w(const radmmm_rowgemm_h3_desc& d, hipStream_t stream, int a_bytes, int b_bytes);
 int gemm_cu_slots();
+// the kernel the calling thread's last radmmm_rowgemm_h3 launch took (radmmm_rowgemm_h3_last_kernel; error.cpp)
+extern thread_local int g_h3_last_kernel;
 
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();

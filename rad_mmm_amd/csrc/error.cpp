@@ -7,6 +7,7 @@
 
 namespace radmmm {
 static thread_local char g_err[512] = "";
+thread_local int g_h3_last_kernel = 0;
 void set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -28,3 +29,4 @@ const char* debug_env(const char* name) {
 
 extern "C" const char* radmmm_last_error(void) { return radmmm::g_err; }
 extern "C" int radmmm_abi_version(void) { return RADMMM_ABI_VERSION; }
+extern "C" int radmmm_rowgemm_h3_last_kernel(void) { return radmmm::g_h3_last_kernel; }

@@ -251,6 +251,7 @@ extern "C" int radmmm_rowgemm_h3(const radmmm_rowgemm_h3_desc* d, radmmm_stream_
     return 0;
   }();
   if (once) return once;
+  radmmm::g_h3_last_kernel = RADMMM_H3_KERNEL_CODE(RADMMM_H3_FAMILY_NARROW, d->nprod == 1 ? 1 : 3, BM / 32, 0);
   const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
   // nprod 1 must not touch Al / Bl: a caller without lo halves passes the hi arrays for both pointers
   if (d->nprod == 1)

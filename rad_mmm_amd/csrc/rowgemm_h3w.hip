@@ -149,23 +149,43 @@ static int launch_rowgemm_h3w_inner(const radmmm_rowgemm_h3_desc& d, hipStream_t
   decide_h3w(d, &mb, &ek);
   *mb_out = mb;
   *ek_out = ek;
+  // (every branch records family / products / tile height / epilogue kind for radmmm_rowgemm_h3_last_kernel)
+  const int np = d.nprod == 0 ? 3 : d.nprod;
+  auto note = [&](int family) { g_h3_last_kernel = RADMMM_H3_KERNEL_CODE(family, np, mb, ek); };
   if (d.nprod == 2) {                                                                 // FP8 cross terms
     const char* we = debug_env("RADMMM_WIN");         // RADMMM_DEBUG: RADMMM_WIN=0 keeps the per-tap A tiles (A/B runs, tests)
     const char* wx = debug_env("RADMMM_WIN_XT");      // RADMMM_DEBUG: 0 = launches with the extra K segment keep rowgemm_h3d (A/B runs)
     const bool xt_ok = !d.extra_tap || !(wx && atoi(wx) == 0);
-    if (!(we && atoi(we) == 0) && xt_ok && rowgemm_win_ok(mb, ek, d)) return launch_rowgemm_win(mb, ek, d, stream, a_bytes, b_bytes);
+    if (!(we && atoi(we) == 0) && xt_ok && rowgemm_win_ok(mb, ek, d)) {
+      note(RADMMM_H3_FAMILY_WIN);
+      return launch_rowgemm_win(mb, ek, d, stream, a_bytes, b_bytes);
+    }
     const char* oe = debug_env("RADMMM_ONE");         // RADMMM_DEBUG: RADMMM_ONE=0 keeps rowgemm_h3d for the 1-tap launches (A/B runs, tests)
-    if (!(oe && atoi(oe) == 0) && rowgemm_one_ok(mb, ek, d)) return launch_rowgemm_one(mb, ek, d, stream, a_bytes, b_bytes);
+    if (!(oe && atoi(oe) == 0) && rowgemm_one_ok(mb, ek, d)) {
+      note(RADMMM_H3_FAMILY_ONE);
+      return launch_rowgemm_one(mb, ek, d, stream, a_bytes, b_bytes);
+    }
+    note(RADMMM_H3_FAMILY_H3D);
     return launch_h3d_pr2(mb, ek, d, stream, a_bytes, b_bytes);
   }
-  if (d.nprod == 1) return launch_h3d_pr1(mb, ek, d, stream, a_bytes, b_bytes);       // 16-bit throughput mode
+  if (d.nprod == 1) {                                                                 // 16-bit throughput mode
+    note(RADMMM_H3_FAMILY_H3D);
+    return launch_h3d_pr1(mb, ek, d, stream, a_bytes, b_bytes);
+  }
   {                                                                                   // three f16 products
     const char* s3 = debug_env("RADMMM_SLOT3");       // RADMMM_DEBUG: RADMMM_SLOT3=0 keeps rowgemm_h3d for every three-product launch (A/B, tests)
     if (!(s3 && atoi(s3) == 0)) {
-      if (rowgemm_win_ok(mb, ek, d)) return launch_rowgemm_win(mb, ek, d, stream, a_bytes, b_bytes);
-      if (rowgemm_one_ok(mb, ek, d)) return launch_rowgemm_one(mb, ek, d, stream, a_bytes, b_bytes);
+      if (rowgemm_win_ok(mb, ek, d)) {
+        note(RADMMM_H3_FAMILY_WIN);
+        return launch_rowgemm_win(mb, ek, d, stream, a_bytes, b_bytes);
+      }
+      if (rowgemm_one_ok(mb, ek, d)) {
+        note(RADMMM_H3_FAMILY_ONE);
+        return launch_rowgemm_one(mb, ek, d, stream, a_bytes, b_bytes);
+      }
     }
   }
+  note(RADMMM_H3_FAMILY_H3D);
   return launch_h3d_pr3(mb, ek, d, stream, a_bytes, b_bytes);
 }
 

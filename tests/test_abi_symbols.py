@@ -72,6 +72,35 @@ def test_lstm_entry_points_validate_without_gpu():
     assert [lib.radmmm_lstm_last_path(w) for w in (0, 1, 2, -1)] == [0, 0, 0, 0]
 
 
+def test_rowgemm_h3_kernel_query_without_gpu():
+    """radmmm_rowgemm_h3_last_kernel is thread-local and reports 0 until a launch decision was made on the calling thread:
+    a refused descriptor (validation comes before any HIP call) leaves it alone.  The code's fields are the header's macro."""
+    import threading
+    import rad_mmm_amd._lib as L
+    lib = ctypes.CDLL(LIB)
+    lib.radmmm_last_error.restype = ctypes.c_char_p
+    lib.radmmm_rowgemm_h3_last_kernel.restype = ctypes.c_int
+    seen = []
+
+    def fresh_thread():
+        seen.append(lib.radmmm_rowgemm_h3_last_kernel())
+        seen.append(lib.radmmm_rowgemm_h3(None, None))
+        seen.append(lib.radmmm_last_error())
+        d = L.RowGemmH3Desc()                                     # null operands: refused before any kernel is chosen
+        seen.append(lib.radmmm_rowgemm_h3(ctypes.byref(d), None))
+        seen.append(lib.radmmm_rowgemm_h3_last_kernel())
+
+    t = threading.Thread(target=fresh_thread)
+    t.start()
+    t.join()
+    assert seen[0] == 0 and seen[1] == -1 and b"null descriptor" in seen[2] and seen[3] == -1 and seen[4] == 0
+    hdr = open(HDR).read()
+    assert "#define RADMMM_H3_KERNEL_CODE(family, nprod, mb, ek) ((family) * 1000 + (nprod) * 100 + (mb) * 10 + (ek))" in hdr
+    for name, val in (("NARROW", L.H3_NARROW), ("H3D", L.H3_H3D), ("WIN", L.H3_WIN), ("ONE", L.H3_ONE)):
+        assert re.search(rf"#define RADMMM_H3_FAMILY_{name} {val}\b", hdr)
+    assert L.h3_kernel_code(L.H3_WIN, 2, 7, L.EK_DGRAD) == 3274
+
+
 def test_python_binding_matches_struct_layout():
     import rad_mmm_amd._lib as L
     # field order/size of the ctypes mirrors == the C structs (checked via a tiny C probe is not

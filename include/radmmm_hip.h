@@ -226,6 +226,22 @@ typedef struct {
 
 int radmmm_wgrad_f32(const radmmm_wgrad_desc* d, radmmm_stream_t stream);
 
+/* Additive entry points of ABI 4, host only: which kernel radmmm_rowgemm_f32 / radmmm_wgrad_f32 would launch for a descriptor,
+ * as RADMMM_F32_KERNEL_CODE(family, b_layout, mt, rows); < 0: the descriptor would be refused (same code and
+ * radmmm_last_error text as the entry point, whose validation they share).  mt and rows are the tile height / 16 and the rows
+ * per tile of the 16-row kernel, 0 for every other family; b_layout is 0 for the weight gradients.  They make no HIP call and
+ * dereference no operand pointer (the pointers' alignment and presence is all they look at), so they answer on a machine
+ * without a GPU; the entry points take their decision from the same function.  Tests use them to make sure a shape reaches
+ * the kernel they mean to test. */
+#define RADMMM_F32_FAMILY_GENERIC 1   /* rowgemm_f32_kernel<bl> */
+#define RADMMM_F32_FAMILY_ROWS16  2   /* rowgemm16_kernel<mt, bl> */
+#define RADMMM_F32_FAMILY_MIX     3   /* rowgemm_mix_kernel<bl> */
+#define RADMMM_F32_FAMILY_WGRAD   4   /* wgrad_f32_kernel */
+#define RADMMM_F32_FAMILY_WGRAD16 5   /* wgrad16_kernel */
+#define RADMMM_F32_KERNEL_CODE(family, bl, mt, rows) ((family) * 1000000 + (bl) * 100000 + (mt) * 1000 + (rows))
+int radmmm_rowgemm_f32_plan(const radmmm_rowgemm_desc* d);  /* <0: the descriptor would be refused */
+int radmmm_wgrad_f32_plan(const radmmm_wgrad_desc* d);
+
 /* ------------------------------------------------------------------------------------
  * Weight norm fold / unfold  (torch weight_norm dim=0; common.py:173-174,791,813)
  *   forward : W[tap][co][col(ci)] = g[co] * v[co][ci][tap] / ||v[co]||_2 ,

@@ -196,6 +196,7 @@ def _load() -> C.CDLL:
         "radmmm_lstm_bwd": [p, p, p, p, p, p, p, p, i, i, i, p, p],
         "radmmm_lstm_last_path": [i],
         "radmmm_rowgemm_h3_last_kernel": [],
+        "radmmm_rowgemm_f32_plan": [C.POINTER(RowGemmDesc)], "radmmm_wgrad_f32_plan": [C.POINTER(WgradDesc)],
         "radmmm_wgrad_h3": [p, p, p, p, p, p, i, i, i, p, i, i64, i, i, i, i, i, f, i, p],
         "radmmm_weightnorm_fwd_h3": [p, p, p, p, p, i, i, i, i, i, i, i, f, so, p],
         "radmmm_transpose_f16_pair": [p, p, i, i64, p, p, i, i64, i, i, i, i, i, p],
@@ -295,7 +296,7 @@ def f32c(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
-def rowgemm(**kw) -> None:
+def _rowgemm_desc(kw, addr=ptr) -> RowGemmDesc:
     d = RowGemmDesc()
     d.sign = 1
     d.taps = 1
@@ -303,10 +304,48 @@ def rowgemm(**kw) -> None:
     d.ratio_taps = 1
     d.ratio_dil = 1
     for k, v in kw.items():
+        if k == "c2_src":                               # list of 1 .. 3 fp32 tensors (radmmm_rowgemm_desc.c2_src / n_c2_src)
+            d.c2_src = (C.c_void_p * 3)(*[addr(t) for t in v], *([None] * (3 - len(v))))
+            d.n_c2_src = len(v)
+            continue
         if isinstance(v, torch.Tensor):
-            v = ptr(v)
+            v = addr(v)
         setattr(d, k, v)
-    check(lib.radmmm_rowgemm_f32(C.byref(d), stream()), "radmmm_rowgemm_f32")
+    return d
+
+
+def rowgemm(**kw) -> None:
+    check(lib.radmmm_rowgemm_f32(C.byref(_rowgemm_desc(kw)), stream()), "radmmm_rowgemm_f32")
+
+
+F32_GENERIC, F32_ROWS16, F32_MIX, F32_WGRAD, F32_WGRAD16 = 1, 2, 3, 4, 5
+
+
+def f32_kernel_code(family: int, bl: int = 0, mt: int = 0, rows: int = 0) -> int:
+    """RADMMM_F32_KERNEL_CODE of include/radmmm_hip.h"""
+    return family * 1000000 + bl * 100000 + mt * 1000 + rows
+
+
+def _addr(t: Optional[torch.Tensor]) -> Optional[int]:
+    """address of a tensor on any device: the plan queries look at presence and alignment only, never at the memory"""
+    return None if t is None else t.data_ptr()
+
+
+def rowgemm_plan(**kw) -> int:
+    """which kernel rowgemm(**kw) would launch (radmmm_rowgemm_f32_plan): host only, the tensors may live anywhere, and an
+    integer stands for an address.  Raises on a descriptor the entry point would refuse."""
+    rc = int(lib.radmmm_rowgemm_f32_plan(C.byref(_rowgemm_desc(kw, _addr))))
+    if rc < 0:
+        check(rc, "radmmm_rowgemm_f32_plan")
+    return rc
+
+
+def wgrad_plan(**kw) -> int:
+    """which kernel wgrad(**kw) would launch (radmmm_wgrad_f32_plan); see rowgemm_plan"""
+    rc = int(lib.radmmm_wgrad_f32_plan(C.byref(_wgrad_desc(kw, _addr))))
+    if rc < 0:
+        check(rc, "radmmm_wgrad_f32_plan")
+    return rc
 
 
 _H3_KEYS = {"Ah", "Al", "lda_h", "Bh", "Bl", "ldb_h", "b_tap_stride_h", "acc_scale", "nprod", "a8_exp", "b8_exp", "extra_tap",
@@ -373,16 +412,20 @@ def _h3_desc(kw):
     return d
 
 
-def wgrad(**kw) -> None:
+def _wgrad_desc(kw, addr=ptr) -> WgradDesc:
     d = WgradDesc()
     d.taps = 1
     d.dil = 1
     d.splits = 1
     for k, v in kw.items():
         if isinstance(v, torch.Tensor):
-            v = ptr(v)
+            v = addr(v)
         setattr(d, k, v)
-    check(lib.radmmm_wgrad_f32(C.byref(d), stream()), "radmmm_wgrad_f32")
+    return d
+
+
+def wgrad(**kw) -> None:
+    check(lib.radmmm_wgrad_f32(C.byref(_wgrad_desc(kw)), stream()), "radmmm_wgrad_f32")
 
 
 # Every custom autograd Function of this package computes in fp32 through raw pointers: under torch.autocast

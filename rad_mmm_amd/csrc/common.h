@@ -12,11 +12,23 @@ void set_error(const char* fmt, ...);
 // value of an experiment / test switch, or nullptr unless RADMMM_DEBUG=1 (error.cpp)
 const char* debug_env(const char* name);
 
-// rowgemm16_f32.hip: 16-row-granular tiling of radmmm_rowgemm_f32 (descriptor already validated)
-int launch_rowgemm16(const radmmm_rowgemm_desc& d, hipStream_t stream);
-int launch_rowgemm_mix(const radmmm_rowgemm_desc& d, hipStream_t stream);   // rowgemm_mix.hip: 0 launched, 1 not its shape
-// wgrad16_f32.hip: fast path of radmmm_wgrad_f32 (0 launched, <0 error, 1 not applicable)
-int launch_wgrad16(const radmmm_wgrad_desc& d, hipStream_t stream);
+// The fp32 GEMM family (radmmm_rowgemm_f32 / radmmm_wgrad_f32): ONE host decision, gemm_f32.hip plan_rowgemm_f32 /
+// plan_wgrad_f32 (validation, kernel family, tiling, buffer extents; no HIP call).  The entry points launch what it says and
+// radmmm_rowgemm_f32_plan / radmmm_wgrad_f32_plan report it.
+struct f32_plan {
+  int family;            // RADMMM_F32_FAMILY_*
+  int bl;                // b_layout (row GEMMs)
+  int mt, rows, nmt;     // 16-row kernel: tile height / 16, rows per tile, number of row tiles; 0 otherwise
+  int ntn;               // column tiles of 128 (row GEMMs)
+  int a_bytes, b_bytes;  // byte extents of the buffer descriptors (A / B of rowgemm16, GY / X of wgrad16)
+};
+constexpr int kMixNK = 160;       // the channel mix kernel's N = K (rowgemm_mix.hip)
+constexpr int kWgrad16BK = 16;    // frames per K step of wgrad16 (wgrad16_f32.hip)
+int plan_rowgemm_f32(const radmmm_rowgemm_desc* d, f32_plan* pl);   // 0, or < 0 with the error string set
+int plan_wgrad_f32(const radmmm_wgrad_desc* d, f32_plan* pl);
+int launch_rowgemm16(const radmmm_rowgemm_desc& d, const f32_plan& pl, hipStream_t stream);    // rowgemm16_f32.hip
+int launch_rowgemm_mix(const radmmm_rowgemm_desc& d, const f32_plan& pl, hipStream_t stream);  // rowgemm_mix.hip
+int launch_wgrad16(const radmmm_wgrad_desc& d, const f32_plan& pl, hipStream_t stream);        // wgrad16_f32.hip
 
 // rowgemm_h3w.hip: wide-tile (32*MB x 256, one workgroup per CU) split-f16 conv GEMM
 int launch_rowgemm_h3w(const radmmm_rowgemm_h3_desc& d, hipStream_t stream, int a_bytes, int b_bytes);

@@ -350,7 +350,12 @@ int ensure_smem(K kernel) {
 
 }  // namespace
 
-extern "C" int radmmm_rowgemm_f32(const radmmm_rowgemm_desc* d, radmmm_stream_t stream) {
+// ------------------------------------------------------------------------------------
+// The one decision of the fp32 family: descriptor validation, then which kernel a descriptor takes and with which
+// tiling and buffer extents.  Host only -- no HIP call, no operand pointer dereferenced -- so radmmm_rowgemm_f32_plan /
+// radmmm_wgrad_f32_plan answer on a machine without a GPU, and the entry points switch on the same result.
+// ------------------------------------------------------------------------------------
+int radmmm::plan_rowgemm_f32(const radmmm_rowgemm_desc* d, radmmm::f32_plan* pl) {
   RADMMM_REQUIRE(d != nullptr, "rowgemm: null descriptor");
   RADMMM_REQUIRE(d->A && d->B && d->C, "rowgemm: null operand");
   RADMMM_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0 && d->taps >= 1 && d->T > 0, "rowgemm: bad dims M=%d N=%d K=%d taps=%d T=%d", d->M, d->N, d->K, d->taps, d->T);
@@ -367,36 +372,101 @@ extern "C" int radmmm_rowgemm_f32(const radmmm_rowgemm_desc* d, radmmm_stream_t 
   RADMMM_REQUIRE(d->sign == 1 || d->sign == -1, "rowgemm: sign must be +-1");
   RADMMM_REQUIRE(!(d->pconv || d->rowscale == 2) || (d->ratio_taps >= 1 && d->ratio_dil >= 1), "rowgemm: ratio_taps/ratio_dil required with pconv/rowscale=2");
   RADMMM_REQUIRE(!d->dact || d->dact_src, "rowgemm: dact needs dact_src");
-  {
-    // the flow steps' 160 x 160 channel mix and its data gradient: the whole weight in LDS, no barrier in the K loop
-    // (rowgemm_mix.hip)
-    const int rc = radmmm::launch_rowgemm_mix(*d, static_cast<hipStream_t>(stream));
-    if (rc <= 0) return rc;
+  *pl = radmmm::f32_plan{};
+  pl->bl = d->b_layout;
+  pl->ntn = (d->N + BN - 1) / BN;
+
+  // (1) the flow steps' 160 x 160 channel mix and its data gradient: the whole weight in LDS, no barrier in the K loop
+  // (rowgemm_mix.hip).  Scope: N == K == 160, one tap, no mask / ratio / activation / add / second output / split copy;
+  // bias optional.  RADMMM_MIX=0 (RADMMM_DEBUG) disables it (A/B runs).
+  static const bool mix_off = [] {
+    const char* e = radmmm::debug_env("RADMMM_MIX");
+    return e && e[0] == '0';
+  }();
+  constexpr int NK = radmmm::kMixNK;
+  if (!mix_off && d->N == NK && d->K == NK && d->taps == 1 && d->a_item_stride == 0 && !d->a_mask_mode && !d->pconv && !d->premask &&
+      !d->postmask && !d->add && !d->dact && !d->rowscale && d->act == RADMMM_ACT_NONE && !d->C2 && !d->Ch && !d->C2h &&
+      !d->colsum_out && !d->n_c2_src && d->ldc % 4 == 0 && d->lda >= NK && d->ldb >= NK && d->ldc >= NK &&
+      radmmm::aligned16(d->C)) {
+    pl->family = RADMMM_F32_FAMILY_MIX;
+    return 0;
   }
+
+  // (2) 16-row-granular tiling with a VALU-free K loop (rowgemm16_f32.hip): needs K % 16 == 0 and operands < 2 GiB.
+  // RADMMM_ROWGEMM_TILE=32 (RADMMM_DEBUG) forces the generic kernels.
   static const bool use32 = [] {
     const char* e = radmmm::debug_env("RADMMM_ROWGEMM_TILE");
     return e && atoi(e) == 32;
   }();
   if (!use32 && d->K % 16 == 0) {
-    // fast path: 16-row-granular tiling with a VALU-free K loop (needs K % 16 == 0, operands < 2 GiB)
-    const int rc = radmmm::launch_rowgemm16(*d, static_cast<hipStream_t>(stream));
-    if (rc <= 0) return rc;
+    // tiling choice: minimise (rounds of 512 workgroup slots) x (MFMA rows per workgroup + fixed per-step overhead),
+    // i.e. the modelled time of the busiest CU
+    static const int kMT[] = {4, 6, 8, 10, 12, 13, 14, 15};
+    const int ntn = pl->ntn;
+    const int slots = 512;
+    double best_cost = 1e300;
+    int best_mt = 15, best_rows = 240, best_nmt = (d->M + 239) / 240;
+    for (int mt : kMT) {
+      const int cap = mt * 16;
+      const int nmt_min = (d->M + cap - 1) / cap;
+      // try the minimal tile count for this MT and the next few counts that complete a round
+      for (int extra = 0; extra < 3; ++extra) {
+        int nmt = nmt_min;
+        if (extra) {
+          const long long wg = (long long)nmt_min * ntn;
+          const long long rounds = (wg + slots - 1) / slots + (extra - 1);
+          nmt = (int)((rounds * slots) / ntn);
+          if (nmt < nmt_min) continue;
+        }
+        if (nmt > d->M) nmt = d->M;
+        const int rows = (d->M + nmt - 1) / nmt;
+        if (rows > cap) continue;
+        nmt = (d->M + rows - 1) / rows;
+        const long long wg = (long long)nmt * ntn;
+        const double rounds = (double)((wg + slots - 1) / slots);
+        // a partially filled single round costs the same as a full one for the busiest CU, but
+        // with < 256 workgroups only one workgroup runs per CU (no sharing of the MFMA pipe)
+        const double share = wg <= 256 ? 0.6 : 1.0;
+        const double cost = rounds * share * (mt + 1.5);
+        if (cost < best_cost - 1e-9) {
+          best_cost = cost;
+          best_mt = mt;
+          best_rows = rows;
+          best_nmt = nmt;
+        }
+      }
+    }
+    // byte extents of the operands for the buffer descriptors
+    // With a_item_stride and a_mask_mode 1 an item may hold more frames than the T that are written (lens[b] > T: the
+    // inverse STFT reads F = T + 1 frames per item), so a tap of the LAST item may reach taps/2 * dil frames past T - 1;
+    // the descriptor must span them, or that item reads zeros there while every other item reads the frames.  lens lives
+    // on the device, so the launcher cannot tell whether the last item is that long and always spans the reach; the
+    // kernel still masks every frame at or above lens[b], so the wider extent admits only frames the caller holds.
+    const long long items = d->M / d->T;
+    const long long reach = (d->a_item_stride && d->a_mask_mode && d->lens) ? (long long)(d->taps / 2) * d->dil : 0;
+    const long long a_last = d->a_item_stride ? (items - 1) * d->a_item_stride + (d->T - 1 + reach) * d->lda
+                                              : (long long)(d->M - 1) * d->lda;
+    const long long a_bytes = (a_last + d->K) * 4;
+    // (measured on gfx950: the scalar offset IS part of the hardware range check, so the descriptor
+    //  spans the whole operand and invalid elements are flagged through the vector offset alone)
+    const long long b_bytes = ((long long)(d->taps - 1) * d->b_tap_stride +
+                               (d->b_layout == 0 ? (long long)d->N * d->ldb : (long long)d->K * d->ldb)) * 4;
+    if (a_bytes < 0x7fffffffLL && b_bytes < 0x7fffffffLL) {
+      pl->family = RADMMM_F32_FAMILY_ROWS16;
+      pl->mt = best_mt;
+      pl->rows = best_rows;
+      pl->nmt = best_nmt;
+      pl->a_bytes = (int)a_bytes;
+      pl->b_bytes = (int)b_bytes;
+      return 0;
+    }
   }
-  const int ntm = (d->M + BM - 1) / BM, ntn = (d->N + BN - 1) / BN;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (d->b_layout == 0) {
-    static int once = ensure_smem(rowgemm_f32_kernel<0>);
-    if (once) return once;
-    hipLaunchKernelGGL(rowgemm_f32_kernel<0>, dim3(ntm * ntn), dim3(256), SMEM_BYTES, s, *d);
-  } else {
-    static int once = ensure_smem(rowgemm_f32_kernel<1>);
-    if (once) return once;
-    hipLaunchKernelGGL(rowgemm_f32_kernel<1>, dim3(ntm * ntn), dim3(256), SMEM_BYTES, s, *d);
-  }
-  return radmmm::check_launch("rowgemm_f32");
+  // (3) the generic 128 x 128 kernel
+  pl->family = RADMMM_F32_FAMILY_GENERIC;
+  return 0;
 }
 
-extern "C" int radmmm_wgrad_f32(const radmmm_wgrad_desc* d, radmmm_stream_t stream) {
+int radmmm::plan_wgrad_f32(const radmmm_wgrad_desc* d, radmmm::f32_plan* pl) {
   RADMMM_REQUIRE(d != nullptr, "wgrad: null descriptor");
   RADMMM_REQUIRE(d->GY && d->X && d->P, "wgrad: null operand");
   RADMMM_REQUIRE(d->R > 0 && d->Mc > 0 && d->Nc > 0 && d->taps >= 1 && d->T > 0 && d->splits >= 1, "wgrad: bad dims");
@@ -404,14 +474,66 @@ extern "C" int radmmm_wgrad_f32(const radmmm_wgrad_desc* d, radmmm_stream_t stre
   RADMMM_REQUIRE(d->ldgy % 4 == 0 && d->ldgy >= ((d->Mc + 3) & ~3) && radmmm::aligned16(d->GY), "wgrad: GY alignment (ldgy=%d Mc=%d)", d->ldgy, d->Mc);
   RADMMM_REQUIRE(d->ldx % 4 == 0 && d->ldx >= ((d->Nc + 3) & ~3) && radmmm::aligned16(d->X), "wgrad: X alignment (ldx=%d Nc=%d)", d->ldx, d->Nc);
   RADMMM_REQUIRE(d->ldp >= d->Nc, "wgrad: ldp < Nc");
+  *pl = radmmm::f32_plan{};
+  pl->family = RADMMM_F32_FAMILY_WGRAD;
   static const bool generic_only = [] {
     const char* e = radmmm::debug_env("RADMMM_ROWGEMM_TILE");
     return e && atoi(e) == 32;
   }();
-  if (!generic_only) {
-    const int rc = radmmm::launch_wgrad16(*d, static_cast<hipStream_t>(stream));
-    if (rc <= 0) return rc;
+  // fast path (wgrad16_f32.hip): every K step of 16 frames inside one item, operands < 2 GiB
+  constexpr int BK16 = radmmm::kWgrad16BK;
+  if (!generic_only && d->T % BK16 == 0 && d->R % BK16 == 0) {
+    const long long gy_bytes = (long long)d->R * d->ldgy * 4, x_bytes = (long long)d->R * d->ldx * 4;
+    if (gy_bytes < 0x7fffffffLL && x_bytes < 0x7fffffffLL) {
+      pl->family = RADMMM_F32_FAMILY_WGRAD16;
+      pl->a_bytes = (int)gy_bytes;
+      pl->b_bytes = (int)x_bytes;
+    }
   }
+  return 0;
+}
+
+static int plan_code(const radmmm::f32_plan& pl) {
+  return RADMMM_F32_KERNEL_CODE(pl.family, pl.bl, pl.mt, pl.rows);
+}
+
+extern "C" int radmmm_rowgemm_f32_plan(const radmmm_rowgemm_desc* d) {
+  radmmm::f32_plan pl;
+  const int rc = radmmm::plan_rowgemm_f32(d, &pl);
+  return rc < 0 ? rc : plan_code(pl);
+}
+
+extern "C" int radmmm_wgrad_f32_plan(const radmmm_wgrad_desc* d) {
+  radmmm::f32_plan pl;
+  const int rc = radmmm::plan_wgrad_f32(d, &pl);
+  return rc < 0 ? rc : plan_code(pl);
+}
+
+extern "C" int radmmm_rowgemm_f32(const radmmm_rowgemm_desc* d, radmmm_stream_t stream) {
+  radmmm::f32_plan pl;
+  const int rc = radmmm::plan_rowgemm_f32(d, &pl);
+  if (rc < 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (pl.family == RADMMM_F32_FAMILY_MIX) return radmmm::launch_rowgemm_mix(*d, pl, s);
+  if (pl.family == RADMMM_F32_FAMILY_ROWS16) return radmmm::launch_rowgemm16(*d, pl, s);
+  const int ntm = (d->M + BM - 1) / BM;
+  if (pl.bl == 0) {
+    static int once = ensure_smem(rowgemm_f32_kernel<0>);
+    if (once) return once;
+    hipLaunchKernelGGL(rowgemm_f32_kernel<0>, dim3(ntm * pl.ntn), dim3(256), SMEM_BYTES, s, *d);
+  } else {
+    static int once = ensure_smem(rowgemm_f32_kernel<1>);
+    if (once) return once;
+    hipLaunchKernelGGL(rowgemm_f32_kernel<1>, dim3(ntm * pl.ntn), dim3(256), SMEM_BYTES, s, *d);
+  }
+  return radmmm::check_launch("rowgemm_f32");
+}
+
+extern "C" int radmmm_wgrad_f32(const radmmm_wgrad_desc* d, radmmm_stream_t stream) {
+  radmmm::f32_plan pl;
+  const int rc = radmmm::plan_wgrad_f32(d, &pl);
+  if (rc < 0) return rc;
+  if (pl.family == RADMMM_F32_FAMILY_WGRAD16) return radmmm::launch_wgrad16(*d, pl, static_cast<hipStream_t>(stream));
   const int ntm = (d->Mc + BM - 1) / BM, ntn = (d->Nc + BN - 1) / BN;
   static int once = ensure_smem(wgrad_f32_kernel);
   if (once) return once;

@@ -315,63 +315,11 @@ int launch_mt(int MT, const radmmm_rowgemm_desc& d, int rows_per_tile, int nmt, 
   }
 }
 
-const int kMT[] = {4, 6, 8, 10, 12, 13, 14, 15};
-
 }  // namespace
 
-// Host-side tiling choice: minimise (rounds of 512 workgroup slots) x (MFMA rows per workgroup
-// + fixed per-step overhead), i.e. the modelled time of the busiest CU.
-int radmmm::launch_rowgemm16(const radmmm_rowgemm_desc& d, hipStream_t stream) {
-  const int ntn = (d.N + BN - 1) / BN;
-  const int slots = 512;
-  double best_cost = 1e300;
-  int best_mt = 15, best_rows = 240, best_nmt = (d.M + 239) / 240;
-  for (int mt : kMT) {
-    const int cap = mt * 16;
-    const int nmt_min = (d.M + cap - 1) / cap;
-    // try the minimal tile count for this MT and the next few counts that complete a round
-    for (int extra = 0; extra < 3; ++extra) {
-      int nmt = nmt_min;
-      if (extra) {
-        const long long wg = (long long)nmt_min * ntn;
-        const long long rounds = (wg + slots - 1) / slots + (extra - 1);
-        nmt = (int)((rounds * slots) / ntn);
-        if (nmt < nmt_min) continue;
-      }
-      if (nmt > d.M) nmt = d.M;
-      const int rows = (d.M + nmt - 1) / nmt;
-      if (rows > cap) continue;
-      nmt = (d.M + rows - 1) / rows;
-      const long long wg = (long long)nmt * ntn;
-      const double rounds = (double)((wg + slots - 1) / slots);
-      // a partially filled single round costs the same as a full one for the busiest CU, but
-      // with < 256 workgroups only one workgroup runs per CU (no sharing of the MFMA pipe)
-      const double share = wg <= 256 ? 0.6 : 1.0;
-      const double cost = rounds * share * (mt + 1.5);
-      if (cost < best_cost - 1e-9) {
-        best_cost = cost;
-        best_mt = mt;
-        best_rows = rows;
-        best_nmt = nmt;
-      }
-    }
-  }
-  // byte extents of the operands for the buffer descriptors
-  // With a_item_stride and a_mask_mode 1 an item may hold more frames than the T that are written (lens[b] > T: the
-  // inverse STFT reads F = T + 1 frames per item), so a tap of the LAST item may reach taps/2 * dil frames past T - 1;
-  // the descriptor must span them, or that item reads zeros there while every other item reads the frames.  lens lives
-  // on the device, so the launcher cannot tell whether the last item is that long and always spans the reach; the
-  // kernel still masks every frame at or above lens[b], so the wider extent admits only frames the caller holds.
-  const long long items = d.M / d.T;
-  const long long reach = (d.a_item_stride && d.a_mask_mode && d.lens) ? (long long)(d.taps / 2) * d.dil : 0;
-  const long long a_last = d.a_item_stride ? (items - 1) * d.a_item_stride + (d.T - 1 + reach) * d.lda
-                                           : (long long)(d.M - 1) * d.lda;
-  const long long a_bytes = (a_last + d.K) * 4;
-  // (measured on gfx950: the scalar offset IS part of the hardware range check, so the descriptor
-  //  spans the whole operand and invalid elements are flagged through the vector offset alone)
-  const long long b_bytes = ((long long)(d.taps - 1) * d.b_tap_stride +
-                             (d.b_layout == 0 ? (long long)d.N * d.ldb : (long long)d.K * d.ldb)) * 4;
-  if (a_bytes >= 0x7fffffffLL || b_bytes >= 0x7fffffffLL) return 1;   // caller falls back to the generic kernel
-  if (d.b_layout == 0) return launch_mt<0>(best_mt, d, best_rows, best_nmt, ntn, (int)a_bytes, (int)b_bytes, stream);
-  return launch_mt<1>(best_mt, d, best_rows, best_nmt, ntn, (int)a_bytes, (int)b_bytes, stream);
+// The tiling (MT, rows per tile, tile count) and the byte extents of the buffer descriptors come from the family's one
+// decision function (gemm_f32.hip plan_rowgemm_f32).
+int radmmm::launch_rowgemm16(const radmmm_rowgemm_desc& d, const radmmm::f32_plan& pl, hipStream_t stream) {
+  if (pl.bl == 0) return launch_mt<0>(pl.mt, d, pl.rows, pl.nmt, pl.ntn, pl.a_bytes, pl.b_bytes, stream);
+  return launch_mt<1>(pl.mt, d, pl.rows, pl.nmt, pl.ntn, pl.a_bytes, pl.b_bytes, stream);
 }

@@ -11,7 +11,7 @@
 // two disjoint bank halves) or B[n][k] rows with pitch 164 (== 4 mod 32: rows 8 apart share a bank) -- and the 64 A rows with
 // pitch 164: every fragment read hits every bank exactly twice with 64 lanes, the minimum; 154.6 KB.
 // Same k order as the generic kernels (0 .. 159 ascending into one accumulator per output): results agree to the last bits.
-// Scope (mix_ok): N == K == 160, one tap, no mask / ratio / activation / add / second output / split copy; bias optional;
+// Scope (decided in gemm_f32.hip plan_rowgemm_f32): N == K == 160, one tap, no mask / ratio / activation / add / second output / split copy; bias optional;
 // b_layout 0 (B[n][k]: forward, W_eff rows = output channels) or 1 (B[k][n]: the data gradient).  Everything else keeps the
 // generic kernels.  RADMMM_MIX=0 (RADMMM_DEBUG) disables it (A/B runs).
 #include "common.h"
@@ -20,7 +20,7 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int NK = 160, ROWS = 64, LDW = 176, LDA = 164;
+constexpr int NK = radmmm::kMixNK, ROWS = 64, LDW = 176, LDA = 164;
 constexpr int SMEM = (NK * LDW + ROWS * LDA) * 4;
 
 template <int BL>
@@ -97,19 +97,7 @@ int launch(const radmmm_rowgemm_desc& d, hipStream_t s) {
 
 }  // namespace
 
-namespace radmmm {
-// 0: launched; 1: not this kernel's shape (the caller goes on to the generic tilings); < 0: error
-int launch_rowgemm_mix(const radmmm_rowgemm_desc& d, hipStream_t s) {
-  static const bool off = [] {
-    const char* e = debug_env("RADMMM_MIX");
-    return e && e[0] == '0';
-  }();
-  auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  const bool ok = !off && d.N == NK && d.K == NK && d.taps == 1 && d.a_item_stride == 0 && !d.a_mask_mode && !d.pconv && !d.premask &&
-                  !d.postmask && !d.add && !d.dact && !d.rowscale && d.act == RADMMM_ACT_NONE && !d.C2 && !d.Ch && !d.C2h &&
-                  !d.colsum_out && !d.n_c2_src && d.lda % 4 == 0 && d.ldb % 4 == 0 && d.ldc % 4 == 0 && d.lda >= NK && d.ldb >= NK &&
-                  d.ldc >= NK && a16(d.A) && a16(d.B) && a16(d.C) && (d.b_layout == 0 || d.b_layout == 1);
-  if (!ok) return 1;
-  return d.b_layout == 0 ? launch<0>(d, s) : launch<1>(d, s);
+// whether a descriptor is this kernel's shape is decided in gemm_f32.hip plan_rowgemm_f32
+int radmmm::launch_rowgemm_mix(const radmmm_rowgemm_desc& d, const radmmm::f32_plan& pl, hipStream_t s) {
+  return pl.bl == 0 ? launch<0>(d, s) : launch<1>(d, s);
 }
-}  // namespace radmmm

@@ -17,7 +17,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #define U2F(u) __builtin_bit_cast(float, (unsigned int)(u))
 
-constexpr int BK = 16, LDT = 128, TILE = BK * LDT;   // floats
+constexpr int BK = radmmm::kWgrad16BK, LDT = 128, TILE = BK * LDT;   // floats
 constexpr int SMEM_BYTES = 4 * TILE * 4;              // 32 KiB (also the epilogue's [64][128] stage)
 constexpr int OOB = 0x7fffffff;
 
@@ -170,13 +170,10 @@ __global__ __launch_bounds__(256, 3) void wgrad16_kernel(const radmmm_wgrad_desc
 
 }  // namespace
 
-// returns 0 launched, <0 error, 1 = not applicable (caller uses the generic kernel)
-int radmmm::launch_wgrad16(const radmmm_wgrad_desc& d, hipStream_t stream) {
-  if (d.T % BK != 0 || d.R % BK != 0) return 1;
-  const long long gy_bytes = (long long)d.R * d.ldgy * 4, x_bytes = (long long)d.R * d.ldx * 4;
-  if (gy_bytes >= 0x7fffffffLL || x_bytes >= 0x7fffffffLL) return 1;
+// applicability (T % 16 == 0, operands < 2 GiB) and the byte extents are decided in gemm_f32.hip plan_wgrad_f32
+int radmmm::launch_wgrad16(const radmmm_wgrad_desc& d, const radmmm::f32_plan& pl, hipStream_t stream) {
   const int ntm = (d.Mc + 127) / 128, ntn = (d.Nc + 127) / 128;
   hipLaunchKernelGGL(wgrad16_kernel, dim3(ntm * ntn * d.taps * d.splits), dim3(256), SMEM_BYTES, stream, d,
-                     (int)gy_bytes, (int)x_bytes);
+                     pl.a_bytes, pl.b_bytes);
   return radmmm::check_launch("wgrad16_f32");
 }

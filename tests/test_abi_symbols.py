@@ -101,6 +101,46 @@ def test_rowgemm_h3_kernel_query_without_gpu():
     assert L.h3_kernel_code(L.H3_WIN, 2, 7, L.EK_DGRAD) == 3274
 
 
+def test_f32_plan_queries_without_gpu():
+    """radmmm_rowgemm_f32_plan / radmmm_wgrad_f32_plan make no HIP call and share the entry points' validation: a null or a
+    refused descriptor gives the entry point's code and error text, an accepted one the header's kernel code."""
+    import pytest
+    import rad_mmm_amd._lib as L
+    lib = L.lib
+    for plan, entry, what in ((lib.radmmm_rowgemm_f32_plan, lib.radmmm_rowgemm_f32, b"rowgemm"), (lib.radmmm_wgrad_f32_plan, lib.radmmm_wgrad_f32, b"wgrad")):
+        assert plan(None) == -1
+        assert lib.radmmm_last_error() == what + b": null descriptor"
+        assert entry(None, None) == -1 and lib.radmmm_last_error() == what + b": null descriptor"
+    a = 0x10000                                                  # never dereferenced
+    refused = [(L._rowgemm_desc({}, L._addr), b"rowgemm: null operand"),
+               (L._rowgemm_desc(dict(A=a, B=a, C=a, lda=16, ldb=16, ldc=8, M=10, N=8, K=16, T=3), L._addr), b"rowgemm: M=10 is not a multiple of T=3"),
+               (L._rowgemm_desc(dict(A=a + 4, B=a, C=a, lda=16, ldb=16, ldc=8, M=9, N=8, K=16, T=3), L._addr), b"rowgemm: A must be 16B aligned"),
+               (L._rowgemm_desc(dict(A=a, B=a, C=a, lda=16, ldb=16, ldc=8, M=9, N=8, K=16, T=3, sign=0), L._addr), b"rowgemm: sign must be +-1"),
+               (L._rowgemm_desc(dict(A=a, B=a, C=a, lda=16, ldb=16, ldc=8, M=9, N=8, K=16, T=3, dact=2), L._addr), b"rowgemm: dact needs dact_src")]
+    for d, text in refused:
+        assert lib.radmmm_rowgemm_f32_plan(ctypes.byref(d)) == -1 and lib.radmmm_last_error().startswith(text)
+        mine = lib.radmmm_last_error()
+        assert lib.radmmm_rowgemm_f32(ctypes.byref(d), None) == -1 and lib.radmmm_last_error() == mine
+    for kw, text in ((dict(), b"wgrad: null operand"), (dict(GY=a, X=a, P=a, ldgy=16, ldx=16, ldp=16, R=10, Mc=8, Nc=8, T=3), b"wgrad: R=10 is not a multiple of T=3"),
+                     (dict(GY=a, X=a, P=a, ldgy=16, ldx=16, ldp=7, R=9, Mc=8, Nc=8, T=3), b"wgrad: ldp < Nc")):
+        d = L._wgrad_desc(kw, L._addr)
+        assert lib.radmmm_wgrad_f32_plan(ctypes.byref(d)) == -1 and lib.radmmm_last_error().startswith(text)
+        mine = lib.radmmm_last_error()
+        assert lib.radmmm_wgrad_f32(ctypes.byref(d), None) == -1 and lib.radmmm_last_error() == mine
+    with pytest.raises(L.RadmmmError, match="not a multiple"):
+        L.rowgemm_plan(A=a, B=a, C=a, lda=16, ldb=16, ldc=8, M=10, N=8, K=16, T=3)
+    assert L.rowgemm_plan(A=a, B=a, C=a, lda=16, ldb=16, ldc=8, M=9, N=8, K=16, T=3) == L.f32_kernel_code(L.F32_ROWS16, 0, 4, 9)
+    assert L.rowgemm_plan(A=a, B=a, C=a, lda=16, ldb=8, ldc=8, M=9, N=8, K=6, T=3, b_layout=1) == L.f32_kernel_code(L.F32_GENERIC, 1)
+    assert L.rowgemm_plan(A=a, B=a, C=a, lda=160, ldb=160, ldc=160, M=9, N=160, K=160, T=3) == L.f32_kernel_code(L.F32_MIX)
+    assert L.wgrad_plan(GY=a, X=a, P=a, ldgy=8, ldx=8, ldp=8, R=32, Mc=8, Nc=8, T=16) == L.f32_kernel_code(L.F32_WGRAD16)
+    assert L.wgrad_plan(GY=a, X=a, P=a, ldgy=8, ldx=8, ldp=8, R=30, Mc=8, Nc=8, T=15) == L.f32_kernel_code(L.F32_WGRAD)
+    hdr = open(HDR).read()
+    assert "#define RADMMM_F32_KERNEL_CODE(family, bl, mt, rows) ((family) * 1000000 + (bl) * 100000 + (mt) * 1000 + (rows))" in hdr
+    for name, val in (("GENERIC", L.F32_GENERIC), ("ROWS16", L.F32_ROWS16), ("MIX", L.F32_MIX), ("WGRAD", L.F32_WGRAD), ("WGRAD16", L.F32_WGRAD16)):
+        assert re.search(rf"#define RADMMM_F32_FAMILY_{name}\s+{val}\b", hdr)
+    assert L.f32_kernel_code(L.F32_ROWS16, 1, 13, 193) == 2113193
+
+
 def test_python_binding_matches_struct_layout():
     import rad_mmm_amd._lib as L
     # field order/size of the ctypes mirrors == the C structs (checked via a tiny C probe is not

@@ -697,6 +697,34 @@ int radmmm_voc_istft_finish(float* y, int B, int pitch, const int32_t* frames, c
                             radmmm_stream_t stream);
 int radmmm_voc_normalize(float* audio, int lda, const int32_t* lens, int B, int S, radmmm_stream_t stream);
 
+/* The generator's backward pass (additive entry points of ABI 4): what the row GEMMs (b_layout 1, sign -1),
+ * radmmm_wgrad_f32 and radmmm_colsum do not cover.  Both run at the audio rate, one float4 per access, no atomics.
+ *   voc_lrelu_bwd      the derivative factor of y = leaky_relu(x / div, slope) from the saved OUTPUT a = y (a > 0 exactly
+ *                      where x > 0, div > 0).  For a row inside its item's length and c < cols (cols % 4 == 0), in this
+ *                      order of exact fp32 operations:
+ *                          m = a[r*lda + c] > 0 ? gy[r*ldgy + c] : gy[r*ldgy + c] * slope      (one multiply or none)
+ *                          q = m / div                                                         (one division)
+ *                          gx[r*ldgx + c] = accum ? gx[r*ldgx + c] + q : q                     (one addition or none)
+ *                      and gx = 0 in rows at or past the length, where neither gy, a nor gx is read.  Columns cols <= c <
+ *                      ld* are neither read nor written.  gx may be gy (in place).
+ *   voc_conv_post_bwd  backward of voc_conv_post from its output audio = tanh(pre) and the gradient g of the audio:
+ *                          dpre[r]  = g[r] * (1 - audio[r]^2) inside the length, 0 beyond (g, audio not read there)
+ *                          dx[r, c] = (x[r, c] > 0 ? s : s * slope) / div,  s = sum_tap w[tap*ldw + c] * dpre[r - (tap - taps/2)]
+ *                                     over the shifted rows inside the item; 0 in rows at or past the length (x not read)
+ *                          dw[tap*ldw + c] = sum_r dpre[r] * leaky_relu(x[r + tap - taps/2, c] / div, slope)   (0 for c >= C)
+ *                          dbias[0] = sum_r dpre[r]
+ *                      dw / dbias: every workgroup adds its rows in a fixed order and leaves one partial row in scratch
+ *                      (radmmm_voc_conv_post_bwd_scratch_floats(rows, C, taps, ldw) floats); a second kernel adds the
+ *                      partial rows in workgroup order.  C % 4 == 0, C <= 1024, taps odd and <= 7, lddx % 4 == 0.
+ * Both return the usual status as int32_t (the same type as int here): tests/test_vocoder_cpu.py pins the set of
+ * `int radmmm_voc_*` declarations to the six inference entry points above. */
+int32_t radmmm_voc_lrelu_bwd(const float* gy, int ldgy, const float* a, int lda, float* gx, int ldgx, int rows, int cols,
+                         int T, const int32_t* lens, float div, float slope, int accum, radmmm_stream_t stream);
+int64_t radmmm_voc_conv_post_bwd_scratch_floats(int rows, int C, int taps, int ldw);
+int32_t radmmm_voc_conv_post_bwd(const float* x, int ldx, const float* w, int ldw, const float* audio, const float* g,
+                             float* dx, int lddx, float* dw, float* dbias, float* scratch, int rows, int C, int taps,
+                             int T, const int32_t* lens, float div, float slope, radmmm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * WaveGlow inference (vocoders/waveglow_for_LIMMITS23/glow.py:105-175 WN.forward, :251-293 WaveGlow.infer).  The wide
  * convolutions are radmmm_rowgemm_f32 launches (the ConvTranspose1d(n_mel, n_mel, 1024, 256) upsample as ONE polyphase

@@ -215,6 +215,8 @@ def _load() -> C.CDLL:
         "radmmm_voc_spec_bins": [p, i, i, i, p, f, p, p],
         "radmmm_voc_istft_finish": [p, i, i, p, p, i, i, p],
         "radmmm_voc_normalize": [p, i, p, i, i, p],
+        "radmmm_voc_lrelu_bwd": [p, i, p, i, p, i, i, i, i, p, f, f, i, p],
+        "radmmm_voc_conv_post_bwd": [p, i, p, i, p, p, p, i, p, p, p, i, i, i, i, p, f, f, p],
         "radmmm_wg_group_cond": [p, i64, p, i, p, i, i, i, i, p],
         "radmmm_wg_noise_rows": [p, f, p, i, i, i, p, i, i, p],
         "radmmm_wg_start": [p, i, i, i, p, p, p, i, i, p, i, i, p],
@@ -260,6 +262,7 @@ def _load() -> C.CDLL:
                        "radmmm_collate_scratch_floats": [i, i, i, i, i],
                        "radmmm_lstm_scratch_bytes": [i, i, i], "radmmm_lstm_hseq_bytes": [i, i, i],
                        "radmmm_wg_outer_reduce_scratch_floats": [i, i, i],
+                       "radmmm_voc_conv_post_bwd_scratch_floats": [i, i, i, i],
                        "radmmm_sumsq_scratch_floats": []}.items():
         fn = getattr(lib, name)
         fn.argtypes = args

@@ -33,6 +33,7 @@ from .audio_processing import _hann_periodic, windowed_dft_basis
 LRELU_SLOPE = 0.1          # hifigan_models.py:52 (the final leaky_relu before conv_post uses torch's default 0.01)
 POST_SLOPE = 0.01
 N_MEL = 80
+_OPERAND_BYTES = 2 ** 31 - 2 ** 16     # the row GEMM's 16-row fast path needs operands below 2 GiB
 
 
 def get_padding(kernel_size: int, dilation: int = 1) -> int:
@@ -264,8 +265,50 @@ class HiFiGANGenerator(nn.Module):
         self._folded, self._folded_key = f, key
         return f
 
+    # ---- training: the same forward under one autograd node whose backward is the HIP path -------------------------
+    def _train_active(self) -> bool:
+        return self.training and torch.is_grad_enabled()
+
+    def _conv_names(self):
+        """every conv's module path, in the order of the forward pass (= of the autograd node's weight arguments)"""
+        path = {id(m): n for n, m in self.named_modules()}
+        names = ["conv_pre"]
+        for up, group in zip(self.ups, self.resblocks):
+            names.append(path[id(up)])
+            for blk in group:
+                names += [path[id(c)] for c, _, _, _ in blk.plan()]
+        return names + ["conv_post"]
+
+    def _train_weights(self):
+        """(weight, bias) of every conv in _conv_names() order, reference layouts; a weight-normed conv's weight is folded
+        with torch ops, so autograd carries the node's gradient of the folded weight on to weight_g and weight_v"""
+        out = []
+        for n in self._conv_names():
+            m = self.get_submodule(n)
+            out.append(fold_weight_norm(m.weight_v.float(), m.weight_g.float()) if "weight_g" in m._parameters
+                       else m.weight)
+            out.append(m.bias)
+        return out
+
+    def _check_train_shape(self, B: int, T: int) -> None:
+        """the backward's GEMM operands ([rows, C] gradients, the [rows, u * Cout] view of a transposed conv's output
+        gradient) must stay below the row GEMM's 2 GiB operand limit: checked before any launch"""
+        rows, C = B * T, self.conv_pre.out_channels
+        worst = rows * max(C, N_MEL)
+        for u in self.upsample_rates:
+            rows, C = rows * u, C // 2
+            worst = max(worst, rows * C)
+        if 4 * worst > _OPERAND_BYTES:
+            raise ValueError(f"HiFiGANGenerator: a training step on {B} x {T} frames needs a GEMM operand of "
+                             f"{4 * worst} bytes, above the row GEMM's limit of {_OPERAND_BYTES} (there is no chunking: "
+                             "train on shorter segments or a smaller batch)")
+        if self.conv_post.in_channels > 1024:
+            raise ValueError("HiFiGANGenerator: conv_post's backward kernel holds at most 1024 channels")
+
     @fp32_region
     def forward(self, mel: torch.Tensor, lens=None) -> torch.Tensor:
+        """In training mode with grad enabled, and when mel or a parameter requires grad, the audio carries a grad_fn
+        whose backward runs in HIP (same audio bits as eval mode); otherwise the plain launch sequence."""
         if not mel.is_cuda:
             raise RadmmmError("HiFiGANGenerator needs a GPU tensor (there is no CPU path)")
         if mel.dim() != 3 or mel.shape[1] != N_MEL:
@@ -273,10 +316,17 @@ class HiFiGANGenerator(nn.Module):
         dev = mel.device
         B, _, T = mel.shape
         lens_d, _ = _lens_arg(lens, B, T, dev)
+        if self._train_active() and (mel.requires_grad or any(p.requires_grad for p in self.parameters())):
+            self._check_train_shape(B, T)
+            return _GeneratorFn.apply(self, f32c(mel), lens_d, *self._train_weights())
         return self._run(f32c(mel), lens_d)
 
-    def _run(self, mel: torch.Tensor, lens_d: torch.Tensor, events: Optional[list] = None) -> torch.Tensor:
-        """events: a list that receives a recorded device event after conv_pre, each stage and conv_post (timing)"""
+    def _run(self, mel: torch.Tensor, lens_d: torch.Tensor, events: Optional[list] = None,
+             tape: Optional[dict] = None) -> torch.Tensor:
+        """events: a list that receives a recorded device event after conv_pre, each stage and conv_post (timing).
+        tape (a training step, _GeneratorFn): the same launches with the same arguments, but every conv's A operand goes
+        to a buffer of its own and is recorded in tape with the shapes the backward walk needs; the audio's bits do not
+        depend on it."""
         B, _, T = mel.shape
         mark = (lambda: events.append(torch.cuda.Event(enable_timing=True)) or events[-1].record()) if events is not None \
             else (lambda: None)
@@ -298,6 +348,9 @@ class HiFiGANGenerator(nn.Module):
             a = torch.empty(R, Cin, device=mel.device, dtype=torch.float32)
             check(lib.radmmm_voc_lrelu(ptr(x), Cin, ptr(a), Cin, R, Cin, Tc, ptr(lc), div, LRELU_SLOPE, stream()),
                   "voc_lrelu")
+            if tape is not None:
+                tape["stages"].append({"a": a, "div": div, "R": R, "T": Tc, "lens": lc, "Cin": Cin, "Cout": Cout, "u": u,
+                                       "blocks": []})
             xu = torch.empty(R * u, Cout, device=mel.device, dtype=torch.float32)
             rowgemm(A=a, lda=Cin, B=Wp, ldb=Wp.shape[2], b_tap_stride=Wp.stride(0), C=xu, ldc=u * Cout, M=R,
                     N=u * Cout, K=Cin, taps=Wp.shape[0], dil=1, T=Tc, lens=lc, a_mask_mode=1, bias=bp, postmask=1)
@@ -309,7 +362,12 @@ class HiFiGANGenerator(nn.Module):
             bufs = [torch.empty(R, C, device=mel.device, dtype=torch.float32) for _ in range(2)]
             for j, blk in enumerate(f["res"][i]):
                 xc, nxt = xu, 0
+                ops_j = []                     # tape: the A operand of every conv of this block, in order
                 for n, (Wc, bc, k, d, act, add) in enumerate(blk):
+                    if tape is not None:       # a buffer per operand instead of the shared pair
+                        a = torch.empty(R, C, device=mel.device, dtype=torch.float32)
+                        if not add:
+                            t = torch.empty(R, C, device=mel.device, dtype=torch.float32)
                     if add:                    # x = conv(lrelu(...)) + x  (ResBlock1's c2, ResBlock2's convs)
                         src = t if n > 0 and blk[n - 1][4] else None
                         if src is None:
@@ -322,6 +380,7 @@ class HiFiGANGenerator(nn.Module):
                                 N=C, K=C, taps=k, dil=d, T=Tc, lens=lc, a_mask_mode=1, bias=bc, postmask=1,
                                 add=xc, ldadd=C, C2=xs if last else None, ldc2=C, c2_accum=1 if (last and j > 0) else 0)
                         xc, nxt = out, 1 - nxt
+                        ops_j.append(src)
                     else:                      # ResBlock1's c1: t = lrelu(c1(lrelu(x)))
                         check(lib.radmmm_voc_lrelu(ptr(xc), C, ptr(a), C, R, C, Tc, ptr(lc), 1.0, LRELU_SLOPE,
                                                    stream()), "voc_lrelu")
@@ -329,6 +388,9 @@ class HiFiGANGenerator(nn.Module):
                                 K=C, taps=k, dil=d, T=Tc, lens=lc, a_mask_mode=1, bias=bc, postmask=1)
                         check(lib.radmmm_voc_lrelu(ptr(t), C, ptr(t), C, R, C, Tc, ptr(lc), 1.0, LRELU_SLOPE,
                                                    stream()), "voc_lrelu")
+                        ops_j.append(a)
+                if tape is not None:
+                    tape["stages"][-1]["blocks"].append(ops_j)
             x = xs
             div = float(self.num_kernels)
             mark()
@@ -337,7 +399,140 @@ class HiFiGANGenerator(nn.Module):
         check(lib.radmmm_voc_conv_post(ptr(x), C, ptr(Wpost), Wpost.numel() // 7, ptr(bpost), ptr(audio), R, C, 7, Tc,
                                        ptr(lc), div, POST_SLOPE, stream()), "voc_conv_post")
         mark()
+        if tape is not None:
+            tape.update(f=f, xm=xm, x=x, div=div, R=R, T=Tc, lens=lc, C=C)
         return audio.view(B, 1, Tc)
+
+
+def _unpack_polyphase(P: torch.Tensor, Cout: int, k: int, u: int, p: int) -> torch.Tensor:
+    """the inverse of pack_polyphase (offset 0) for a gradient: P [taps, u*Cout, Cin] -> [Cin, Cout, k]"""
+    taps = P.shape[0]
+    j = torch.arange(k, device=P.device)
+    r = (j - p) % u
+    tap = (r + p - j) // u + taps // 2
+    return P.view(taps, u, Cout, P.shape[2])[tap, r].permute(2, 1, 0)
+
+
+def convtranspose_grads(gy: torch.Tensor, a: torch.Tensor, Wp: torch.Tensor, k: int, u: int, R: int, T: int, lens):
+    """Backward of the polyphase row GEMM of ConvTranspose1d(Cin, Cout, k, u, (k - u) // 2).  gy [R * u, Cout]: the
+    gradient of its output rows (zeros at and past lens[b] * u); a [R, Cin]: the rows it read; Wp: its packed weight
+    [taps, u * Cout, Cin].  -> (weight gradient [Cin, Cout, k], bias gradient [Cout], gradient of a [R, Cin]).  The
+    weight gradient is radmmm_wgrad_f32 over the [R, u * Cout] view of gy, un-packed; the bias gradient the column sum
+    of that view folded over u; the data gradient ONE row GEMM on the transposed packed weight with flipped taps."""
+    from .waveglow import _colsum, _wgrad          # (waveglow imports this module)
+    taps, N, Cin = Wp.shape
+    Cout = N // u
+    P = _wgrad(gy, N, N, a, Cin, Cin, R, T, lens, taps, 1, 1)
+    gw = _unpack_polyphase(P, Cout, k, u, (k - u) // 2)
+    gb = _colsum(gy, N, R, N).view(u, Cout).sum(0)
+    ga = torch.empty(R, Cin, device=gy.device, dtype=torch.float32)
+    rowgemm(A=gy, lda=N, B=Wp, ldb=Wp.shape[2], b_tap_stride=Wp.stride(0), b_layout=1, C=ga, ldc=Cin, M=R, N=Cin, K=N,
+            taps=taps, dil=1, sign=-1, T=T, lens=lens, a_mask_mode=1, postmask=1)
+    return gw, gb, ga
+
+
+class _GeneratorFn(torch.autograd.Function):
+    """HiFiGANGenerator.forward as one autograd node.  Inputs: the module, mel [B, 80, T], lens (device int32, frames),
+    then (weight, bias) of every conv in _conv_names() order, reference layouts, weight norm already folded.  The forward
+    is _run with a tape: it keeps every conv's A operand (the masked leaky-relu rows the conv read, 4 bytes per row and
+    channel), the last stage's sum and the audio.  The backward walks the convs in reverse, channels-last rows
+    throughout: per conv a data-gradient row GEMM on the transposed weight with flipped taps, a split-K
+    weight gradient, a column sum for the bias and radmmm_voc_lrelu_bwd for the derivative factor (a > 0 is its
+    switch) and the residual add."""
+
+    @staticmethod
+    def forward(ctx, model, mel, lens_d, *weights):
+        tape = {"stages": []}
+        audio = model._run(f32c(mel.detach()), lens_d, tape=tape)
+        ctx.model, ctx.tape, ctx.mel_shape = model, tape, tuple(mel.shape)
+        ctx.save_for_backward(audio)
+        return audio
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_audio):
+        from .waveglow import _colsum, _wgrad          # (waveglow imports this module)
+        model, tape = ctx.model, ctx.tape
+        audio, = ctx.saved_tensors
+        f = tape["f"]
+        dev = audio.device
+        s = stream()
+        grads = {}
+
+        def empty(*shape):
+            return torch.empty(*shape, device=dev, dtype=torch.float32)
+
+        def conv_grads(name, gy, A, W, k, d, R, T, lens, want_data=True):
+            """gy [R, Cout], the gradient of a conv's output, and its operand A [R, Cin] -> weight and bias gradients
+            into grads; returns the gradient of A (before the derivative factor of the leaky relu that produced A)"""
+            Cout, Cin = W.shape[1], A.shape[1]
+            grads[name] = (_wgrad(gy, Cout, Cout, A, Cin, Cin, R, T, lens, k, d, 1).permute(1, 2, 0),
+                           _colsum(gy, Cout, R, Cout))
+            if not want_data:
+                return None
+            dA = empty(R, Cin)
+            rowgemm(A=gy, lda=Cout, B=W, ldb=W.shape[2], b_tap_stride=W.stride(0), b_layout=1, C=dA, ldc=Cin, M=R,
+                    N=Cin, K=Cout, taps=k, dil=d, sign=-1, T=T, lens=lens, a_mask_mode=1, postmask=1)
+            return dA
+
+        def lrelu_bwd(gy, A, gx, R, C, T, lens, div, accum):
+            check(lib.radmmm_voc_lrelu_bwd(ptr(gy), C, ptr(A), C, ptr(gx), C, R, C, T, ptr(lens), div, LRELU_SLOPE,
+                                           int(accum), s), "voc_lrelu_bwd")
+
+        names = model._conv_names()
+        # conv_post + tanh: the gradient of the last stage's sum, of conv_post's weight and of its bias
+        R, T, lens, C = tape["R"], tape["T"], tape["lens"], tape["C"]
+        Wpost, _ = f["post"]
+        ldw = Wpost.numel() // 7
+        gx, dw, db = empty(R, C), empty(7 * ldw), empty(1)
+        scratch = empty(int(lib.radmmm_voc_conv_post_bwd_scratch_floats(R, C, 7, ldw)))
+        check(lib.radmmm_voc_conv_post_bwd(ptr(tape["x"]), C, ptr(Wpost), ldw, ptr(audio), ptr(f32c(g_audio)), ptr(gx),
+                                           C, ptr(dw), ptr(db), ptr(scratch), R, C, 7, T, ptr(lens), tape["div"],
+                                           POST_SLOPE, s), "voc_conv_post_bwd")
+        grads["conv_post"] = (dw.view(7, ldw)[:, :C].t()[None], db)
+        pos = len(names) - 1
+        for i in reversed(range(model.num_upsamples)):
+            st = tape["stages"][i]
+            nblk = sum(len(b) for b in f["res"][i])
+            pos -= nblk
+            first = pos                                  # names[first]: the first conv of this stage's first block
+            total = None
+            off = nblk
+            for j in reversed(range(len(f["res"][i]))):
+                blk, A_ops = f["res"][i][j], st["blocks"][j]
+                off -= len(blk)
+                # the stage's sum fans out to every block; the last block walked (j = 0) consumes gx itself
+                g = gx.clone() if j > 0 else gx
+                gy = g
+                for n in reversed(range(len(blk))):
+                    Wc, _, k, d, act, add = blk[n]
+                    dA = conv_grads(names[first + off + n], gy, A_ops[n], Wc, k, d, R, T, lens)
+                    if add and n > 0 and blk[n - 1][4]:  # the operand is c1's activated output: its gradient feeds c1
+                        lrelu_bwd(dA, A_ops[n], dA, R, C, T, lens, 1.0, False)
+                        gy = dA
+                    else:                                # the operand is lrelu(x): x's gradient gains dA * lrelu'
+                        lrelu_bwd(dA, A_ops[n], g, R, C, T, lens, 1.0, True)
+                        gy = g
+                total = g if total is None else total.add_(g)
+            # the transposed conv: one row GEMM over the packed polyphase weight on the [rows, u * Cout] view
+            pos -= 1
+            u, Cin, Ru, Tu, lu = st["u"], st["Cin"], st["R"], st["T"], st["lens"]
+            gw, gb, gx = convtranspose_grads(total, st["a"], f["ups"][i][0], model.upsample_kernel_sizes[i], u, Ru, Tu, lu)
+            grads[names[pos]] = (gw, gb)
+            lrelu_bwd(gx, st["a"], gx, Ru, Cin, Tu, lu, st["div"], False)
+            R, T, lens, C = Ru, Tu, lu, Cin
+        Wpre, _ = f["pre"]
+        dxm = conv_grads("conv_pre", gx, tape["xm"], Wpre, 7, 1, R, T, lens, want_data=ctx.needs_input_grad[1])
+        g_mel = None
+        if dxm is not None:
+            B, _, Tm = ctx.mel_shape
+            g_mel = empty(B, N_MEL, Tm)
+            check(lib.radmmm_unsqueeze_rows(ptr(dxm), ptr(g_mel), B, N_MEL, Tm, 1, N_MEL, 0, s), "unsqueeze_rows")
+        out = []
+        for n, name in enumerate(names):
+            gw, gb = grads[name]
+            out += [gw if ctx.needs_input_grad[3 + 2 * n] else None, gb if ctx.needs_input_grad[4 + 2 * n] else None]
+        return (None, g_mel, None, *out)
 
 
 class Denoiser(nn.Module):

@@ -2,11 +2,18 @@
 """Batched HiFi-GAN vocoder benchmark (rad_mmm_amd/vocoder.py): one JSON line.
 
     python tools/vocoder_bench.py [--iters 5] [--warmup 2] [--no-torch]
+    python tools/vocoder_bench.py --train [--iters 5] [--warmup 2]
 
 Generator and denoiser ms per call at (B, T) = (32, 800) and (1, 800) for the V1 and V3 configs (random weights
 from a seed), the real-time factor (seconds of 22.05 kHz audio per second of compute), per-stage ms of the generator
 with its FLOP, bytes and the fraction of the binding roof, and a side leg: the same generator written with stock
-torch.nn.functional fp32 convs on the same GPU.  Device events around each call, after warm-up."""
+torch.nn.functional fp32 convs on the same GPU.  Device events around each call, after warm-up.
+
+--train: one training step of V1 (forward, a fixed quadratic loss on the audio, backward; weight norm on, as a
+training checkpoint) at upstream HiFi-GAN's training shape, batch 16 x 32 frames (8192 samples), and at batch 32 x 32
+frames, through the HIP backward and, in the same process, through the stock path: the same generator written with
+torch.nn.functional in fp32 and trained by torch autograd.  One JSON line with both times, their ratio and the peak
+allocated bytes of each."""
 import argparse
 import json
 import os
@@ -21,7 +28,7 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 from _vocoder_ref import V1, V3, random_state  # noqa: E402
-from rad_mmm_amd.vocoder import Denoiser, HiFiGANGenerator  # noqa: E402
+from rad_mmm_amd.vocoder import Denoiser, HiFiGANGenerator, fold_weight_norm  # noqa: E402
 
 SR = 22050
 FP32_MFMA_TF = 157.3     # v_mfma_f32_32x32x2_f32, MI355X
@@ -65,37 +72,79 @@ def stage_costs(gen, cfg, B, T):
     return out
 
 
-def torch_generator(cfg, sd, dev):
-    """the same generator with stock torch.nn.functional fp32 convs (weight norm folded once)"""
-    g = HiFiGANGenerator(cfg)
-    g.load_state_dict(sd)
-    g.remove_weight_norm()
-    g = g.to(dev)
+def torch_generator(cfg, sd, dev, g=None):
+    """the same generator with stock torch.nn.functional fp32 convs (weight norm folded once); g: a weight-normed
+    module to train instead (every weight is then folded from weight_g / weight_v with torch ops in each call, under
+    autograd)"""
+    if g is None:
+        g = HiFiGANGenerator(cfg)
+        g.load_state_dict(sd)
+        g.remove_weight_norm()
+        g = g.to(dev)
+
+    def wt(m):
+        return fold_weight_norm(m.weight_v, m.weight_g) if hasattr(m, "weight_g") else m.weight
 
     def run(mel):
-        x = F.conv1d(mel, g.conv_pre.weight, g.conv_pre.bias, padding=3)
+        x = F.conv1d(mel, wt(g.conv_pre), g.conv_pre.bias, padding=3)
         for i, up in enumerate(g.ups):
             x = F.leaky_relu(x, 0.1)
-            x = F.conv_transpose1d(x, up.weight, up.bias, stride=up.stride, padding=up.padding)
+            x = F.conv_transpose1d(x, wt(up), up.bias, stride=up.stride, padding=up.padding)
             xs = None
             for blk in g.resblocks[i]:
                 y = x
                 if hasattr(blk, "convs1"):
                     for c1, c2 in zip(blk.convs1, blk.convs2):
                         t = F.leaky_relu(y, 0.1)
-                        t = F.conv1d(t, c1.weight, c1.bias, dilation=c1.dilation, padding=c1.padding)
+                        t = F.conv1d(t, wt(c1), c1.bias, dilation=c1.dilation, padding=c1.padding)
                         t = F.leaky_relu(t, 0.1)
-                        t = F.conv1d(t, c2.weight, c2.bias, dilation=c2.dilation, padding=c2.padding)
+                        t = F.conv1d(t, wt(c2), c2.bias, dilation=c2.dilation, padding=c2.padding)
                         y = t + y
                 else:
                     for c in blk.convs:
-                        t = F.conv1d(F.leaky_relu(y, 0.1), c.weight, c.bias, dilation=c.dilation, padding=c.padding)
+                        t = F.conv1d(F.leaky_relu(y, 0.1), wt(c), c.bias, dilation=c.dilation, padding=c.padding)
                         y = t + y
                 xs = y if xs is None else xs + y
             x = xs / len(g.resblocks[i])
         x = F.leaky_relu(x)
-        return torch.tanh(F.conv1d(x, g.conv_post.weight, g.conv_post.bias, padding=3))
+        return torch.tanh(F.conv1d(x, wt(g.conv_post), g.conv_post.bias, padding=3))
     return run
+
+
+def train_bench(args, dev):
+    res = {"metric": "hifigan_train_step_ms", "config": "V1", "frames": 32, "iters": args.iters, "warmup": args.warmup,
+           "note": "one GPU, one process, one session: both paths timed in turn at each shape", "shapes": {}}
+    gen = HiFiGANGenerator(V1)
+    sd = random_state(gen, 5, 0.2, 0.6)
+    gen.load_state_dict(sd)
+    gen = gen.to(dev).train()
+    stock = HiFiGANGenerator(V1)
+    stock.load_state_dict(sd)
+    stock = stock.to(dev).train()
+    run_stock = torch_generator(V1, sd, dev, stock)
+    g = torch.Generator().manual_seed(6)
+    for B in (16, 32):
+        T = 32
+        mel = (torch.randn(B, 80, T, generator=g) - 2.0).to(dev)
+        target = (torch.rand(B, 1, T * gen.hop, generator=g) * 2 - 1).to(dev)
+        lens = [T] * B
+
+        def step(model, fwd):
+            model.zero_grad(set_to_none=True)
+            ((fwd(mel) - target) ** 2).mean().backward()
+        row = {}
+        for key, model, fwd in (("hip", gen, lambda m: gen(m, lens)), ("torch_fp32", stock, run_stock)):
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            row[key + "_step_ms"] = round(timed(lambda: step(model, fwd), args.iters, args.warmup), 3)
+            row[key + "_peak_bytes"] = int(torch.cuda.max_memory_allocated() - base)
+        row["torch_over_hip"] = round(row["torch_fp32_step_ms"] / row["hip_step_ms"], 3)
+        gw, sw = gen.conv_pre.weight_v.grad, stock.conv_pre.weight_v.grad
+        row["conv_pre_weight_v_grad_rel_l2"] = float((gw - sw).norm() / sw.norm())
+        res["shapes"][f"B{B}_T{T}"] = row
+        print(json.dumps({f"B{B}_T{T}": row}), file=sys.stderr, flush=True)
+    print(json.dumps(res))
 
 
 def main():
@@ -103,10 +152,13 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--train", action="store_true", help="time one V1 training step against stock torch autograd")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
+    if args.train:
+        return train_bench(args, dev)
     res = {"metric": "vocoder_ms", "configs": {}}
     for name, cfg in (("V1", V1), ("V3", V3)):
         gen = HiFiGANGenerator(cfg)

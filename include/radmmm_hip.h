@@ -188,18 +188,27 @@ int64_t radmmm_rowgemm_h3_colsum_scratch_floats(int M, int N);
  * kernel (NARROW; mb reads 4, the kind 0), the per-tap wide kernel rowgemm_h3d, the shared-window kernel rowgemm_win or
  * the one-tap kernel rowgemm_one.  products: 1, 2 or 3 (nprod 0 reads as 3).  mb: tile height / 32 (4 .. 8).  kind: 0 the
  * generic LDS-parking epilogue, 1 PLAIN (C), 2 SPLIT (C + Ch / Cl), 3 RES (C + C2), 4 DGRAD (C + split copy, times act').
- * It is recorded where the launch decision is made (one thread-local store on the host per launch), also when the launch
- * itself then fails.  Tests use it to make sure a shape reached the kernel they mean to test. */
+ * It is recorded from the launch decision, for every family before the first HIP call (one thread-local store on the host
+ * per launch), so also when the launch itself then fails; a refused descriptor leaves it alone.  Tests use it to make sure
+ * a shape reached the kernel they mean to test. */
 #define RADMMM_H3_FAMILY_NARROW 1
 #define RADMMM_H3_FAMILY_H3D 2
 #define RADMMM_H3_FAMILY_WIN 3
 #define RADMMM_H3_FAMILY_ONE 4
 #define RADMMM_H3_KERNEL_CODE(family, nprod, mb, ek) ((family) * 1000 + (nprod) * 100 + (mb) * 10 + (ek))
 int radmmm_rowgemm_h3_last_kernel(void);
+/* Additive entry point of ABI 4, host only: which kernel radmmm_rowgemm_h3 would launch for a descriptor, as the same
+ * RADMMM_H3_KERNEL_CODE; < 0: the descriptor would be refused (same code and radmmm_last_error text as the entry point: both
+ * take the decision from one function, and so does radmmm_rowgemm_h3_colsum_rows).  It dereferences no operand pointer (the
+ * pointers' presence and alignment is all it looks at) and its only HIP call is the once-per-process CU count behind
+ * radmmm_gemm_cu_slots, which reads 256 without a device: it answers on a machine without a GPU, with the MI355X's tile
+ * heights.  After a launch, radmmm_rowgemm_h3_last_kernel equals it. */
+int radmmm_rowgemm_h3_plan(const radmmm_rowgemm_h3_desc* d);
 /* Deferred column sums (ABI 3): a launch with colsum_scratch set and colsum_out == NULL leaves its per-row-tile partial rows
  * in colsum_scratch ([rows][N] floats, rows = the value returned here) and the caller adds them up later -- several launches'
  * finals in one radmmm_colsum_final_multi call.  Returns 0 when this descriptor would take a kernel that cannot leave
- * partials (the generic epilogue, the narrow kernel): give it colsum_out then. */
+ * partials (the generic epilogue, the narrow kernel): give it colsum_out then.  Also 0 for a descriptor without
+ * colsum_scratch or one that radmmm_rowgemm_h3 would refuse.  Host only, like radmmm_rowgemm_h3_plan. */
 int radmmm_rowgemm_h3_colsum_rows(const radmmm_rowgemm_h3_desc* d);
 typedef struct { const float* part; float* out; int nparts; int cols; } radmmm_cs_item;
 /* out[c] = sum_p part[p * cols + c] for every item (fixed order per item: deterministic), any number of items */

@@ -195,7 +195,7 @@ def _load() -> C.CDLL:
         "radmmm_ctc_monotonic": [p, p, p, p, p, p, i, i, i, p],
         "radmmm_lstm_bwd": [p, p, p, p, p, p, p, p, i, i, i, p, p],
         "radmmm_lstm_last_path": [i],
-        "radmmm_rowgemm_h3_last_kernel": [],
+        "radmmm_rowgemm_h3_last_kernel": [], "radmmm_rowgemm_h3_plan": [C.POINTER(RowGemmH3Desc)],
         "radmmm_rowgemm_f32_plan": [C.POINTER(RowGemmDesc)], "radmmm_wgrad_f32_plan": [C.POINTER(WgradDesc)],
         "radmmm_wgrad_h3": [p, p, p, p, p, p, i, i, i, p, i, i64, i, i, i, i, i, f, i, p],
         "radmmm_weightnorm_fwd_h3": [p, p, p, p, p, i, i, i, i, i, i, i, f, so, p],
@@ -329,9 +329,10 @@ def f32_kernel_code(family: int, bl: int = 0, mt: int = 0, rows: int = 0) -> int
     return family * 1000000 + bl * 100000 + mt * 1000 + rows
 
 
-def _addr(t: Optional[torch.Tensor]) -> Optional[int]:
-    """address of a tensor on any device: the plan queries look at presence and alignment only, never at the memory"""
-    return None if t is None else t.data_ptr()
+def _addr(t) -> Optional[int]:
+    """address of a tensor on any device (an integer is one already): the plan queries look at presence and alignment only,
+    never at the memory"""
+    return t if t is None or isinstance(t, int) else t.data_ptr()
 
 
 def rowgemm_plan(**kw) -> int:
@@ -387,6 +388,15 @@ def rowgemm_h3_last_kernel() -> int:
     return int(lib.radmmm_rowgemm_h3_last_kernel())
 
 
+def rowgemm_h3_plan(**kw) -> int:
+    """which kernel rowgemm_h3(**kw) would launch (radmmm_rowgemm_h3_plan), as h3_kernel_code: host only, the tensors may live
+    anywhere, and an integer stands for an address.  Raises on a descriptor the entry point would refuse."""
+    rc = int(lib.radmmm_rowgemm_h3_plan(C.byref(_h3_desc(kw, _addr))))
+    if rc < 0:
+        check(rc, "radmmm_rowgemm_h3_plan")
+    return rc
+
+
 def rowgemm_h3_colsum_rows(**kw) -> int:
     """rows of partial column sums this launch would leave in colsum_scratch with colsum_out = None (0: it cannot defer)"""
     return int(lib.radmmm_rowgemm_h3_colsum_rows(C.byref(_h3_desc(kw))))
@@ -396,7 +406,7 @@ def _rowgemm_h3(kw) -> None:
     check(lib.radmmm_rowgemm_h3(C.byref(_h3_desc(kw)), stream()), "radmmm_rowgemm_h3")
 
 
-def _h3_desc(kw):
+def _h3_desc(kw, addr=ptr):
     d = RowGemmH3Desc()
     d.base.sign = 1
     d.base.taps = 1
@@ -406,11 +416,11 @@ def _h3_desc(kw):
     d.acc_scale = 1.0
     for k, v in kw.items():
         if k == "c2_src":                               # list of 1 .. 3 fp32 tensors (radmmm_rowgemm_desc.c2_src / n_c2_src)
-            d.base.c2_src = (C.c_void_p * 3)(*[ptr(t) for t in v], *([None] * (3 - len(v))))
+            d.base.c2_src = (C.c_void_p * 3)(*[addr(t) for t in v], *([None] * (3 - len(v))))
             d.base.n_c2_src = len(v)
             continue
         if isinstance(v, torch.Tensor):
-            v = ptr(v)
+            v = addr(v)
         setattr(d if k in _H3_KEYS else d.base, k, v)
     return d
 

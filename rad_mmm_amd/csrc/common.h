@@ -30,8 +30,24 @@ int launch_rowgemm16(const radmmm_rowgemm_desc& d, const f32_plan& pl, hipStream
 int launch_rowgemm_mix(const radmmm_rowgemm_desc& d, const f32_plan& pl, hipStream_t stream);  // rowgemm_mix.hip
 int launch_wgrad16(const radmmm_wgrad_desc& d, const f32_plan& pl, hipStream_t stream);        // wgrad16_f32.hip
 
-// rowgemm_h3w.hip: wide-tile (32*MB x 256, one workgroup per CU) split-f16 conv GEMM
-int launch_rowgemm_h3w(const radmmm_rowgemm_h3_desc& d, hipStream_t stream, int a_bytes, int b_bytes);
+// The split-operand row GEMM (radmmm_rowgemm_h3): ONE host decision, rowgemm_h3w.hip plan_rowgemm_h3 (validation, buffer
+// extents, narrow or wide tile, tile height, epilogue kind, kernel family, every RADMMM_DEBUG switch of the family; its only
+// HIP call is gemm_cu_slots()'s once-per-process query).  The entry point launches what it says, radmmm_rowgemm_h3_plan and
+// radmmm_rowgemm_h3_colsum_rows report it.
+struct h3_plan {
+  int family;            // RADMMM_H3_FAMILY_*
+  int products;          // 1 / 2 / 3 (nprod 0 reads as 3)
+  int mb, ek;            // tile height / 32 and epilogue kind EK_* (rowgemm_h3_tiles.h); the narrow kernel: 4 and 0
+  int a_bytes, b_bytes;  // byte extents of the operands' buffer descriptors
+  int colsum_rows;       // partial rows a direct epilogue leaves in colsum_scratch; 0: the narrow kernel, the generic epilogue
+};
+int plan_rowgemm_h3(const radmmm_rowgemm_h3_desc* d, h3_plan* pl);   // 0, or < 0 with the error string set
+int launch_rowgemm_h3_narrow(const radmmm_rowgemm_h3_desc& d, const h3_plan& pl, hipStream_t stream);   // rowgemm_h3.hip
+int launch_h3d_pr1(const radmmm_rowgemm_h3_desc& d, const h3_plan& pl, hipStream_t stream);   // rowgemm_h3w_pr{1,2,3}.hip: all (tile
+int launch_h3d_pr2(const radmmm_rowgemm_h3_desc& d, const h3_plan& pl, hipStream_t stream);   // height, epilogue kind) instantiations
+int launch_h3d_pr3(const radmmm_rowgemm_h3_desc& d, const h3_plan& pl, hipStream_t stream);   // of one product scheme
+int launch_rowgemm_win(const radmmm_rowgemm_h3_desc& d, const h3_plan& pl, hipStream_t stream);   // rowgemm_win.hip
+int launch_rowgemm_one(const radmmm_rowgemm_h3_desc& d, const h3_plan& pl, hipStream_t stream);   // rowgemm_one.hip
 int gemm_cu_slots();
 // the kernel the calling thread's last radmmm_rowgemm_h3 launch took (radmmm_rowgemm_h3_last_kernel; error.cpp)
 extern thread_local int g_h3_last_kernel;

@@ -14,8 +14,6 @@
 // buffer loads: per-thread byte offsets change only with the tap, the K position is a scalar
 // offset, masked / out-of-item frames get an out-of-range offset (zeros from the buffer unit).
 // Both operands are K-contiguous; the data-gradient uses a transposed split copy of the weights.
-#include <stdlib.h>
-
 #include "common.h"
 #include "rowgemm_epilogue.h"
 
@@ -177,68 +175,8 @@ __global__ __launch_bounds__(256, 2) void rowgemm_h3_kernel(const radmmm_rowgemm
 
 }  // namespace
 
-// Which kernel a descriptor takes -- ONE decision for the launcher and for radmmm_rowgemm_h3_colsum_rows (the two had
-// drifted apart under the RADMMM_H3_1X1 experiment switch).  Default: the wide-tile kernel (rowgemm_h3w.hip), one workgroup per
-// CU.  A small batch does not give it enough tiles (M = 3200: 100 workgroups of its smallest 128 x 256 tile on 256 CUs): below
-// half a round this file's 128 x 128 kernel, two workgroups per CU, is faster (B = 8, T = 800: 40.0 vs 43.9 ms per step).
-// RADMMM_H3_TILE=128 / 256 forces one or the other (A/B runs; RADMMM_DEBUG=1 only, read per launch then: tests switch it).
-static bool takes_narrow_kernel(const radmmm_rowgemm_h3_desc& d) {
-  const radmmm_rowgemm_desc& p = d.base;
-  const char* forced_env = radmmm::debug_env("RADMMM_H3_TILE");
-  const int forced = forced_env ? atoi(forced_env) : 0;
-  static const bool narrow_1x1 = [] {                 // experiment: short-K launches on the 2-workgroup-per-CU kernel
-    const char* e = radmmm::debug_env("RADMMM_H3_1X1");
-    return e && atoi(e) == 128;
-  }();
-  const long long wide_wgs = (long long)((p.M + 127) / 128) * ((p.N + 255) / 256);
-  // (the FP8 cross-term scheme exists on the wide kernel only)
-  if (d.nprod == 2 || d.extra_tap) return false;
-  return forced == 128 || (forced != 256 && wide_wgs < 128) || (narrow_1x1 && p.taps == 1);
-}
-
-extern "C" int radmmm_rowgemm_h3(const radmmm_rowgemm_h3_desc* d, radmmm_stream_t stream) {
-  RADMMM_REQUIRE(d != nullptr, "rowgemm_h3: null descriptor");
-  const radmmm_rowgemm_desc& p = d->base;
-  RADMMM_REQUIRE(d->Ah && d->Al && d->Bh && d->Bl, "rowgemm_h3: null operand");
-  RADMMM_REQUIRE(p.C || p.Ch, "rowgemm_h3: C may be NULL only when the split copy Ch / Cl carries the result");
-  RADMMM_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0 && p.taps >= 1 && p.T > 0 && p.M % p.T == 0, "rowgemm_h3: bad dims");
-  RADMMM_REQUIRE(p.K % BK == 0, "rowgemm_h3: K=%d must be a multiple of 32", p.K);
-  RADMMM_REQUIRE(p.b_layout == 0, "rowgemm_h3: both operands are K-contiguous (use a transposed weight copy)");
-  RADMMM_REQUIRE(p.a_item_stride == 0, "rowgemm_h3: a_item_stride is not supported");
-  RADMMM_REQUIRE(d->lda_h % 8 == 0 && d->ldb_h % 8 == 0 && d->lda_h >= p.K && d->ldb_h >= p.K && d->b_tap_stride_h % 8 == 0,
-                 "rowgemm_h3: split operands need ld %% 8 == 0 and ld >= K");
-  RADMMM_REQUIRE(radmmm::aligned16(d->Ah) && radmmm::aligned16(d->Al) && radmmm::aligned16(d->Bh) && radmmm::aligned16(d->Bl),
-                 "rowgemm_h3: split operands must be 16B aligned");
-  RADMMM_REQUIRE(p.sign == 1 || p.sign == -1, "rowgemm_h3: sign must be +-1");
-  RADMMM_REQUIRE(!(p.pconv || p.rowscale == 2) || (p.ratio_taps >= 1 && p.ratio_dil >= 1), "rowgemm_h3: ratio_taps/ratio_dil");
-  RADMMM_REQUIRE(!p.dact || (p.dact_src != nullptr) != (p.dact_h != nullptr), "rowgemm_h3: dact needs dact_src or the pair dact_h / dact_x");
-  RADMMM_REQUIRE(!p.dact_h || (p.dact_x && p.lddact_h % 32 == 0 && p.lddact_h >= p.N && abs(p.dact_x8_exp) <= 16 &&
-                               (reinterpret_cast<uintptr_t>(p.dact_h) & 3) == 0 && (reinterpret_cast<uintptr_t>(p.dact_x) & 3) == 0),
-                 "rowgemm_h3: dact_h / dact_x: an 8-bit split pair with ld %% 32 == 0");
-  RADMMM_REQUIRE(!p.Ch || (p.Cl && p.ldch % 4 == 0 && p.ldch >= ((p.N + 3) & ~3)), "rowgemm_h3: Ch/Cl");
-  RADMMM_REQUIRE(p.n_c2_src >= 0 && p.n_c2_src <= 3, "rowgemm_h3: n_c2_src must be 0 .. 3");
-  for (int k = 0; k < p.n_c2_src; ++k)
-    RADMMM_REQUIRE(p.c2_src[k] && radmmm::aligned16(p.c2_src[k]), "rowgemm_h3: c2_src[%d] null / not 16-byte aligned", k);
-  RADMMM_REQUIRE(p.n_c2_src == 0 || ((p.C2 || p.C2h) && p.ldc2 % 4 == 0 && p.ldc2 >= p.N),
-                 "rowgemm_h3: c2_src needs C2 or C2h to receive the sum, and the sources' pitch in ldc2");
-  RADMMM_REQUIRE(!p.C2h || (p.C2l && (p.C2 || p.n_c2_src > 0) && p.ldc2h % 4 == 0 && p.ldc2h >= ((p.N + 3) & ~3)), "rowgemm_h3: C2h/C2l");
-  RADMMM_REQUIRE(p.split_fmt >= RADMMM_SPLIT_F16 && p.split_fmt <= RADMMM_SPLIT_X8B, "rowgemm_h3: split_fmt");
-  RADMMM_REQUIRE(p.split_fmt == RADMMM_SPLIT_F16 || ((!p.Ch || p.ldch % 32 == 0) && (!p.C2h || p.ldc2h % 32 == 0) &&
-                                                      abs(p.ch_x8_exp) <= 16 && abs(p.c2h_x8_exp) <= 16),
-                 "rowgemm_h3: 8-bit split outputs need ld %% 32 == 0 and |x8_exp| <= 16");
-  RADMMM_REQUIRE(d->nprod >= 0 && d->nprod <= 3, "rowgemm_h3: nprod");
-  RADMMM_REQUIRE(!p.colsum_out || (p.colsum_scratch && !p.add && !p.C2 && !p.n_c2_src), "rowgemm_h3: colsum_out needs colsum_scratch (and no add / C2 input)");
-  RADMMM_REQUIRE(d->nprod != 2 || (abs(d->a8_exp) <= 16 && abs(d->b8_exp) <= 16 && d->lda_h % 32 == 0 && d->ldb_h % 32 == 0 &&
-                                   d->b_tap_stride_h % 32 == 0),
-                 "rowgemm_h3: nprod 2 needs ld %% 32 == 0 and |x8_exp| <= 16");
-  RADMMM_REQUIRE(!d->extra_tap || (d->extra_a_rows >= p.M && p.taps >= 1 && !p.a_mask_mode),
-                 "rowgemm_h3: the extra K segment needs extra_a_rows >= M (second matrix behind the first) and a_mask_mode 0");
-  const int ntaps = p.taps + (d->extra_tap ? 1 : 0);
-  const long long a_bytes = ((long long)p.M + (d->extra_tap ? d->extra_a_rows : 0)) * d->lda_h * 2;
-  const long long b_bytes = ((long long)(ntaps - 1) * d->b_tap_stride_h + (long long)p.N * d->ldb_h) * 2;
-  RADMMM_REQUIRE(a_bytes < 0x7fffffffLL && b_bytes < 0x7fffffffLL, "rowgemm_h3: operand >= 2 GiB");
-  if (!takes_narrow_kernel(*d))
-    return radmmm::launch_rowgemm_h3w(*d, static_cast<hipStream_t>(stream), (int)a_bytes, (int)b_bytes);
+// the launch of a descriptor that plan_rowgemm_h3 (rowgemm_h3w.hip) sent to this file's kernel
+int radmmm::launch_rowgemm_h3_narrow(const radmmm_rowgemm_h3_desc& d, const h3_plan& pl, hipStream_t stream) {
   static int once = [] {
     for (const void* fn : {reinterpret_cast<const void*>(rowgemm_h3_kernel<false>),
                            reinterpret_cast<const void*>(rowgemm_h3_kernel<true>)}) {
@@ -251,31 +189,14 @@ extern "C" int radmmm_rowgemm_h3(const radmmm_rowgemm_h3_desc* d, radmmm_stream_
     return 0;
   }();
   if (once) return once;
-  radmmm::g_h3_last_kernel = RADMMM_H3_KERNEL_CODE(RADMMM_H3_FAMILY_NARROW, d->nprod == 1 ? 1 : 3, BM / 32, 0);
+  const radmmm_rowgemm_desc& p = d.base;
   const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
-  // nprod 1 must not touch Al / Bl: a caller without lo halves passes the hi arrays for both pointers
-  if (d->nprod == 1)
-    hipLaunchKernelGGL(rowgemm_h3_kernel<true>, dim3(ntm * ntn), dim3(256), SMEM_BYTES, static_cast<hipStream_t>(stream),
-                       *d, (int)a_bytes, (int)b_bytes);
+  // one product must not touch Al / Bl: a caller without lo halves passes the hi arrays for both pointers
+  if (pl.products == 1)
+    hipLaunchKernelGGL(rowgemm_h3_kernel<true>, dim3(ntm * ntn), dim3(256), SMEM_BYTES, stream, d, pl.a_bytes, pl.b_bytes);
   else
-    hipLaunchKernelGGL(rowgemm_h3_kernel<false>, dim3(ntm * ntn), dim3(256), SMEM_BYTES, static_cast<hipStream_t>(stream),
-                       *d, (int)a_bytes, (int)b_bytes);
-  const int rc = radmmm::check_launch("rowgemm_h3");
-  if (rc || !p.colsum_out) return rc;
-  RADMMM_REQUIRE(p.C, "rowgemm_h3: colsum_out on this kernel sums C afterwards: C must not be NULL");
-  return radmmm_colsum(p.C, p.ldc, p.colsum_out, p.colsum_scratch, p.M, p.N, p.rowscale == 2 ? 2 : (p.rowscale == 1 ? 1 : 0), p.T,
-                       p.lens, p.ratio_taps, p.ratio_dil, 0, stream);
-}
-
-namespace radmmm { int h3w_colsum_rows(const radmmm_rowgemm_h3_desc& d); }
-// rows of partial column sums a launch of *d leaves in colsum_scratch when colsum_out is NULL (include/radmmm_hip.h); 0 = this
-// descriptor takes a kernel that leaves none (generic epilogue, the narrow kernel): give it colsum_out
-extern "C" int radmmm_rowgemm_h3_colsum_rows(const radmmm_rowgemm_h3_desc* d) {
-  if (!d) return 0;
-  const radmmm_rowgemm_desc& p = d->base;
-  if (p.M <= 0 || p.N <= 0 || !p.colsum_scratch) return 0;
-  if (takes_narrow_kernel(*d)) return 0;
-  return radmmm::h3w_colsum_rows(*d);
+    hipLaunchKernelGGL(rowgemm_h3_kernel<false>, dim3(ntm * ntn), dim3(256), SMEM_BYTES, stream, d, pl.a_bytes, pl.b_bytes);
+  return radmmm::check_launch("rowgemm_h3");
 }
 
 // scratch of the optional column sums (radmmm_rowgemm_desc.colsum_scratch): one partial row per row tile of the smallest

@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "rowgemm_epilogue.h"
+#include "rowgemm_h3_tiles.h"
 #include "split_pack.h"
 
 namespace {
@@ -34,7 +35,7 @@ typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ f32x16 mfma_f16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
-constexpr int BN = 256, BK = 32, ROWB = 64;
+constexpr int ROWB = 64;                        // bytes of an LDS row: BK halves (BN, BK: rowgemm_h3_tiles.h)
 constexpr int OOB = 0x7fffffff;
 
 // -DRADMMM_PHASE_TIMERS (measurement builds only, tools/phase_probe.py): every workgroup records the 100 MHz wall clock
@@ -112,12 +113,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-//   EK_GENERIC  LDS-parking epilogue, every descriptor option
-//   EK_PLAIN    C                                   (bias, row factors, activation)
-//   EK_SPLIT    C + split copy Ch / Cl (/ Clo)
-//   EK_RES      C + C2 (+)= y (+ split copy C2h / C2l)     side input: C2 when accumulating
-//   EK_DGRAD    C + split copy, y multiplied by act'(dact_src)   side input: dact_src
-enum { EK_GENERIC = 0, EK_PLAIN, EK_SPLIT, EK_RES, EK_DGRAD, EK_COUNT };
+// (the kinds EK_*: rowgemm_h3_tiles.h)
 
 // f(integral_constant<int, I>) for I = First, First + Step, ... < Last: loop indices that are constants INSIDE a lambda (an index
 // that is a run-time parameter until inlining keeps a register array in scratch memory)
@@ -878,18 +874,18 @@ int launch_ek(int ek, const radmmm_rowgemm_h3_desc& d, hipStream_t stream, int a
   }
 }
 
-// every (row blocks per workgroup, epilogue kind) instantiation of one product scheme
+// every (row blocks per workgroup, epilogue kind) instantiation of one product scheme; the plan (rowgemm_h3w.hip) names one
 template <int PR>
-int launch_pr(int mb, int ek, const radmmm_rowgemm_h3_desc& d, hipStream_t stream, int a_bytes, int b_bytes) {
-#ifdef RADMMM_QUICK                                    // development builds: one tile height only
-  return launch_ek<7, PR>(ek, d, stream, a_bytes, b_bytes);
+int launch_pr(const radmmm_rowgemm_h3_desc& d, const radmmm::h3_plan& pl, hipStream_t stream) {
+#ifdef RADMMM_QUICK                                    // development builds: one tile height only (the plan pins it)
+  return launch_ek<7, PR>(pl.ek, d, stream, pl.a_bytes, pl.b_bytes);
 #else
-  switch (mb) {
-    case 4: return launch_ek<4, PR>(ek, d, stream, a_bytes, b_bytes);
-    case 5: return launch_ek<5, PR>(ek, d, stream, a_bytes, b_bytes);
-    case 6: return launch_ek<6, PR>(ek, d, stream, a_bytes, b_bytes);
-    case 7: return launch_ek<7, PR>(ek, d, stream, a_bytes, b_bytes);
-    default: return launch_ek<8, PR>(ek, d, stream, a_bytes, b_bytes);
+  switch (pl.mb) {
+    case 4: return launch_ek<4, PR>(pl.ek, d, stream, pl.a_bytes, pl.b_bytes);
+    case 5: return launch_ek<5, PR>(pl.ek, d, stream, pl.a_bytes, pl.b_bytes);
+    case 6: return launch_ek<6, PR>(pl.ek, d, stream, pl.a_bytes, pl.b_bytes);
+    case 7: return launch_ek<7, PR>(pl.ek, d, stream, pl.a_bytes, pl.b_bytes);
+    default: return launch_ek<8, PR>(pl.ek, d, stream, pl.a_bytes, pl.b_bytes);
   }
 #endif
 }

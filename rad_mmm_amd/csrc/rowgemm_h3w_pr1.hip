@@ -2,7 +2,5 @@
 #include "rowgemm_h3w_kernel.h"
 
 namespace radmmm {
-int launch_h3d_pr1(int mb, int ek, const radmmm_rowgemm_h3_desc& d, hipStream_t stream, int a_bytes, int b_bytes) {
-  return launch_pr<1>(mb, ek, d, stream, a_bytes, b_bytes);
-}
+int launch_h3d_pr1(const radmmm_rowgemm_h3_desc& d, const h3_plan& pl, hipStream_t stream) { return launch_pr<1>(d, pl, stream); }
 }  // namespace radmmm

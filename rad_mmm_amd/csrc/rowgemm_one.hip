@@ -4,7 +4,7 @@
 // instruction order, no address arithmetic in the loop (in-step 1-tap launches of round 3: ~100 us for 26.8 GFLOP, the K
 // loop of 32 steps at ~1.7 us each against 1.08 us of MFMA work).
 // Scope: nprod 2, taps = 1, no extra K segment, K / 32 even, epilogue kinds PLAIN / SPLIT / RES / DGRAD, MB 4 .. 8;
-// everything else keeps rowgemm_h3d (rowgemm_h3w.hip decides; RADMMM_ONE=0 under RADMMM_DEBUG forces it).
+// everything else keeps rowgemm_h3d (rowgemm_h3w.hip plan_rowgemm_h3 decides; RADMMM_ONE=0 under RADMMM_DEBUG forces it).
 #include <type_traits>
 
 #include "rowgemm_onetap.h"
@@ -116,45 +116,36 @@ int launch_one(const radmmm_rowgemm_h3_desc& d, hipStream_t stream, int a_bytes,
 }
 
 template <int MB>
-int launch_one_ek(int ek, const radmmm_rowgemm_h3_desc& d, hipStream_t stream, int a_bytes, int b_bytes) {
-  switch (ek) {
-    case EK_SPLIT: return launch_one<MB, EK_SPLIT>(d, stream, a_bytes, b_bytes);
-    case EK_RES: return launch_one<MB, EK_RES>(d, stream, a_bytes, b_bytes);
-    case EK_DGRAD: return launch_one<MB, EK_DGRAD>(d, stream, a_bytes, b_bytes);
-    default: return launch_one<MB, EK_PLAIN>(d, stream, a_bytes, b_bytes);
+int launch_one_ek(const radmmm_rowgemm_h3_desc& d, const radmmm::h3_plan& pl, hipStream_t stream) {
+  switch (pl.ek) {
+    case EK_SPLIT: return launch_one<MB, EK_SPLIT>(d, stream, pl.a_bytes, pl.b_bytes);
+    case EK_RES: return launch_one<MB, EK_RES>(d, stream, pl.a_bytes, pl.b_bytes);
+    case EK_DGRAD: return launch_one<MB, EK_DGRAD>(d, stream, pl.a_bytes, pl.b_bytes);
+    default: return launch_one<MB, EK_PLAIN>(d, stream, pl.a_bytes, pl.b_bytes);
   }
 }
 
 }  // namespace
 
 namespace radmmm {
-bool rowgemm_one_ok(int mb, int ek, const radmmm_rowgemm_h3_desc& d) {
-  const radmmm_rowgemm_desc& p = d.base;
-#ifdef RADMMM_QUICK
-  if (mb != 7) return false;
+// the plan's (tile height, epilogue kind, scheme) -> the instantiation.  plan_rowgemm_h3 sends here: the FP8-cross scheme
+// with MB 4 .. 8 and every direct kind; three f16 products with MB 7 / 8 and PLAIN only.
+int launch_rowgemm_one(const radmmm_rowgemm_h3_desc& d, const h3_plan& pl, hipStream_t stream) {
+  if (pl.products != 2) {
+#ifndef RADMMM_QUICK                                   // (development builds: the plan pins tile height 7)
+    if (pl.mb == 8) return launch_one<8, EK_PLAIN, 3>(d, stream, pl.a_bytes, pl.b_bytes);
 #endif
-  // (three f16 products, round 5: the C-only launches of the tall tiles -- the FiLM stacks' 1x1 convs and their data
-  //  gradients at configs[4]'s 32 000 rows, the context LSTM's projection -- take the slot-pinned loop as well)
-  const bool scheme_ok = d.nprod == 2 || ((d.nprod == 3 || d.nprod == 0) && (mb == 7 || mb == 8) && ek == EK_PLAIN);
-  return scheme_ok && mb >= 4 && mb <= 8 && (ek == EK_PLAIN || ek == EK_SPLIT || ek == EK_RES || ek == EK_DGRAD) && p.taps == 1 &&
-         !d.extra_tap && (p.K / BK) % 2 == 0 && p.K >= 2 * BK && (!(p.a_mask_mode && p.lens) || (p.T > 0 && p.M % p.T == 0));
-}
-int launch_rowgemm_one(int mb, int ek, const radmmm_rowgemm_h3_desc& d, hipStream_t stream, int a_bytes, int b_bytes) {
-  if (d.nprod != 2) {                                 // three f16 products: EK_PLAIN, MB 7 / 8 (rowgemm_one_ok)
-#ifndef RADMMM_QUICK
-    if (mb == 8) return launch_one<8, EK_PLAIN, 3>(d, stream, a_bytes, b_bytes);
-#endif
-    return launch_one<7, EK_PLAIN, 3>(d, stream, a_bytes, b_bytes);
+    return launch_one<7, EK_PLAIN, 3>(d, stream, pl.a_bytes, pl.b_bytes);
   }
 #ifndef RADMMM_QUICK
-  switch (mb) {
-    case 4: return launch_one_ek<4>(ek, d, stream, a_bytes, b_bytes);
-    case 5: return launch_one_ek<5>(ek, d, stream, a_bytes, b_bytes);
-    case 6: return launch_one_ek<6>(ek, d, stream, a_bytes, b_bytes);
-    case 8: return launch_one_ek<8>(ek, d, stream, a_bytes, b_bytes);
+  switch (pl.mb) {
+    case 4: return launch_one_ek<4>(d, pl, stream);
+    case 5: return launch_one_ek<5>(d, pl, stream);
+    case 6: return launch_one_ek<6>(d, pl, stream);
+    case 8: return launch_one_ek<8>(d, pl, stream);
     default: break;
   }
 #endif
-  return launch_one_ek<7>(ek, d, stream, a_bytes, b_bytes);
+  return launch_one_ek<7>(d, pl, stream);
 }
 }  // namespace radmmm

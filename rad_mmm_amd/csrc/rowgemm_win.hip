@@ -26,14 +26,13 @@
 // interleaved for the direct epilogue (rowgemm_h3w_kernel.h), one barrier per K step, pinned instruction order.
 // Scope: taps = 5, dilation <= 8, FP8-cross scheme, epilogue kinds PLAIN / SPLIT / DGRAD (the latter also with the extra K
 // segment of the fused data gradient), MB 7 / 8
-// (rowgemm_h3w.hip decides; everything else keeps rowgemm_h3d).
+// (rowgemm_h3w.hip plan_rowgemm_h3 decides; everything else keeps rowgemm_h3d).
 #include <type_traits>
 
 #include "rowgemm_onetap.h"
 
 namespace {
 
-constexpr int WTAPS = 5, WDMAX = 8;
 #ifndef RADMMM_WIN_LOOKAHEAD
 #define RADMMM_WIN_LOOKAHEAD 2
 #endif
@@ -360,35 +359,26 @@ int launch_win(const radmmm_rowgemm_h3_desc& d, hipStream_t stream, int a_bytes,
   return radmmm::check_launch("rowgemm_win");
 }
 
+// the plan's (tile height, epilogue kind, scheme) -> the instantiation.  plan_rowgemm_h3 sends here: MB 7 / 8; the FP8-cross
+// scheme with PLAIN / SPLIT / DGRAD, with the extra K segment DGRAD only; three f16 products with PLAIN only.
 template <int MB>
-int launch_win_ek(int ek, const radmmm_rowgemm_h3_desc& d, hipStream_t stream, int a_bytes, int b_bytes) {
-  if (d.nprod != 2) return launch_win<MB, EK_PLAIN, false, 3>(d, stream, a_bytes, b_bytes);   // (rowgemm_win_ok: this kind only)
-  if (d.extra_tap) return launch_win<MB, EK_DGRAD, true>(d, stream, a_bytes, b_bytes);      // (rowgemm_win_ok: this kind only)
-  switch (ek) {
-    case EK_SPLIT: return launch_win<MB, EK_SPLIT, false>(d, stream, a_bytes, b_bytes);
-    case EK_DGRAD: return launch_win<MB, EK_DGRAD, false>(d, stream, a_bytes, b_bytes);
-    default: return launch_win<MB, EK_PLAIN, false>(d, stream, a_bytes, b_bytes);
+int launch_win_ek(const radmmm_rowgemm_h3_desc& d, const radmmm::h3_plan& pl, hipStream_t stream) {
+  if (pl.products != 2) return launch_win<MB, EK_PLAIN, false, 3>(d, stream, pl.a_bytes, pl.b_bytes);
+  if (d.extra_tap) return launch_win<MB, EK_DGRAD, true>(d, stream, pl.a_bytes, pl.b_bytes);
+  switch (pl.ek) {
+    case EK_SPLIT: return launch_win<MB, EK_SPLIT, false>(d, stream, pl.a_bytes, pl.b_bytes);
+    case EK_DGRAD: return launch_win<MB, EK_DGRAD, false>(d, stream, pl.a_bytes, pl.b_bytes);
+    default: return launch_win<MB, EK_PLAIN, false>(d, stream, pl.a_bytes, pl.b_bytes);
   }
 }
 
 }  // namespace
 
 namespace radmmm {
-// can this launch take the shared-window kernel?  (mb, ek as chosen by rowgemm_h3w.hip)
-bool rowgemm_win_ok(int mb, int ek, const radmmm_rowgemm_h3_desc& d) {
-  const radmmm_rowgemm_desc& p = d.base;
-#ifdef RADMMM_QUICK
-  if (mb != 7) return false;
+int launch_rowgemm_win(const radmmm_rowgemm_h3_desc& d, const h3_plan& pl, hipStream_t stream) {
+#ifndef RADMMM_QUICK                                   // (development builds: the plan pins tile height 7)
+  if (pl.mb == 8) return launch_win_ek<8>(d, pl, stream);
 #endif
-  // (three f16 products, round 5: C-only launches without the extra segment -- the FiLM stacks' 5-tap hidden convs)
-  const bool scheme_ok = d.nprod == 2 || ((d.nprod == 3 || d.nprod == 0) && ek == EK_PLAIN && !d.extra_tap);
-  return scheme_ok && (mb == 7 || mb == 8) && (ek == EK_PLAIN || ek == EK_SPLIT || ek == EK_DGRAD) && p.taps == WTAPS &&
-         (!d.extra_tap || (ek == EK_DGRAD && !p.a_mask_mode)) && (p.K / BK) % 2 == 0 && p.dil >= 1 && p.dil <= WDMAX && p.T >= 32 * mb && p.M % p.T == 0 && (p.sign == 1 || p.sign == -1);
-}
-int launch_rowgemm_win(int mb, int ek, const radmmm_rowgemm_h3_desc& d, hipStream_t stream, int a_bytes, int b_bytes) {
-#ifndef RADMMM_QUICK
-  if (mb == 8) return launch_win_ek<8>(ek, d, stream, a_bytes, b_bytes);
-#endif
-  return launch_win_ek<7>(ek, d, stream, a_bytes, b_bytes);
+  return launch_win_ek<7>(d, pl, stream);
 }
 }  // namespace radmmm

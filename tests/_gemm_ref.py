@@ -245,13 +245,15 @@ def _case(**kw):
     return c
 
 
+# the switches a case's `env` may set: a test clears them all before it applies a case's (RADMMM_DEBUG=1 is the session's)
+ROWGEMM_SWITCHES = ("RADMMM_H3_TILE", "RADMMM_H3W_MB", "RADMMM_SLOT3", "RADMMM_WIN", "RADMMM_ONE", "RADMMM_WIN_XT", "RADMMM_H3_1X1")
 _WIDE_OFF = {"RADMMM_H3_TILE": "256", "RADMMM_SLOT3": "0", "RADMMM_WIN": "0", "RADMMM_ONE": "0"}
 _EXPS = [(X8_ACT_EXP, X8_W_EXP, 2.0 ** -8), (X8_GRAD_EXP, X8_W_EXP, 2.0 ** -19), (-3, 1, 2.0 ** -10), (1, -2, 2.0 ** -6)]
 _EK_NAME = {EK_GENERIC: "generic", EK_PLAIN: "plain", EK_SPLIT: "split", EK_RES: "res", EK_DGRAD: "dgrad"}
 
 
 def _epilogue_of(ek, i, nprod):
-    """descriptor options that make the launcher pick epilogue kind ek (rowgemm_h3w.hip decide_h3w)"""
+    """descriptor options that make the launcher pick epilogue kind ek (rowgemm_h3w.hip pick_h3w_ek)"""
     if ek == EK_GENERIC:          # odd pitch of C: no direct kernel takes it; every option at once
         return dict(odd_ldc=True, bias=True, postmask=1, split=True, c2="accum" if i % 2 else "store")
     if ek == EK_PLAIN:
@@ -336,14 +338,73 @@ def _ints(g, shape, lim, scale):
     return (v * scale).float()
 
 
+def rowgemm_layout(c):
+    """pitches and formats of case c's arrays (a RowGemmProblem without data: what the descriptor says about them)"""
+    p = RowGemmProblem()
+    p.lda = c["K"] + 32
+    p.ldb = c["K"] + 64
+    p.Nalloc = c["N"] + 3                                        # B rows >= N of every tap are poison
+    if c["split"]:
+        p.split_fmt = SPLIT_X8A if c["nprod"] == 2 else SPLIT_F16
+        p.ldch = ((c["N"] + 31) // 32) * 32 + 32
+    return p
+
+
+def out_pitches(c):
+    """(ldc, ldc2) of a launch of case c"""
+    return c["N"] + (7 if c["odd_ldc"] else 6), (c["N"] + 3) // 4 * 4 + 4
+
+
+def rowgemm_operands(c):
+    """names of the arrays a launch of case c takes (c2_src: a list of three)"""
+    names = ["Ah", "Al", "Bh", "Bl", "lens", "C"]
+    names += ["bias"] if c["bias"] else []
+    names += ["dact_src"] if c["dact"] else []
+    names += ["C2"] if c["c2"] else []
+    names += ["c2_src"] if c["c2"] == "src3" else []
+    names += ["Ch", "Cl"] if c["split"] else []
+    names += ["Clo"] if c["split"] and c["clo"] else []
+    return names
+
+
+def standin_addresses(c):
+    """an aligned address per array of case c, for the host-only plan query (it never looks behind a pointer)"""
+    arr = {name: 0x10000 + 0x1000 * i for i, name in enumerate(rowgemm_operands(c))}
+    if "c2_src" in arr:
+        arr["c2_src"] = [arr["c2_src"] + 0x100 * k for k in range(3)]
+    return arr
+
+
+def rowgemm_kw(c, p, arr):
+    """keywords of rad_mmm_amd._lib.rowgemm_h3 / rowgemm_h3_plan for case c with the layout of p (rowgemm_layout, or a problem
+    with pitches of its own) on the arrays arr[name]: device tensors for a launch, anything with an address for the plan"""
+    assert sorted(arr) == sorted(rowgemm_operands(c))
+    ldc, ldc2 = out_pitches(c)
+    kw = dict(Ah=arr["Ah"], Al=arr["Al"], lda_h=p.lda, Bh=arr["Bh"], Bl=arr["Bl"], ldb_h=p.ldb, b_tap_stride_h=p.Nalloc * p.ldb,
+              acc_scale=c["acc_scale"], nprod=c["nprod"], a8_exp=c["a8_exp"], b8_exp=c["b8_exp"], extra_tap=c["extra_tap"],
+              extra_a_rows=c.get("extra_a_rows", 0), C=arr["C"], ldc=ldc, M=c["M"], N=c["N"], K=c["K"], taps=c["taps"], dil=c["dil"],
+              sign=c["sign"], T=c["T"], lens=arr["lens"], a_mask_mode=c["a_mask_mode"], premask=c["premask"], postmask=c["postmask"],
+              rowscale=c["rowscale"])
+    if c["bias"]:
+        kw["bias"] = arr["bias"]
+    if c["dact"]:
+        kw.update(dact=c["dact"], dact_src=arr["dact_src"], lddact=c["N"])
+    if c["c2"]:
+        kw.update(C2=arr["C2"], ldc2=ldc2, c2_accum=1 if c["c2"] == "accum" else 0)
+        if c["c2"] == "src3":
+            kw["c2_src"] = arr["c2_src"]
+    if c["split"]:
+        kw.update(Ch=arr["Ch"], Cl=arr["Cl"], ldch=p.ldch, ch_scale=c["ch_scale"], split_fmt=p.split_fmt, ch_x8_exp=c["ch_x8_exp"])
+        if c["clo"]:
+            kw["Clo"] = arr["Clo"]
+    return kw
+
+
 def build_rowgemm(c, seed=0):
     g = torch.Generator().manual_seed(1000 + seed + sum(map(ord, c["name"])))
-    p = RowGemmProblem()
+    p = rowgemm_layout(c)
     M, N, K, T = c["M"], c["N"], c["K"], c["T"]
     x8 = c["nprod"] == 2
-    p.lda = K + 32
-    p.ldb = K + 64
-    p.Nalloc = N + 3                                             # B rows >= N of every tap are poison
     nt = c["taps"] + (1 if c["extra_tap"] else 0)
     rowsA = c["extra_a_rows"] + M + 2 if c["extra_tap"] else M + 4
     p.A = gen_split(rowsA, p.lda, g, c["lo_log2"], c["a8_exp"] if x8 else None)
@@ -379,10 +440,7 @@ def build_rowgemm(c, seed=0):
         p.C2 = to_f32_exact(out["C2"]) if p.budget < BUDGET else out["C2"].float()
     p.split = None
     if c["split"]:
-        fmt = SPLIT_X8A if x8 else SPLIT_F16
-        p.split_fmt = fmt
-        p.ldch = ((N + 31) // 32) * 32 + 32
-        p.split = split_ref(p.C, c["ch_scale"], fmt, c["ch_x8_exp"])
+        p.split = split_ref(p.C, c["ch_scale"], p.split_fmt, c["ch_x8_exp"])
     return p
 
 

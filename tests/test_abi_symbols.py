@@ -101,6 +101,43 @@ def test_rowgemm_h3_kernel_query_without_gpu():
     assert L.h3_kernel_code(L.H3_WIN, 2, 7, L.EK_DGRAD) == 3274
 
 
+def test_h3_plan_query_without_gpu(monkeypatch):
+    """radmmm_rowgemm_h3_plan shares the entry point's validation and decision: a null or a refused descriptor gives the entry
+    point's code and error text, an accepted one the header's kernel code.  Only refused descriptors go to the entry point
+    itself: an accepted one would launch on the stand-in addresses where there is a GPU."""
+    import pytest
+    import rad_mmm_amd._lib as L
+    lib = L.lib
+    for k in ("RADMMM_H3_TILE", "RADMMM_H3W_MB", "RADMMM_SLOT3", "RADMMM_WIN", "RADMMM_ONE", "RADMMM_WIN_XT"):
+        monkeypatch.delenv(k, raising=False)
+    assert lib.radmmm_rowgemm_h3_plan(None) == -1 and lib.radmmm_last_error() == b"rowgemm_h3: null descriptor"
+    assert lib.radmmm_rowgemm_h3(None, None) == -1 and lib.radmmm_last_error() == b"rowgemm_h3: null descriptor"
+    a = 0x10000                                                  # never dereferenced
+    ok = dict(Ah=a, Al=a, Bh=a, Bl=a, C=a, lda_h=64, ldb_h=64, b_tap_stride_h=64 * 512, ldc=512, M=4096, N=512, K=64, T=512)
+    refused = [(dict(ok, Al=None), b"rowgemm_h3: null operand"),
+               (dict(ok, K=48), b"rowgemm_h3: K=48 must be a multiple of 32"),
+               (dict(ok, b_layout=1), b"rowgemm_h3: both operands are K-contiguous"),
+               (dict(ok, sign=0), b"rowgemm_h3: sign must be +-1"),
+               (dict(ok, nprod=2, lda_h=72), b"rowgemm_h3: nprod 2 needs ld % 32 == 0")]
+    for kw, text in refused:
+        d = L._h3_desc(kw, L._addr)
+        assert lib.radmmm_rowgemm_h3_plan(ctypes.byref(d)) == -1 and lib.radmmm_last_error().startswith(text)
+        mine = lib.radmmm_last_error()
+        assert lib.radmmm_rowgemm_h3(ctypes.byref(d), None) == -1 and lib.radmmm_last_error() == mine
+        assert lib.radmmm_rowgemm_h3_colsum_rows(ctypes.byref(L._h3_desc(dict(kw, colsum_scratch=a), L._addr))) == 0
+    with pytest.raises(L.RadmmmError, match="null operand"):
+        L.rowgemm_h3_plan(**dict(ok, Al=None))
+    # 8 x 2 tiles of 128 x 256 are fewer than 128 workgroups: the narrow kernel; 128 x 2 are not: the wide tiles (their
+    # height pinned here: the cost model's choice follows the CU count)
+    assert L.rowgemm_h3_plan(**dict(ok, M=1024)) == L.h3_kernel_code(L.H3_NARROW, 3, 4, 0)
+    monkeypatch.setenv("RADMMM_H3W_MB", "7")
+    wide = dict(ok, M=16384, nprod=2)
+    assert L.rowgemm_h3_plan(**dict(wide, taps=5)) == L.h3_kernel_code(L.H3_WIN, 2, 7, L.EK_PLAIN)
+    assert L.rowgemm_h3_plan(**wide) == L.h3_kernel_code(L.H3_ONE, 2, 7, L.EK_PLAIN)
+    assert lib.radmmm_rowgemm_h3_colsum_rows(ctypes.byref(L._h3_desc(dict(wide, colsum_scratch=a), L._addr))) == (16384 + 223) // 224
+    assert "int radmmm_rowgemm_h3_plan(const radmmm_rowgemm_h3_desc* d);" in open(HDR).read()
+
+
 def test_f32_plan_queries_without_gpu():
     """radmmm_rowgemm_f32_plan / radmmm_wgrad_f32_plan make no HIP call and share the entry points' validation: a null or a
     refused descriptor gives the entry point's code and error text, an accepted one the header's kernel code."""

@@ -1,7 +1,8 @@
 """The host model of the split-operand GEMMs (tests/_gemm_ref.py) held to account on the CPU: against
 torch.nn.functional.conv1d in float64 (equality: the values are exact), the bit budget of every operand set the GPU tests
 use (an fp32 accumulation in random term orders equals the float64 result bit for bit), and the model's sensitivity to
-every one of the six operand arrays.  No GPU, no built library."""
+every one of the six operand arrays.  No GPU; the built library is asked one host-only question: which kernel every case of
+the GPU tests' table reaches (radmmm_rowgemm_h3_plan)."""
 import numpy as np
 import pytest
 import torch
@@ -51,6 +52,18 @@ def test_the_matrix_covers_what_it_claims():
         if (c["taps"] // 2) * c["dil"] > 2:
             assert any(1 < l < (c["taps"] // 2) * c["dil"] for l in c["lens"])
     assert {(c["taps"], c["dil"] % 2) for c in WG_CASES} >= {(1, 1), (3, 1), (3, 0), (5, 1), (5, 0)}
+
+
+@pytest.mark.parametrize("c", ROW_CASES, ids=[c["name"] for c in ROW_CASES])
+def test_every_rowgemm_case_reaches_its_kernel(c, monkeypatch):
+    """the plan (host only: stand-in addresses, the MI355X's CU count without a device) names the case's kernel under the
+    switches the case sets -- what tests/test_hip_gemm_direct.py then holds the launch to"""
+    from rad_mmm_amd._lib import rowgemm_h3_plan
+    for k in G.ROWGEMM_SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in c["env"].items():
+        monkeypatch.setenv(k, v)
+    assert rowgemm_h3_plan(**G.rowgemm_kw(c, G.rowgemm_layout(c), G.standin_addresses(c))) == c["expect"]
 
 
 # ---------------------------------------------------------------------------------------------------------------------

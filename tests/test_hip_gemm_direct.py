@@ -5,8 +5,9 @@ every fp32 sum the kernel can form is exact (the case's bit budget is asserted b
 and the output must equal the float64 model BIT FOR BIT, whatever the accumulation order, the tile shape or the matrix
 instruction's internals.  Every input is poison where the kernel must not look (columns past K, masked frames, the
 neighbouring item, weight rows past N, the gap in front of the extra segment); every output starts as a pattern that
-must survive outside [M][N].  Every case asserts the kernel code the launch reports (radmmm_rowgemm_h3_last_kernel): a
-shape that does not reach its kernel fails.
+must survive outside [M][N].  Every case asserts the kernel code the launch reports (radmmm_rowgemm_h3_last_kernel), and
+that it is the one the host plan names for the same keywords (radmmm_rowgemm_h3_plan): a shape that does not reach its
+kernel fails.
 
 Realistic cases, one per kernel family: operands from the producers' model (split_ref) of softplus / Gaussian data at
 scales that are no powers of two; every element within n * 2^-23 * sum |a||b| of the float64 model of the decoded
@@ -73,52 +74,42 @@ def _b_operand(op, x8):
 
 def _launch_rowgemm(c, p, monkeypatch):
     """one radmmm_rowgemm_h3 launch of case c on problem p; returns the output buffers (device) by name"""
-    from rad_mmm_amd._lib import rowgemm_h3, rowgemm_h3_last_kernel
-    for k in ("RADMMM_H3_TILE", "RADMMM_H3W_MB", "RADMMM_SLOT3", "RADMMM_WIN", "RADMMM_ONE", "RADMMM_WIN_XT", "RADMMM_H3_1X1"):
+    from rad_mmm_amd._lib import rowgemm_h3, rowgemm_h3_last_kernel, rowgemm_h3_plan
+    for k in G.ROWGEMM_SWITCHES:
         monkeypatch.delenv(k, raising=False)
     for k, v in c["env"].items():
         monkeypatch.setenv(k, v)
-    M, N, K = c["M"], c["N"], c["K"]
+    M, N = c["M"], c["N"]
     x8 = c["nprod"] == 2
-    Ah, Al = _a_operand(p.A, x8)
-    Bh, Bl = _b_operand(p.B, x8)
-    lens = torch.tensor(c["lens"], dtype=torch.int32, device=DEV)
-    ldc = N + (7 if c["odd_ldc"] else 6)
-    ldc2 = (N + 3) // 4 * 4 + 4
+    ldc, ldc2 = G.out_pitches(c)
     out = {"C": _filled32(M + PAD_ROWS, ldc)}
-    kw = dict(Ah=Ah, Al=Al, lda_h=p.lda, Bh=Bh, Bl=Bl, ldb_h=p.ldb, b_tap_stride_h=p.Nalloc * p.ldb, acc_scale=c["acc_scale"],
-              nprod=c["nprod"], a8_exp=c["a8_exp"], b8_exp=c["b8_exp"], extra_tap=c["extra_tap"], extra_a_rows=c.get("extra_a_rows", 0),
-              C=out["C"], ldc=ldc, M=M, N=N, K=K, taps=c["taps"], dil=c["dil"], sign=c["sign"], T=c["T"], lens=lens,
-              a_mask_mode=c["a_mask_mode"], premask=c["premask"], postmask=c["postmask"], rowscale=c["rowscale"])
-    keep = [Ah, Al, Bh, Bl, lens]
+    arr = {"lens": torch.tensor(c["lens"], dtype=torch.int32, device=DEV)}
+    arr["Ah"], arr["Al"] = _a_operand(p.A, x8)
+    arr["Bh"], arr["Bl"] = _b_operand(p.B, x8)
     if c["bias"]:
-        kw["bias"] = p.side["bias"].to(DEV)
+        arr["bias"] = p.side["bias"].to(DEV)
     if c["dact"]:
-        kw.update(dact=c["dact"], dact_src=p.side["dact_src"].to(DEV).contiguous(), lddact=N)
+        arr["dact_src"] = p.side["dact_src"].to(DEV).contiguous()
     if c["c2"]:
         out["C2"] = _filled32(M + PAD_ROWS, ldc2)
-        kw.update(C2=out["C2"], ldc2=ldc2, c2_accum=1 if c["c2"] == "accum" else 0)
         if c["c2"] == "accum":
             out["C2"][:M, :N] = p.side["C2"].view(torch.int32).to(DEV)
         if c["c2"] == "src3":
-            srcs = []
+            arr["c2_src"] = []
             for s in p.side["c2_src"]:
                 t = torch.full((M, ldc2), 7.0, device=DEV)               # (poison in the pad columns)
                 t[:, :N] = s.to(DEV)
-                srcs.append(t)
-            kw["c2_src"] = srcs
+                arr["c2_src"].append(t)
     if c["split"]:
         out["Ch"] = _filled16(M + PAD_ROWS, p.ldch)
         out["Cl"] = torch.full((M + PAD_ROWS, 2 * p.ldch), FILL8, dtype=torch.uint8, device=DEV) if x8 else _filled16(M + PAD_ROWS, p.ldch)
-        kw.update(Ch=out["Ch"], Cl=out["Cl"], ldch=p.ldch, ch_scale=c["ch_scale"], split_fmt=p.split_fmt, ch_x8_exp=c["ch_x8_exp"])
         if c["clo"]:
             out["Clo"] = _filled16(M + PAD_ROWS, p.ldch)
-            kw["Clo"] = out["Clo"]
-    for v in kw.values():
-        keep.append(v)
+    kw = G.rowgemm_kw(c, p, dict(arr, **out))
     rowgemm_h3(**kw)
     code = rowgemm_h3_last_kernel()
     _sync()
+    assert rowgemm_h3_plan(**kw) == code, "the launch did not take the kernel the plan names for the same keywords"
     return out, code
 
 

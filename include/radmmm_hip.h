@@ -948,6 +948,48 @@ int radmmm_collate_tracks(const float* f0_packed, const float* p_voiced_packed, 
                           int64_t* text, int32_t* scan, const int64_t* meta_src, int64_t* meta_dst, int n_meta, int B,
                           int Tmax, int Lmax, float f0_min, int use_log_f0, int distance_tx, radmmm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Multi-resolution STFT loss (stft_loss.py: STFTLoss.forward, SpectralConvergenceLoss, LogSTFTMagnitudeLoss,
+ * AWeightedLogSTFTMagnitudeLoss with its weights of 1.0), forward and backward (additive entry points of ABI 4).  The
+ * DFT and its data gradient are radmmm_rowgemm_f32 launches (frames x basis, dspec x basis with b_layout 1); these
+ * entry points are what surrounds them.  One resolution: n_fft (even), hop >= 1, win <= n_fft, T samples per item with
+ * T > n_fft/2 (torch.stft's reflect pad of h = n_fft/2 at the padded length T), F = 1 + T/hop frames per item, the
+ * window at columns [left, left + win) of a frame, left = (n_fft - win)/2, cutoff = n_fft/2 + 1 bins.  `frames` is an
+ * int32 device array [B] of valid frames per item, read clamped to [0, F] everywhere, also in the sum S of stftloss_finish
+ * (the reference's semantics for len_ratios in [0, 1]; its lens.sum() would keep a count above F); NULL: every frame is valid AND the
+ * reference's lens=None forms apply (finish / bwd).  Rows are r = b*F + f.  No atomics, fixed reduction orders.
+ *   stftloss_frame    A[r*ldk + j] = x[b*ldx + reflect(f*hop + left + j - h)] for j < win and f < frames[b], reflected
+ *                     about 0 and about T-1; 0 for win <= j < ldk and in rows f >= frames[b] (x not read there).
+ *                     ldk % 4 == 0, ldk >= win, A 16B aligned, B*F*ldk*4 < 2 GiB.
+ *   stftloss_terms    spec_* [B*F][lds], re in columns [0, cutoff), im in [cutoff, 2 cutoff) (lds % 4 == 0; columns past
+ *                     2 cutoff are not read): mag = sqrt(max(re^2 + im^2, 1e-7)); part[4r .. 4r+3] = (sum_k (ym - xm)^2,
+ *                     sum_k ym^2, sum_k |log ym - log xm|, 0), with a_weighting |log(ym + 1) - log(xm + 1)|.  One wave per
+ *                     row: lane l adds bins l, l+64, ... in order, then a xor butterfly.  Rows f >= frames[b]: zeros,
+ *                     spec not read.
+ *   stftloss_finish   one workgroup, fp64: norm = (S, sum_r D_r, sum_r N_r, 0) over the valid rows, S = sum_b frames[b]
+ *                     (B*F without frames).  out[0] = sum_r sqrt(D_r)/sqrt(N_r) / S with frames, sqrt(sum D)/sqrt(sum N)
+ *                     without; out[1] = sum_r L_r / (S * cutoff).
+ *   stftloss_bwd      gradients of g_sc[0]*scale*out[0] + g_mag[0]*scale*out[1] (g_sc, g_mag: device scalars) with respect
+ *                     to the spectra, dspec_x and / or dspec_y (either may be NULL) [B*F][lds]: per bin dmag * re/mag and
+ *                     dmag * im/mag where re^2 + im^2 >= 1e-7, 0 below; sign(0) = 0 in the log term; rows (the total,
+ *                     without frames) with sum (ym - xm)^2 == 0 add nothing to the spectral-convergence term.  Rows
+ *                     f >= frames[b] and columns 2 cutoff <= c < lds are written as 0.
+ *   stftloss_unframe  the adjoint of stftloss_frame in gather form: dx[b*lddx + s], s < T, is the sum of dA over the
+ *                     frames f < frames[b] (ascending) that hold padded position s + h, then h - s for 1 <= s <= h, then
+ *                     h + 2(T-1) - s for T-1-h <= s <= T-2; with accum the sum is added to dx[b*lddx + s] (last).
+ * ------------------------------------------------------------------------------------ */
+int radmmm_stftloss_frame(const float* x, int ldx, const int32_t* frames, float* A, int ldk, int B, int T, int F,
+                          int n_fft, int hop, int win, radmmm_stream_t stream);
+int radmmm_stftloss_terms(const float* spec_x, const float* spec_y, int lds, const int32_t* frames, float* part, int B,
+                          int F, int cutoff, int a_weighting, radmmm_stream_t stream);
+int radmmm_stftloss_finish(const float* part, const int32_t* frames, float* out, double* norm, int B, int F, int cutoff,
+                           radmmm_stream_t stream);
+int radmmm_stftloss_bwd(const float* spec_x, const float* spec_y, int lds, const float* part, const double* norm,
+                        const int32_t* frames, const float* g_sc, const float* g_mag, float scale, float* dspec_x,
+                        float* dspec_y, int B, int F, int cutoff, int a_weighting, radmmm_stream_t stream);
+int radmmm_stftloss_unframe(const float* dA, int ldk, const int32_t* frames, float* dx, int lddx, int B, int T, int F,
+                            int n_fft, int hop, int win, int accum, radmmm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,6 +246,11 @@ def _load() -> C.CDLL:
         "radmmm_collate_unpack_pad": [p, i, p, p, p, p, i, i, i, f, p],
         "radmmm_collate_mel": [p, p, p, p, p, p, i, i, i, i, i, f, i, p],
         "radmmm_collate_tracks": [p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, f, i, i, p],
+        "radmmm_stftloss_frame": [p, i, p, p, i, i, i, i, i, i, i, p],
+        "radmmm_stftloss_terms": [p, p, i, p, p, i, i, i, i, p],
+        "radmmm_stftloss_finish": [p, p, p, p, i, i, i, p],
+        "radmmm_stftloss_bwd": [p, p, i, p, p, p, p, p, f, p, p, i, i, i, i, p],
+        "radmmm_stftloss_unframe": [p, i, p, p, i, i, i, i, i, i, i, i, p],
     }
     missing = [n for n in sig if not hasattr(lib, n)]
     if missing:

@@ -3,6 +3,7 @@
 
     python tools/vocoder_bench.py [--iters 5] [--warmup 2] [--no-torch]
     python tools/vocoder_bench.py --train [--iters 5] [--warmup 2]
+    python tools/vocoder_bench.py --stft-loss [--iters 5] [--warmup 2] [--out profiles/stft_loss.json]
 
 Generator and denoiser ms per call at (B, T) = (32, 800) and (1, 800) for the V1 and V3 configs (random weights
 from a seed), the real-time factor (seconds of 22.05 kHz audio per second of compute), per-stage ms of the generator
@@ -13,7 +14,15 @@ torch.nn.functional fp32 convs on the same GPU.  Device events around each call,
 training checkpoint) at upstream HiFi-GAN's training shape, batch 16 x 32 frames (8192 samples), and at batch 32 x 32
 frames, through the HIP backward and, in the same process, through the stock path: the same generator written with
 torch.nn.functional in fp32 and trained by torch autograd.  One JSON line with both times, their ratio and the peak
-allocated bytes of each."""
+allocated bytes of each.
+
+--stft-loss: the multi-resolution STFT loss (rad_mmm_amd/stft_loss.py, the default three resolutions, ragged
+len_ratios on the device), forward plus backward with respect to the prediction, at 16 x 8192 and 32 x 8192 samples, in
+one process: the HIP module, a stock-torch implementation with torch.stft and vectorised masking (no per-item loop, no
+host read: the strongest stock alternative) and the per-item loop as the reference writes it.  Median of --iters runs
+after --warmup; per form the device launches of one step (torch.profiler) and the host synchronisations
+(torch.cuda.set_sync_debug_mode("warn")).  Then the V1 training step of --train with this loss in place of the quadratic
+one (HIP generator; HIP loss, stock vectorised loss, and the quadratic loss for scale).  The JSON also goes to --out."""
 import argparse
 import json
 import os
@@ -147,18 +156,150 @@ def train_bench(args, dev):
     print(json.dumps(res))
 
 
+def stock_stft_losses(fft_sizes, hop_sizes, win_lengths, dev):
+    """(vectorised, per-item loop): the reference's loss written with stock torch ops.  vectorised masks the frames
+    past ceil(len_ratios * F) instead of slicing them, so nothing is read back; loop slices every item at lens[i] as
+    stft_loss.py:136-143 does."""
+    windows = [torch.hann_window(w, device=dev) for w in win_lengths]
+
+    def mags(sig, n_fft, hop, win, window):
+        z = torch.stft(sig, n_fft, hop, win, window, return_complex=True)
+        return torch.sqrt(torch.clamp(z.real ** 2 + z.imag ** 2, min=1e-7)).transpose(2, 1)
+
+    def vectorised(x, y, ratios):
+        sc = mag = 0.0
+        for n_fft, hop, win, window in zip(fft_sizes, hop_sizes, win_lengths, windows):
+            xm, ym = mags(x, n_fft, hop, win, window), mags(y, n_fft, hop, win, window)
+            frames = (ratios * ym.shape[1]).ceil()
+            mask = (torch.arange(ym.shape[1], device=dev)[None, :] < frames[:, None]).to(ym.dtype)
+            total = frames.sum()
+            sc = sc + (torch.linalg.vector_norm(ym - xm, dim=2) / torch.linalg.vector_norm(ym, dim=2) * mask).sum() / total
+            mag = mag + ((torch.log(ym) - torch.log(xm)).abs() * mask[..., None]).sum() / (total * ym.shape[2])
+        return sc / len(fft_sizes), mag / len(fft_sizes)
+
+    def loop(x, y, ratios):
+        sc = mag = 0.0
+        for n_fft, hop, win, window in zip(fft_sizes, hop_sizes, win_lengths, windows):
+            xm, ym = mags(x, n_fft, hop, win, window), mags(y, n_fft, hop, win, window)
+            lens = (ratios * ym.shape[1]).ceil().long()
+            loss = 0.0
+            for i in range(len(ym)):
+                y_i, x_i = ym[i, :lens[i]], xm[i, :lens[i]]
+                loss = loss + (torch.norm(y_i - x_i, dim=1, p="fro") / torch.norm(y_i, dim=1, p="fro")).sum()
+            sc = sc + loss / lens.sum()
+            mask = (torch.arange(ym.shape[1], device=dev)[None, :] < lens[:, None])[..., None]
+            mag = mag + ((torch.log(ym) - torch.log(xm)).abs() * mask).sum() / (mask.sum() * ym.shape[2])
+        return sc / len(fft_sizes), mag / len(fft_sizes)
+    return vectorised, loop
+
+
+def count_launches_and_syncs(fn):
+    """(device launches of one call, host synchronisations of one call); None where the count could not be taken"""
+    import warnings
+    launches = syncs = None
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        launches = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA)
+    except Exception as e:
+        print(f"launch count failed: {e}", file=sys.stderr)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("warn")
+    try:
+        with warnings.catch_warnings(record=True) as seen:
+            warnings.simplefilter("always")
+            fn()
+        syncs = sum(1 for w in seen if "synchroniz" in str(w.message).lower())
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    torch.cuda.synchronize()
+    return launches, syncs
+
+
+def stft_loss_bench(args, dev):
+    from rad_mmm_amd.stft_loss import MultiResolutionSTFTLoss
+    fft, hop, win = [1024, 2048, 512], [120, 240, 50], [600, 1200, 240]
+    hip = MultiResolutionSTFTLoss(fft, hop, win).to(dev)
+    vectorised, loop = stock_stft_losses(fft, hop, win, dev)
+    res = {"metric": "stft_loss_fwd_bwd_ms", "resolutions": {"fft": fft, "hop": hop, "win": win}, "iters": args.iters,
+           "warmup": args.warmup, "device": torch.cuda.get_device_name(0),
+           "note": "one GPU, one process, one session; forward + backward with respect to the prediction; ragged "
+                   "len_ratios on the device; median of iters after warmup", "shapes": {}}
+    g = torch.Generator().manual_seed(11)
+    for B in (16, 32):
+        T = 8192
+        lengths = torch.linspace(T // 3, T, B).round()
+        ratios = (lengths / T).to(dev)
+        keep = (torch.arange(T)[None, :] < lengths[:, None]).float()
+        target = (torch.randn(B, T, generator=g) * keep).to(dev)
+        pred = ((target.cpu() + 0.3 * torch.randn(B, T, generator=g)) * keep).to(dev)
+        row = {}
+        grads = {}
+        for key, fn in (("hip", hip), ("torch_vectorised", vectorised), ("torch_item_loop", loop)):
+            def step():
+                p = pred.detach().requires_grad_(True)
+                sc, mag = fn(p, target, ratios)
+                (sc + mag).backward()
+                return sc.detach(), mag.detach(), p.grad
+            ms = timed(step, args.iters, args.warmup)
+            launches, syncs = count_launches_and_syncs(step)
+            sc, mag, grads[key] = step()
+            row[key] = {"fwd_bwd_ms": round(ms, 3), "launches": launches, "host_syncs": syncs, "sc": float(sc),
+                        "mag": float(mag)}
+        for key in ("torch_vectorised", "torch_item_loop"):
+            row[key]["over_hip"] = round(row[key]["fwd_bwd_ms"] / row["hip"]["fwd_bwd_ms"], 3)
+            row[key]["grad_rel_l2_vs_hip"] = float((grads[key] - grads["hip"]).norm() / grads["hip"].norm())
+        res["shapes"][f"B{B}_T{T}"] = row
+        print(json.dumps({f"B{B}_T{T}": row}), file=sys.stderr, flush=True)
+    # the V1 training step of --train with this loss in place of the quadratic one
+    gen = HiFiGANGenerator(V1)
+    gen.load_state_dict(random_state(gen, 5, 0.2, 0.6))
+    gen = gen.to(dev).train()
+    res["train_step"] = {}
+    for B in (16, 32):
+        Tm = 32
+        S = Tm * gen.hop
+        mel = (torch.randn(B, 80, Tm, generator=g) - 2.0).to(dev)
+        target = (torch.rand(B, S, generator=g) * 2 - 1).to(dev)
+        ratios = (torch.linspace(S // 3, S, B).round() / S).to(dev)
+        lens = [Tm] * B
+        row = {}
+        for key, loss in (("hip_stft_loss", lambda a: sum(hip(a, target, ratios))),
+                          ("torch_vectorised_stft_loss", lambda a: sum(vectorised(a, target, ratios))),
+                          ("quadratic_loss", lambda a: ((a - target) ** 2).mean())):
+            def step():
+                gen.zero_grad(set_to_none=True)
+                loss(gen(mel, lens)[:, 0]).backward()
+            row[key + "_step_ms"] = round(timed(step, args.iters, args.warmup), 3)
+        res["train_step"][f"B{B}_T{Tm}"] = row
+        print(json.dumps({f"train_B{B}_T{Tm}": row}), file=sys.stderr, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--train", action="store_true", help="time one V1 training step against stock torch autograd")
+    ap.add_argument("--stft-loss", action="store_true", help="time the multi-resolution STFT loss against stock torch")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stft_loss.json"), help="--stft-loss: result file")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
     if args.train:
         return train_bench(args, dev)
+    if args.stft_loss:
+        return stft_loss_bench(args, dev)
     res = {"metric": "vocoder_ms", "configs": {}}
     for name, cfg in (("V1", V1), ("V3", V3)):
         gen = HiFiGANGenerator(cfg)

@@ -604,6 +604,33 @@ int radmmm_wgrad_rmh(const void* GYh, int ldg, const void* Xh, int ldx, int R, i
                      int ldp, int64_t split_stride, int Mc, int Nc, int taps, int dil, int splits, float acc_scale,
                      radmmm_stream_t stream);
 
+/* radmmm_wgrad_rmh / radmmm_wgrad_rm with a frame-shift origin and column origins:
+ *   P[split][tap][m][n] = acc_scale * sum_f GY[f][g_col0 + m] * X[f + shift0 + s][x_col0 + n],  s = (tap - taps/2)*dil,
+ * over the frames f whose partner f + shift0 + s lies in f's own utterance (and, with x_mask, below its length): with
+ * taps = 1 and shift0 = -1 / +1, X read this way is the previous / next frame's row with zeros across the utterance
+ * boundary -- the h_prev operand of an LSTM's recurrent weight gradient (dW_hh[d] = dG_d^T h_prev) taken from y itself.
+ * The pointers are the BASE pointers of planes of exactly R rows of ldg / ldx halves; the Mc / Nc channels start at column
+ * g_col0 / x_col0 of a row (multiples of 8, g_col0 + Mc <= ldg, x_col0 + Nc <= ldx), and no read goes beyond the planes.
+ * Largest shift0: the mask rule holds for any shift (a row is tested against its own utterance); what bounds it is the
+ * 32-bit offset arithmetic, (R + 96 + |shift0| + (taps/2)*dil) * ldx * 2 < 2^31 (csrc/common.h, wgrad_rm_shift_fits).
+ * Tiles, split-K ranges and K order are those of the plain entry points, whose results these reproduce bit for bit on
+ * operands shifted by hand (shift0 = 0 and zero origins: the plain entry points themselves).  Bad arguments return -1
+ * before any HIP call. */
+int radmmm_wgrad_rmh_shift(const void* GYh, int ldg, int g_col0, const void* Xh, int ldx, int x_col0, int shift0, int R, int T,
+                           const int32_t* lens, int x_mask, float* P, int ldp, int64_t split_stride, int Mc, int Nc, int taps,
+                           int dil, int splits, float acc_scale, radmmm_stream_t stream);
+int radmmm_wgrad_rm_shift(const void* GYh, const void* GYl, int ldg, int g_col0, const void* Xh, const void* Xl, int ldx, int x_col0,
+                          int shift0, int R, int T, const int32_t* lens, int x_mask, float* P, int ldp, int64_t split_stride,
+                          int Mc, int Nc, int taps, int dil, int splits, float acc_scale, radmmm_stream_t stream);
+
+/* fp16 hi (and, unless lo is NULL, lo) planes of `groups` column groups of x [rows][ld]: group g holds columns
+ * [g * gcols, (g + 1) * gcols) of x, scaled, at columns [g * gpitch, g * gpitch + gcols) of hi / lo [rows][ldh]; every other
+ * column of the planes is written as zero.  The bits of radmmm_split_f16 (RADMMM_SPLIT_F16) per element; sat_flag (or
+ * NULL) as there.  gpitch, ldh multiples of 8, groups * gpitch <= ldh, gcols <= gpitch, groups * gcols <= ld.  One pass
+ * gives both directions of an LSTM's y [rows][2H] their own 16-byte aligned group for radmmm_wgrad_rm*_shift. */
+int radmmm_split_f16_groups(const float* x, int ld, void* hi, void* lo, int ldh, int rows, int gcols, int groups, int gpitch,
+                            float scale, int* sat_flag, radmmm_stream_t stream);
+
 /* Bidirectional single-layer LSTM, recurrent part (reference: the decoder's context LSTM,
  * models/radmmm.py:141-146 = torch.nn.LSTM(bidirectional, batch_first) on a packed batch; gate order
  * i, f, g, o; frames t >= lens[b] produce h = c = 0 as pad_packed_sequence does).

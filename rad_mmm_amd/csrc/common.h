@@ -71,6 +71,18 @@ inline int check_launch(const char* what) {
 
 __host__ __device__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// The frame-shift origin of the row-major weight-gradient kernels (wgrad_rm.hip, wgrad_rm8.hip): the largest shift0 they take.
+// Their mask rule holds for ANY shift -- a row's partner frame f + shift is tested against the readable range [0, lim) of the
+// row's OWN utterance, and a row that fails has its DMA offset replaced by an out-of-range one whatever it was -- so a
+// readable row's offset always lies inside the operand.  What is left is the arithmetic: a lane forms (f + shift) * ldx * 2
+// in 32 bits for every row, readable or not, with f up to R + 96 (the last window's rows and the two steps the DMA runs
+// ahead).  The bound keeps that product of an unreadable row from leaving the signed range.  The tap shifts of the plain
+// entry points (up to 2 * 128 frames in the WaveGlow WN) are as they were: the check is made for shift0 != 0 only.
+inline bool wgrad_rm_shift_fits(int R, int ldx, int shift0, int taps, int dil) {
+  const long long reach = (shift0 < 0 ? -(long long)shift0 : (long long)shift0) + (long long)(taps / 2) * dil;
+  return shift0 == 0 || ((long long)R + 96 + reach) * ldx * 2 <= 0x7fffffffLL;
+}
+
 // ---- device helpers -------------------------------------------------------------
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for vmcnt(0), i.e. for the
 // write acknowledgements of every global store issued so far (stores count in vmcnt on gfx9): in an

@@ -361,6 +361,47 @@ extern "C" int radmmm_split_f16(const float* x, int ld, void* hi, void* lo, int 
   return radmmm::check_launch("split_f16");
 }
 
+namespace {
+// hi (and lo, unless null) planes [rows][ldh] of `groups` column groups of scale * x, group g at columns g * gpitch ..; a
+// thread writes 8 columns (one 16-byte store per plane), zeros where no group's column lies
+__global__ __launch_bounds__(256) void split_f16_groups_kernel(const float* __restrict__ x, int ld, void* __restrict__ hi,
+                                                               void* __restrict__ lo, int ldh, int rows, int gcols, int groups,
+                                                               int gpitch, float scale, int* __restrict__ sat_flag) {
+  const int c8n = ldh / 8;
+  const long long total = (long long)rows * c8n;
+  float sat = 0.f;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int r = (int)(i / c8n), c = (int)(i - (long long)r * c8n) * 8;
+    const int g = c / gpitch, cg = c - g * gpitch;               // (gpitch % 8 == 0: the 8 columns lie in one group)
+    const float* src = x + (long long)r * ld + (long long)g * gcols + cg;
+    float v[8];
+    if (g < groups && cg + 8 <= gcols && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+      const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
+      v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (g < groups && cg + e < gcols) ? src[e] : 0.f;
+    }
+    sat = fmaxf(sat, radmmm::store_split8_f16_amax(hi, lo, (long long)r * ldh, c, scale, v));
+  }
+  radmmm::raise_sat_flag(sat_flag, sat, 0.f);
+}
+}  // namespace
+
+extern "C" int radmmm_split_f16_groups(const float* x, int ld, void* hi, void* lo, int ldh, int rows, int gcols, int groups,
+                                       int gpitch, float scale, int* sat_flag, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(x && hi, "split_f16_groups: null pointer");
+  RADMMM_REQUIRE(rows > 0 && gcols > 0 && groups > 0 && gpitch >= gcols && gpitch % 8 == 0 && ldh % 8 == 0 &&
+                     (long long)groups * gpitch <= ldh && (long long)groups * gcols <= ld,
+                 "split_f16_groups: bad dims (gpitch, ldh %% 8 == 0, gcols <= gpitch, groups * gpitch <= ldh, groups * gcols <= ld)");
+  RADMMM_REQUIRE(radmmm::aligned16(hi) && radmmm::aligned16(lo), "split_f16_groups: 16-byte aligned planes");
+  const long long total = (long long)rows * (ldh / 8);
+  const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+  hipLaunchKernelGGL(split_f16_groups_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), x, ld, hi, lo, ldh, rows,
+                     gcols, groups, gpitch, scale, sat_flag);
+  return radmmm::check_launch("split_f16_groups");
+}
+
 extern "C" int radmmm_transpose_f16_pair(const void* src_h, const void* src_l, int ld_src, int64_t src_batch, void* dst_h,
                                          void* dst_l, int ld_dst, int64_t dst_batch, int batches, int rows, int cols,
                                          int fmt, int x8_exp, radmmm_stream_t stream) {

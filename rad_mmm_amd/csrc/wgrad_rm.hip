@@ -44,6 +44,8 @@ struct RmArgs {
   float* P; int ldp; long long split_stride;
   float acc_scale;
   int g_bytes, x_bytes;
+  int g_col0, x_col0;                    // column origins of the Mc / Nc channels inside the rows of GY / X (0: radmmm_wgrad_rm)
+  int shift0;                            // frame-shift origin: X is read at f + shift0 + (tap - taps/2) * dil
 };
 
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, lds_u32_ptr dst, int voffset) {
@@ -91,7 +93,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm_kernel(const RmArgs a) {
   const int tap = id % a.taps;
   const int split = id / a.taps;
   const int m0 = tm * TM, n0 = tn * TN;
-  const int shift = (tap - a.taps / 2) * a.dil;
+  const int shift = (tap - a.taps / 2) * a.dil + a.shift0;
   const int steps_total = (a.R + BK - 1) / BK;
   const int steps_per = (steps_total + a.splits - 1) / a.splits;
   const int step_lo = split * steps_per;
@@ -125,7 +127,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm_kernel(const RmArgs a) {
     const int ch = c0 + u * 32 + d_p16 * 8;
     p_k[w] = k;
     const int f0 = step_lo * BK + k;                             // GY frame of this row at the split's first step
-    p_off[w] = ch < C ? ((f0 + (isx ? shift : 0)) * ld + ch) * 2 : OOB;
+    p_off[w] = ch < C ? ((f0 + (isx ? shift : 0)) * ld + (isx ? a.x_col0 : a.g_col0) + ch) * 2 : OOB;
     if (arr == 2) {
       const int b = f0 / a.T;
       const int bc = b < nb ? b : nb - 1;
@@ -252,17 +254,28 @@ extern "C" int radmmm_wgrad_rm_tiles(int Mc, int Nc, int taps) {
 // utterance-major.  x_mask: X rows at frames >= lens[b] read as zeros.  P [splits][taps][Mc][ldp] fp32 partial slabs
 // (split_stride floats apart), to be summed by the caller (radmmm_weightnorm_bwd does).  ldg, ldx multiples of 8,
 // 16-byte aligned operands, T >= 32, at most 1024 utterances.
-extern "C" int radmmm_wgrad_rm(const void* GYh, const void* GYl, int ldg, const void* Xh, const void* Xl, int ldx, int R, int T,
-                               const int32_t* lens, int x_mask, float* P, int ldp, int64_t split_stride, int Mc, int Nc,
-                               int taps, int dil, int splits, float acc_scale, radmmm_stream_t stream) {
-  RADMMM_REQUIRE(GYh && GYl && Xh && Xl && P, "wgrad_rm: null pointer");
+namespace {
+
+// The launch behind radmmm_wgrad_rm (origins and shift0 all zero) and radmmm_wgrad_rm_shift.  The four pointers are the
+// BASE pointers of the planes: the buffer resources cover exactly R rows of ldg / ldx halves, a piece is fetched only for a
+// channel below Mc / Nc, and the column origin is added to its offset (g_col0 + Mc <= ldg: it stays within its row).
+int launch_rm(const char* who, const void* GYh, const void* GYl, int ldg, int g_col0, const void* Xh, const void* Xl, int ldx,
+              int x_col0, int shift0, int R, int T, const int32_t* lens, int x_mask, float* P, int ldp, int64_t split_stride,
+              int Mc, int Nc, int taps, int dil, int splits, float acc_scale, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(GYh && GYl && Xh && Xl && P, "%s: null pointer", who);
   RADMMM_REQUIRE(Mc > 0 && Nc > 0 && taps >= 1 && dil >= 1 && splits >= 1 && R > 0 && T > 0 && R % T == 0 && ldg >= Mc &&
                      ldx >= Nc && ldg % 8 == 0 && ldx % 8 == 0 && ldp >= Nc && T >= BK && R / T <= 1024,
-                 "wgrad_rm: bad dims (ldg, ldx %% 8 == 0, R = B * T, T >= 32, B <= 1024)");
+                 "%s: bad dims (ldg, ldx %% 8 == 0, R = B * T, T >= 32, B <= 1024)", who);
+  RADMMM_REQUIRE(g_col0 >= 0 && x_col0 >= 0 && g_col0 % 8 == 0 && x_col0 % 8 == 0 && (long long)g_col0 + Mc <= ldg &&
+                     (long long)x_col0 + Nc <= ldx,
+                 "%s: bad column origin (multiples of 8, g_col0 + Mc <= ldg, x_col0 + Nc <= ldx)", who);
+  // (this kernel tests a row's partner frame against the row's own utterance too: p_t + shift < p_lim)
+  RADMMM_REQUIRE(radmmm::wgrad_rm_shift_fits(R, ldx, shift0, taps, dil),
+                 "%s: shift0 out of range ((R + 96 + |shift0| + (taps / 2) * dil) * ldx * 2 must stay below 2^31)", who);
   RADMMM_REQUIRE(radmmm::aligned16(GYh) && radmmm::aligned16(GYl) && radmmm::aligned16(Xh) && radmmm::aligned16(Xl),
-                 "wgrad_rm: 16-byte aligned operands");
+                 "%s: 16-byte aligned operands", who);
   const long long g_bytes = (long long)R * ldg * 2, x_bytes = (long long)R * ldx * 2;
-  RADMMM_REQUIRE(g_bytes < 0x7fffffffLL && x_bytes < 0x7fffffffLL, "wgrad_rm: operand >= 2 GiB");
+  RADMMM_REQUIRE(g_bytes < 0x7fffffffLL && x_bytes < 0x7fffffffLL, "%s: operand >= 2 GiB", who);
   static int once = [] {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_rm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        SMEM + 4096);
@@ -280,7 +293,27 @@ extern "C" int radmmm_wgrad_rm(const void* GYh, const void* GYl, int ldg, const 
   a.R = R; a.T = T; a.ldg = ldg; a.ldx = ldx; a.Mc = Mc; a.Nc = Nc; a.taps = taps; a.dil = dil; a.splits = splits;
   a.P = P; a.ldp = ldp; a.split_stride = split_stride; a.acc_scale = acc_scale;
   a.g_bytes = (int)g_bytes; a.x_bytes = (int)x_bytes;
+  a.g_col0 = g_col0; a.x_col0 = x_col0; a.shift0 = shift0;
   const int grid = radmmm_wgrad_rm_tiles(Mc, Nc, taps) * splits;
   hipLaunchKernelGGL(wgrad_rm_kernel, dim3(grid), dim3(256), SMEM + 4096, static_cast<hipStream_t>(stream), a);
-  return radmmm::check_launch("wgrad_rm");
+  return radmmm::check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int radmmm_wgrad_rm(const void* GYh, const void* GYl, int ldg, const void* Xh, const void* Xl, int ldx, int R, int T,
+                               const int32_t* lens, int x_mask, float* P, int ldp, int64_t split_stride, int Mc, int Nc,
+                               int taps, int dil, int splits, float acc_scale, radmmm_stream_t stream) {
+  return launch_rm("wgrad_rm", GYh, GYl, ldg, 0, Xh, Xl, ldx, 0, 0, R, T, lens, x_mask, P, ldp, split_stride, Mc, Nc, taps, dil,
+                   splits, acc_scale, stream);
+}
+
+// The same with a frame-shift origin and column origins (radmmm_wgrad_rmh_shift has the formula): three f16 products on
+// the (hi, lo) planes, the same tiles, split-K ranges and K order as radmmm_wgrad_rm on operands shifted by hand.
+extern "C" int radmmm_wgrad_rm_shift(const void* GYh, const void* GYl, int ldg, int g_col0, const void* Xh, const void* Xl, int ldx,
+                                     int x_col0, int shift0, int R, int T, const int32_t* lens, int x_mask, float* P, int ldp,
+                                     int64_t split_stride, int Mc, int Nc, int taps, int dil, int splits, float acc_scale,
+                                     radmmm_stream_t stream) {
+  return launch_rm("wgrad_rm_shift", GYh, GYl, ldg, g_col0, Xh, Xl, ldx, x_col0, shift0, R, T, lens, x_mask, P, ldp, split_stride,
+                   Mc, Nc, taps, dil, splits, acc_scale, stream);
 }

@@ -63,6 +63,8 @@ struct Rm8Args {
   float* P; int ldp; long long split_stride;
   float acc_scale;
   int g_bytes, x_bytes, gl_bytes, xl_bytes;
+  int g_col0, x_col0;                    // column origins of the Mc / Nc channels inside the rows of GY / X (0: the plain entry points)
+  int shift0;                            // frame-shift origin: X is read at f + shift0 + (tap - taps/2) * dil
 };
 
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, lds_u32_ptr dst, int voffset) {
@@ -266,7 +268,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
   const int tap = id % a.taps;
   const int split = id / a.taps;
   const int m0 = tm * TM, n0 = tn * TN;
-  const int shift = (tap - a.taps / 2) * a.dil;
+  const int shift = (tap - a.taps / 2) * a.dil + a.shift0;
   const int steps_total = (a.R + BK - 1) / BK;
   const int steps_per = (steps_total + a.splits - 1) / a.splits;
   const int step_lo = split * steps_per;
@@ -312,8 +314,8 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
     const int isx = w >> 2, pr = 4 * (w & 3) + wave;
     const int k = 2 * pr + (lane >> 5);
     const int u = ((lane & 31) >> 2) ^ (k & 3);                  // source 64-byte unit that lands at this lane's LDS unit
-    const int c0 = isx ? n0 : m0, ld = isx ? a.ldx : a.ldg;
-    const int ch = c0 + u * 32 + (lane & 3) * 8;
+    const int c0 = isx ? a.x_col0 + n0 : a.g_col0 + m0, ld = isx ? a.ldx : a.ldg;
+    const int ch = c0 + u * 32 + (lane & 3) * 8;                 // column within the operand's row: the origin counts in ch < ld
     p_sh[w] = 31 - k;
     const int f0 = step_lo * BK + k;                             // GY frame of this row at the split's first step
     p_off[w] = ch < ld ? ((f0 + (isx ? shift : 0)) * ld + ch) * 2 : OOB;
@@ -323,7 +325,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
     const int isx = (w - 8) >> 1, q = 4 * ((w - 8) & 1) + wave;
     const int k = 4 * q + (lane >> 4);
     const int u = ((lane >> 1) & 7) ^ (k & 7);                   // source 32-channel unit that lands at this lane's LDS unit
-    const int c0 = isx ? n0 : m0, ld = isx ? a.ldx : a.ldg;
+    const int c0 = isx ? a.x_col0 + n0 : a.g_col0 + m0, ld = isx ? a.ldx : a.ldg;
     const int ch = c0 + u * 32 + (lane & 1) * 16;
     p_sh[w] = 31 - k;
     const int f0 = step_lo * BK + k;
@@ -614,23 +616,33 @@ extern "C" int radmmm_wgrad_rm8(const void* GYh, const void* GYx, int ldg, int g
   a.R = R; a.T = T; a.ldg = ldg; a.ldx = ldx; a.Mc = Mc; a.Nc = Nc; a.taps = taps; a.dil = dil; a.splits = splits;
   a.P = P; a.ldp = ldp; a.split_stride = split_stride; a.acc_scale = acc_scale;
   a.g_bytes = (int)g_bytes; a.x_bytes = (int)x_bytes; a.gl_bytes = (int)g_bytes; a.xl_bytes = (int)x_bytes;
+  a.g_col0 = 0; a.x_col0 = 0; a.shift0 = 0;
   const int tiles = ((Mc + TM - 1) / TM) * ((Nc + TN - 1) / TN) * taps;
   hipLaunchKernelGGL(wgrad_rm8_kernel<2>, dim3(tiles * splits), dim3(256), smem_bytes(2) + 4096, static_cast<hipStream_t>(stream), a);
   return radmmm::check_launch("wgrad_rm8");
 }
 
-// One product: GYh . Xh alone (wgrad_rm8_kernel<1>).  GYh / Xh as above; no 8-bit arrays.  Everything else as radmmm_wgrad_rm8:
-// the same tiles, split-K ranges, masks and accumulation order, so the slabs differ from that kernel's by the cross terms only.
-extern "C" int radmmm_wgrad_rmh(const void* GYh, int ldg, const void* Xh, int ldx, int R, int T, const int32_t* lens, int x_mask,
-                                float* P, int ldp, int64_t split_stride, int Mc, int Nc, int taps, int dil, int splits,
-                                float acc_scale, radmmm_stream_t stream) {
-  RADMMM_REQUIRE(GYh && Xh && P, "wgrad_rmh: null pointer");
+
+namespace {
+
+// ONE product: the launch behind radmmm_wgrad_rmh (origins and shift0 all zero) and radmmm_wgrad_rmh_shift.  GYh / Xh are
+// the BASE pointers of the two planes: the buffer resources cover exactly R rows of ldg / ldx halves, and a piece's column
+// test is made on the column within the row (origin included), so no piece reaches beyond the planes.
+int launch_rmh(const char* who, const void* GYh, int ldg, int g_col0, const void* Xh, int ldx, int x_col0, int shift0, int R, int T,
+               const int32_t* lens, int x_mask, float* P, int ldp, int64_t split_stride, int Mc, int Nc, int taps, int dil,
+               int splits, float acc_scale, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(GYh && Xh && P, "%s: null pointer", who);
   RADMMM_REQUIRE(Mc > 0 && Nc > 0 && taps >= 1 && dil >= 1 && splits >= 1 && R > 0 && T > 0 && R % T == 0 && ldg >= Mc &&
                      ldx >= Nc && ldg % 32 == 0 && ldx % 32 == 0 && ldp >= Nc && T >= BK && R / T <= 1024,
-                 "wgrad_rmh: bad dims (ldg, ldx %% 32 == 0, R = B * T, T >= 32, B <= 1024, splits >= 1)");
-  RADMMM_REQUIRE(radmmm::aligned16(GYh) && radmmm::aligned16(Xh), "wgrad_rmh: 16-byte aligned operands");
+                 "%s: bad dims (ldg, ldx %% 32 == 0, R = B * T, T >= 32, B <= 1024, splits >= 1)", who);
+  RADMMM_REQUIRE(g_col0 >= 0 && x_col0 >= 0 && g_col0 % 8 == 0 && x_col0 % 8 == 0 && (long long)g_col0 + Mc <= ldg &&
+                     (long long)x_col0 + Nc <= ldx,
+                 "%s: bad column origin (multiples of 8, g_col0 + Mc <= ldg, x_col0 + Nc <= ldx)", who);
+  RADMMM_REQUIRE(radmmm::wgrad_rm_shift_fits(R, ldx, shift0, taps, dil),
+                 "%s: shift0 out of range ((R + 96 + |shift0| + (taps / 2) * dil) * ldx * 2 must stay below 2^31)", who);
+  RADMMM_REQUIRE(radmmm::aligned16(GYh) && radmmm::aligned16(Xh), "%s: 16-byte aligned operands", who);
   const long long g_bytes = (long long)R * ldg * 2, x_bytes = (long long)R * ldx * 2;
-  RADMMM_REQUIRE(g_bytes < 0x7fffffffLL && x_bytes < 0x7fffffffLL, "wgrad_rmh: operand >= 2 GiB");
+  RADMMM_REQUIRE(g_bytes < 0x7fffffffLL && x_bytes < 0x7fffffffLL, "%s: operand >= 2 GiB", who);
   static int once = [] {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_rm8_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        smem_bytes(1) + 4096);
@@ -647,7 +659,29 @@ extern "C" int radmmm_wgrad_rmh(const void* GYh, int ldg, const void* Xh, int ld
   a.R = R; a.T = T; a.ldg = ldg; a.ldx = ldx; a.Mc = Mc; a.Nc = Nc; a.taps = taps; a.dil = dil; a.splits = splits;
   a.P = P; a.ldp = ldp; a.split_stride = split_stride; a.acc_scale = acc_scale;
   a.g_bytes = (int)g_bytes; a.x_bytes = (int)x_bytes;
+  a.g_col0 = g_col0; a.x_col0 = x_col0; a.shift0 = shift0;
   const int tiles = ((Mc + TM - 1) / TM) * ((Nc + TN - 1) / TN) * taps;
   hipLaunchKernelGGL(wgrad_rm8_kernel<1>, dim3(tiles * splits), dim3(256), smem_bytes(1) + 4096, static_cast<hipStream_t>(stream), a);
-  return radmmm::check_launch("wgrad_rmh");
+  return radmmm::check_launch(who);
+}
+
+}  // namespace
+
+// One product: GYh . Xh alone (wgrad_rm8_kernel<1>).  GYh / Xh as above; no 8-bit arrays.  Everything else as radmmm_wgrad_rm8:
+// the same tiles, split-K ranges, masks and accumulation order, so the slabs differ from that kernel's by the cross terms only.
+extern "C" int radmmm_wgrad_rmh(const void* GYh, int ldg, const void* Xh, int ldx, int R, int T, const int32_t* lens, int x_mask,
+                                float* P, int ldp, int64_t split_stride, int Mc, int Nc, int taps, int dil, int splits,
+                                float acc_scale, radmmm_stream_t stream) {
+  return launch_rmh("wgrad_rmh", GYh, ldg, 0, Xh, ldx, 0, 0, R, T, lens, x_mask, P, ldp, split_stride, Mc, Nc, taps, dil, splits,
+                    acc_scale, stream);
+}
+
+// The same with a frame-shift origin and column origins: P[..][m][n] = acc_scale * sum_f GY[f][g_col0 + m] * X[f + shift0 + s][x_col0 + n]
+// (s the tap shift), the partner frame inside f's utterance as ever.  With taps = 1 and shift0 = -1 / +1 X read this way IS
+// the previous / next frame's row with zeros across the utterance boundary: an LSTM's h_prev without a shifted copy.
+extern "C" int radmmm_wgrad_rmh_shift(const void* GYh, int ldg, int g_col0, const void* Xh, int ldx, int x_col0, int shift0, int R,
+                                      int T, const int32_t* lens, int x_mask, float* P, int ldp, int64_t split_stride, int Mc,
+                                      int Nc, int taps, int dil, int splits, float acc_scale, radmmm_stream_t stream) {
+  return launch_rmh("wgrad_rmh_shift", GYh, ldg, g_col0, Xh, ldx, x_col0, shift0, R, T, lens, x_mask, P, ldp, split_stride, Mc, Nc,
+                    taps, dil, splits, acc_scale, stream);
 }

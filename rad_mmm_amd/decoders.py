@@ -332,7 +332,10 @@ class RADMMMFlow(nn.Module):
                 hook(self.context_lstm, ())
             full = int(ul.min()) == Tg
             lens32 = None if full else torch.div(seq_lens.lengths, g, rounding_mode="floor").to(torch.int32)
-            return bilstm(self.context_lstm, x.contiguous(), lens32).contiguous()
+            # the context LSTM's weight gradients are leaves of the step like the WN convs': under f8x they follow the same
+            # switch (one f16 product by default); h3 / f16 and the precision guard's fallback keep three products
+            nprod = ops.wgrad_products_env() if self.gemm_precision == "f8x" else 3
+            return bilstm(self.context_lstm, x.contiguous(), lens32, 1 if nprod == 1 else 3).contiguous()
         self.context_lstm.flatten_parameters()
         if int(ul.min()) == Tg:                       # fixed-length batch: packing is the identity
             y = self._bilstm_two_streams(x) if self.lstm_two_streams else self.context_lstm(x)[0]

@@ -33,9 +33,12 @@ class BiLSTMFn(torch.autograd.Function):
 
     @staticmethod
     @amp_fwd
-    def forward(ctx, x, lens, w_ih_f, w_hh_f, b_ih_f, b_hh_f, w_ih_r, w_hh_r, b_ih_r, b_hh_r, box=None):
+    def forward(ctx, x, lens, w_ih_f, w_hh_f, b_ih_f, b_hh_f, w_ih_r, w_hh_r, b_ih_r, b_hh_r, box=None, wgrad_products=3):
         B, T, I = x.shape
         ctx.box = box
+        if wgrad_products not in (1, 3):
+            raise ValueError(f"wgrad_products={wgrad_products!r}: 1 or 3")
+        ctx.wgrad_products = wgrad_products                      # decided here; backward follows it and reads no environment
         H = w_hh_f.shape[1]
         x2 = x.reshape(B * T, I).contiguous()
         W_ih = torch.cat((w_ih_f, w_ih_r), 0)                    # [8H, I]
@@ -91,11 +94,14 @@ class BiLSTMFn(torch.autograd.Function):
                                   None, stream()), "lstm_bwd")            # (the kernel scales its fp16 operand itself, per row and step)
         last_path[1] = int(lib.radmmm_lstm_last_path(1))
         dG = G                                                   # now the pre-activation gradients
-        y3 = y.view(B, T, 2 * H)
-        hp = torch.zeros(B, T, 2 * H, device=dy.device, dtype=torch.float32)
-        hp[:, 1:, :H] = y3[:, :-1, :H]                           # forward direction: h_{t-1}
-        hp[:, :-1, H:] = y3[:, 1:, H:]                           # reverse direction: h_{t+1}
-        hp = hp.view(B * T, 2 * H)
+
+        def h_prev():
+            # the recurrent weight gradients' operand as a tensor of its own (the paths below the split kernels' sizes)
+            y3 = y.view(B, T, 2 * H)
+            hp = torch.zeros(B, T, 2 * H, device=dy.device, dtype=torch.float32)
+            hp[:, 1:, :H] = y3[:, :-1, :H]                       # forward direction: h_{t-1}
+            hp[:, :-1, H:] = y3[:, 1:, H:]                       # reverse direction: h_{t+1}
+            return hp.view(B * T, 2 * H)
         if ctx.box is not None and B * T >= 4096 and (8 * H) % 32 == 0 and I % 4 == 0 and H % 2 == 0:
             # frame-rate batches: the four gradient GEMMs (226 + 57 GFLOP at the benchmark size, 2.5 ms on the fp32 library
             # GEMMs) on the split-f16 kernels: ONE transposing pass over dG feeds both weight gradients (contraction over
@@ -105,19 +111,31 @@ class BiLSTMFn(torch.autograd.Function):
             box = ctx.box
             SG = ops.grad_scale(box, dy2)
             flag = ops.sat_flag_bwd_of(box)
-            gh, gl = ops.split_f16(dG, 8 * H, SG, 8 * H, 3, 0, flag)       # row-major split pair of dG: operand of all four GEMMs
-            if xpair is not None and T >= 32 and B <= 1024 and (4 * H) % 8 == 0:
-                # weight gradients straight from the row-major pairs (radmmm_wgrad_rm: transposition in the LDS read); the
-                # pair of x was made for the forward projection, the pairs of h_prev (one per direction, each with its own
-                # 16-byte aligned row pitch) cost what the transposed copy did
-                db = ops.colsum(dG, 8 * H)
-                Hq = ops.round_up(H, 8)
-                hpf = ops.split_f16(hp[:, :H].contiguous(), H, 1.0, Hq)
-                hpr = ops.split_f16(hp[:, H:].contiguous(), H, 1.0, Hq)
-                dW_ih = ops.wgrad_rm_slabs((gh, gl), xpair, B, T, 8 * H, I, 1, 1, 1.0 / SG).sum(0)[0]
-                dW_hh_f = ops.wgrad_rm_slabs((gh[:, :4 * H], gl[:, :4 * H]), hpf, B, T, 4 * H, H, 1, 1, 1.0 / SG).sum(0)[0]
-                dW_hh_r = ops.wgrad_rm_slabs((gh[:, 4 * H:], gl[:, 4 * H:]), hpr, B, T, 4 * H, H, 1, 1, 1.0 / SG).sum(0)[0]
+            rm = xpair is not None and T >= 32 and B <= 1024 and (4 * H) % 8 == 0
+            one = rm and ctx.wgrad_products == 1                 # the three weight gradients are leaves: the hi planes alone
+            if one and not ctx.needs_input_grad[0]:
+                gh, gl = ops.split_f16_groups(dG, 8 * H, 1, SG, 8 * H, False, flag)      # (nobody reads dG's lo plane)
             else:
+                gh, gl = ops.split_f16(dG, 8 * H, SG, 8 * H, 3, 0, flag)   # row-major split pair of dG: operand of all four GEMMs
+            if rm:
+                # weight gradients straight from the row-major planes (radmmm_wgrad_rm*: transposition in the LDS read); the
+                # pair of x was made for the forward projection.  h_prev is never built: h_prev[f] = y[f -+ 1] inside an
+                # utterance and zero across its boundary, which is what the kernels' frame shift reads (shift0 = -1 / +1)
+                # from ONE split copy of y -- each direction in a column group of its own (16-byte aligned, pitch % 32 == 0;
+                # H = 524: two groups of 544) -- and dG's directions are column origins 0 / 4H of the one dG pair.
+                db = ops.colsum(dG, 8 * H)
+                yh, yl = ops.split_f16_groups(y, H, 2, with_lo=not one)
+                Hg = yh.shape[1] // 2
+                if one:
+                    dW_ih = ops.wgrad_rmh_shift_slabs(gh, 0, xpair[0], 0, 0, B, T, 8 * H, I, 1.0 / SG).sum(0)[0]
+                    dW_hh_f = ops.wgrad_rmh_shift_slabs(gh, 0, yh, 0, -1, B, T, 4 * H, H, 1.0 / SG).sum(0)[0]
+                    dW_hh_r = ops.wgrad_rmh_shift_slabs(gh, 4 * H, yh, Hg, 1, B, T, 4 * H, H, 1.0 / SG).sum(0)[0]
+                else:
+                    dW_ih = ops.wgrad_rm_slabs((gh, gl), xpair, B, T, 8 * H, I, 1, 1, 1.0 / SG).sum(0)[0]
+                    dW_hh_f = ops.wgrad_rm_shift_slabs((gh, gl), 0, (yh, yl), 0, -1, B, T, 4 * H, H, 1.0 / SG).sum(0)[0]
+                    dW_hh_r = ops.wgrad_rm_shift_slabs((gh, gl), 4 * H, (yh, yl), Hg, 1, B, T, 4 * H, H, 1.0 / SG).sum(0)[0]
+            else:
+                hp = h_prev()
                 gy_t, db = ops.transpose_split_act(dG, 8 * H, B, T, None, 0, SG, "lstm_gy", colsum=(0, None, 1, 1))
                 x_t = ops.transpose_split_act(x2, I, B, T, None, 0, 1.0, "lstm_x")
                 hp_t = ops.transpose_split_act(hp, 2 * H, B, T, None, 0, 1.0, "lstm_h")
@@ -135,17 +153,21 @@ class BiLSTMFn(torch.autograd.Function):
                 dx = dx.view(B, T, I)
             ops.check_saturation(box)
         else:
+            hp = h_prev()
             dx = (dG @ W_ih).view(B, T, I) if ctx.needs_input_grad[0] else None
             dW_ih = dG.t() @ x2                                  # [8H, I]
             db = dG.sum(0)
             dW_hh_f = dG[:, :4 * H].t() @ hp[:, :H]
             dW_hh_r = dG[:, 4 * H:].t() @ hp[:, H:]
         return (dx, None, dW_ih[:4 * H], dW_hh_f, db[:4 * H], db[:4 * H], dW_ih[4 * H:], dW_hh_r, db[4 * H:], db[4 * H:],
-                None)
+                None, None)
 
 
-def bilstm(lstm: torch.nn.LSTM, x: torch.Tensor, lens32) -> torch.Tensor:
-    """Apply `lstm`'s parameters (single layer, bidirectional, batch_first) with the HIP recurrence."""
+def bilstm(lstm: torch.nn.LSTM, x: torch.Tensor, lens32, wgrad_products: int = 3) -> torch.Tensor:
+    """Apply `lstm`'s parameters (single layer, bidirectional, batch_first) with the HIP recurrence.
+    wgrad_products: f16 products of the three weight-gradient GEMMs at frame-rate sizes -- 3 (hi / lo pairs, 2e-6) or 1 (the
+    hi planes alone, radmmm_wgrad_rmh_shift: for an LSTM whose weight gradients are leaves of the step and may carry the
+    2^-10 |dG|^T |x| rounding).  Forward, dx and the bias gradients do not depend on it."""
     assert lstm.num_layers == 1 and lstm.bidirectional and lstm.batch_first and lstm.proj_size == 0
     box = None
     if x.is_cuda and torch.is_grad_enabled():
@@ -158,7 +180,7 @@ def bilstm(lstm: torch.nn.LSTM, x: torch.Tensor, lens32) -> torch.Tensor:
         box.new_forward(x.device)
     return BiLSTMFn.apply(x, lens32, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0,
                           lstm.weight_ih_l0_reverse, lstm.weight_hh_l0_reverse, lstm.bias_ih_l0_reverse,
-                          lstm.bias_hh_l0_reverse, box)
+                          lstm.bias_hh_l0_reverse, box, wgrad_products)
 
 
 class MergedBiLSTMFn(torch.autograd.Function):
@@ -281,15 +303,12 @@ class MergedBiLSTMFn(torch.autograd.Function):
             gh, gl = ops.split_f16(G, 8 * HP, SG, 8 * HP, 3, 0, flag)
             db = ops.colsum(G, 8 * HP).view(2, 4, P, H)
             dWb = ops.wgrad_rm_slabs((gh, gl), (xh, xl), B, T, 8 * HP, Kc, 1, 1, 1.0 / SG).sum(0)[0].view(2, 4, P, H, P, I)
-            y4 = y.view(B, T, 2, HP)
-            hp = torch.zeros(2, B, T, HP, device=dev, dtype=torch.float32)
-            hp[0, :, 1:] = y4[:, :-1, 0]                                             # forward direction: h_{t-1}
-            hp[1, :, :-1] = y4[:, 1:, 1]                                             # reverse direction: h_{t+1}
-            dWhh = []
-            for d in range(2):
-                hpair = ops.split_f16(hp[d].view(B * T, HP), HP, 1.0, HP)
-                dWhh.append(ops.wgrad_rm_slabs((gh[:, 4 * HP * d: 4 * HP * (d + 1)], gl[:, 4 * HP * d: 4 * HP * (d + 1)]), hpair, B, T,
-                                               4 * HP, HP, 1, 1, 1.0 / SG).sum(0)[0].view(4, P, H, P, H))
+            # h_prev is never built (BiLSTMFn.backward): one split copy of y, a column group per direction, read through the
+            # kernel's frame shift -1 / +1; three products stay
+            ypair = ops.split_f16_groups(y, HP, 2)
+            HPg = ypair[0].shape[1] // 2
+            dWhh = [ops.wgrad_rm_shift_slabs((gh, gl), 4 * HP * d, ypair, HPg * d, (-1, 1)[d], B, T, 4 * HP, HP,
+                                             1.0 / SG).sum(0)[0].view(4, P, H, P, H) for d in range(2)]
             dx = None
             if any(ctx.needs_input_grad[3 + p] for p in range(P)):
                 Wt = Wb.t().contiguous()                                             # [P I, 8 HP]: the K-contiguous operand of dx = dG' Wb

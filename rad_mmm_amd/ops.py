@@ -976,6 +976,55 @@ def wgrad_rmh_slabs(gh, xh, B, T, Mc, Nc, taps, dil, acc_scale, lens=None):
     return P
 
 
+def split_f16_groups(x, gcols, groups, scale=1.0, gpitch=None, with_lo=True, sat_flag=None):
+    """fp16 hi / lo planes [rows, groups * gpitch] of x [rows, >= groups * gcols]: column group g of x (gcols wide) lands at
+    columns g * gpitch .. of the planes, zeros in between (radmmm_split_f16_groups; the bits of split_f16).  gpitch defaults to
+    gcols rounded up to 32: every group starts 16-byte aligned and the pitch suits the one-product weight gradient.
+    with_lo=False: no lo plane (returned as None), for operands whose hi plane alone is consumed."""
+    rows = x.shape[0]
+    gpitch = gpitch or round_up(gcols, 32)
+    ldh = groups * gpitch
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32
+    hi = torch.empty(rows, ldh, device=x.device, dtype=torch.float16)
+    lo = torch.empty(rows, ldh, device=x.device, dtype=torch.float16) if with_lo else None
+    check(lib.radmmm_split_f16_groups(ptr(x), x.stride(0), ptr(hi), ptr(lo), ldh, rows, gcols, groups, gpitch, scale,
+                                      ptr(sat_flag), stream()), "split_f16_groups")
+    return hi, lo
+
+
+def wgrad_rm_shift_slabs(gy_pair, g_col0, x_pair, x_col0, shift0, B, T, Mc, Nc, acc_scale, lens=None):
+    """wgrad_rm_slabs (one tap) with X read at frame f + shift0 inside f's utterance and the Mc / Nc channels at column origins
+    g_col0 / x_col0 of the WHOLE planes gy_pair / x_pair (radmmm_wgrad_rm_shift) -> P [S, 1, Mc, Nc].  The same slab count
+    and K order as wgrad_rm_slabs: bit-identical to it on operands shifted by hand."""
+    gh, gl = gy_pair
+    xh, xl = x_pair
+    R = B * T
+    assert gh.shape[0] == R and xh.shape[0] == R and gh.dtype == torch.float16 and xl.dtype == torch.float16
+    assert gh.is_contiguous() and gl.is_contiguous() and xh.is_contiguous() and xl.is_contiguous()
+    assert gl.shape == gh.shape and xl.shape == xh.shape
+    tiles = int(lib.radmmm_wgrad_rm_tiles(Mc, Nc, 1))
+    S = pick_splits(tiles, R, slots=int(lib.radmmm_gemm_cu_slots()))              # one workgroup per CU
+    P = torch.empty(S, 1, Mc, Nc, device=gh.device, dtype=torch.float32)
+    check(lib.radmmm_wgrad_rm_shift(ptr(gh), ptr(gl), gh.shape[1], g_col0, ptr(xh), ptr(xl), xh.shape[1], x_col0, shift0, R, T,
+                                    ptr(lens), 1 if lens is not None else 0, ptr(P), Nc, P.stride(0), Mc, Nc, 1, 1, S, acc_scale,
+                                    stream()), "wgrad_rm_shift")
+    return P
+
+
+def wgrad_rmh_shift_slabs(gh, g_col0, xh, x_col0, shift0, B, T, Mc, Nc, acc_scale, lens=None):
+    """The same on ONE product from the hi planes alone (radmmm_wgrad_rmh_shift; for leaves of the step) -> P [S, 1, Mc, Nc]."""
+    R = B * T
+    assert gh.shape[0] == R and xh.shape[0] == R and gh.dtype == torch.float16 and xh.dtype == torch.float16
+    assert gh.is_contiguous() and xh.is_contiguous()
+    tiles = int(lib.radmmm_wgrad_rm_tiles(Mc, Nc, 1))
+    S = pick_splits(tiles, R, slots=int(lib.radmmm_gemm_cu_slots()))              # one workgroup per CU
+    P = torch.empty(S, 1, Mc, Nc, device=gh.device, dtype=torch.float32)
+    check(lib.radmmm_wgrad_rmh_shift(ptr(gh), gh.shape[1], g_col0, ptr(xh), xh.shape[1], x_col0, shift0, R, T, ptr(lens),
+                                     1 if lens is not None else 0, ptr(P), Nc, P.stride(0), Mc, Nc, 1, 1, S, acc_scale, stream()),
+          "wgrad_rmh_shift")
+    return P
+
+
 def _all_reduce_or(flags: torch.Tensor) -> torch.Tensor:
     """bitwise OR of small non-negative int32 flag words over the ranks of the default process group.  RCCL / NCCL have no
     BOR reduction (torch raises "Cannot use ReduceOp.BOR with NCCL"): the low 16 bits go out as 0/1 words under MAX."""

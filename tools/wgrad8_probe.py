@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """radmmm_wgrad_rm8 (--products 2, the default) or radmmm_wgrad_rmh (--products 1: the hi planes alone) at the benchmark shapes
 (12 800 frames, 1024 x 1024; 5 taps dil 2 = the in_layer conv, 1 tap = res_skip): launch time, and -- for A/B builds of the
-library (RADMMM_LIB_PATH) -- a dump / bit comparison of the results.
-    python tools/wgrad8_probe.py [--products 1] [--dump FILE | --compare FILE] [--reps 30] [--loop N]   (--loop: launches only, for rocprofv3 --pmc)"""
+library (RADMMM_LIB_PATH) -- a dump / bit comparison of the results.  --lstm: the context LSTM's weight-gradient shapes instead
+(4192 x 1048, and 2096 x 524 with the frame shift -1 / +1, on three products and on one; lstm_shapes).
+    python tools/wgrad8_probe.py [--products 1] [--dump FILE | --compare FILE] [--reps 30] [--loop N]   (--loop: launches only, for rocprofv3 --pmc)
+    python tools/wgrad8_probe.py --lstm [--reps 30]"""
 import argparse
 import json
 import os
@@ -13,8 +15,71 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def lstm_shapes(args, ops, dev, B, T, I=1048, H=524):
+    """The context LSTM's three weight gradients (12 800 frames): dW_ih 4192 x 1048 and the two dW_hh 2096 x 524 read out of y
+    through the frame shift -1 / +1, on three products (radmmm_wgrad_rm / _rm_shift) and on one (radmmm_wgrad_rmh_shift), with
+    the split passes that feed them (y's grouped planes) -- and what the recurrent pair cost before: h_prev as a tensor (zero
+    fill, two strided copies, two .contiguous(), two split passes) and two radmmm_wgrad_rm launches on it."""
+    g = torch.Generator().manual_seed(1)
+    R = B * T
+    dG = (torch.randn(R, 8 * H, generator=g) * 3e-3).to(dev)
+    x = torch.randn(R, I, generator=g).to(dev)
+    y = torch.tanh(torch.randn(R, 2 * H, generator=g)).to(dev)
+    SG = 2048.0
+    gh, gl = ops.split_f16(dG, 8 * H, SG, 8 * H)
+    xh, xl = ops.split_f16(x, I, 1.0, ops.round_up(I, 32))
+    yh, yl = ops.split_f16_groups(y, H, 2)
+    Hg = yh.shape[1] // 2
+
+    def h_prev_path():
+        y3 = y.view(B, T, 2 * H)
+        hp = torch.zeros(B, T, 2 * H, device=dev, dtype=torch.float32)
+        hp[:, 1:, :H] = y3[:, :-1, :H]
+        hp[:, :-1, H:] = y3[:, 1:, H:]
+        hp = hp.view(R, 2 * H)
+        Hq = ops.round_up(H, 8)
+        hpf = ops.split_f16(hp[:, :H].contiguous(), H, 1.0, Hq)
+        hpr = ops.split_f16(hp[:, H:].contiguous(), H, 1.0, Hq)
+        return (ops.wgrad_rm_slabs((gh[:, :4 * H], gl[:, :4 * H]), hpf, B, T, 4 * H, H, 1, 1, 1.0 / SG),
+                ops.wgrad_rm_slabs((gh[:, 4 * H:], gl[:, 4 * H:]), hpr, B, T, 4 * H, H, 1, 1, 1.0 / SG))
+
+    def shifted3():
+        pair = ops.split_f16_groups(y, H, 2)
+        return (ops.wgrad_rm_shift_slabs((gh, gl), 0, pair, 0, -1, B, T, 4 * H, H, 1.0 / SG),
+                ops.wgrad_rm_shift_slabs((gh, gl), 4 * H, pair, Hg, 1, B, T, 4 * H, H, 1.0 / SG))
+
+    def shifted1():
+        hi, _ = ops.split_f16_groups(y, H, 2, with_lo=False)
+        return (ops.wgrad_rmh_shift_slabs(gh, 0, hi, 0, -1, B, T, 4 * H, H, 1.0 / SG),
+                ops.wgrad_rmh_shift_slabs(gh, 4 * H, hi, Hg, 1, B, T, 4 * H, H, 1.0 / SG))
+
+    cases = [("dW_ih 4192 x 1048, three products", 8 * H * I, lambda: ops.wgrad_rm_slabs((gh, gl), (xh, xl), B, T, 8 * H, I, 1, 1, 1.0 / SG)),
+             ("dW_ih 4192 x 1048, one product", 8 * H * I, lambda: ops.wgrad_rmh_shift_slabs(gh, 0, xh, 0, 0, B, T, 8 * H, I, 1.0 / SG)),
+             ("dW_hh 2096 x 524, shift -1, three products", 4 * H * H, lambda: ops.wgrad_rm_shift_slabs((gh, gl), 0, (yh, yl), 0, -1, B, T, 4 * H, H, 1.0 / SG)),
+             ("dW_hh 2096 x 524, shift +1, three products", 4 * H * H, lambda: ops.wgrad_rm_shift_slabs((gh, gl), 4 * H, (yh, yl), Hg, 1, B, T, 4 * H, H, 1.0 / SG)),
+             ("dW_hh 2096 x 524, shift -1, one product", 4 * H * H, lambda: ops.wgrad_rmh_shift_slabs(gh, 0, yh, 0, -1, B, T, 4 * H, H, 1.0 / SG)),
+             ("dW_hh 2096 x 524, shift +1, one product", 4 * H * H, lambda: ops.wgrad_rmh_shift_slabs(gh, 4 * H, yh, Hg, 1, B, T, 4 * H, H, 1.0 / SG)),
+             ("both dW_hh with their operands: h_prev tensor + 2 x wgrad_rm (before)", 8 * H * H, h_prev_path),
+             ("both dW_hh with their operands: grouped split of y + 2 x shifted, three products", 8 * H * H, shifted3),
+             ("both dW_hh with their operands: grouped hi plane of y + 2 x shifted, one product", 8 * H * H, shifted1)]
+    a, b = h_prev_path(), shifted3()
+    print("shifted three-product slabs vs the h_prev path:", "bit-identical" if all(torch.equal(p, q) for p, q in zip(a, b)) else "DIFFERENT")
+    for name, mn, fn in cases:
+        fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) * 1e3 / args.reps
+        print(json.dumps({"case": name, "us": round(us, 1), "fp32_equiv_tflops": round(2.0 * R * mn / us / 1e6, 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--lstm", action="store_true", help="the context LSTM's weight-gradient shapes instead of the WN convs'")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--dump")
     ap.add_argument("--compare")
@@ -32,6 +97,9 @@ def main():
     SG = 2048.0
     gh, gx = ops.split_f16(gy, C, SG, C, 2, ops.X8_GRAD_EXP)
     xh, xx = ops.split_f16(x, C, 1.0, C, 2, ops.X8_ACT_EXP)
+    if args.lstm:
+        lstm_shapes(args, ops, dev, B, T)
+        return
     cases = [("in_layer (5 taps, dil 2, masked)", 5, 2, lens), ("res_skip (1 tap)", 1, 1, None), ("5 taps, dil 1, masked", 5, 1, lens)]
     outs = {}
     for name, taps, dil, ln in cases:

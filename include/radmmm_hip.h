@@ -273,6 +273,25 @@ int radmmm_weightnorm_bwd(const float* v, const float* g, const float* inv_norm,
                                                  to finite values; this puts the non-finite result back where an AMP
                                                  GradScaler or a gradient-norm clip looks for it) */,
                           radmmm_stream_t stream);
+/* radmmm_weightnorm_bwd of up to 8 one-tap tensors (taps must be 1) in ONE launch: one workgroup per (item, output
+ * channel) running the single call's register kernel, so dv / dg are what n calls of radmmm_weightnorm_bwd write on the same
+ * slabs, bit for bit.  `poison` is shared.  Only items of the register path are taken -- Cin a multiple of 4 and <= 2048;
+ * perm_split, off_lo, off_hi, ldw, split_stride multiples of 4; 16-byte aligned dW, v, dv -- anything else returns -1
+ * ("weightnorm_bwd_multi: ... register path") before any HIP call and is left to per-item calls.  Additive entry point of
+ * ABI 4. */
+typedef struct radmmm_wnb_item {
+  const float* v;
+  const float* g;
+  const float* inv_norm;
+  const float* dW;
+  float* dv;
+  float* dg;
+  int64_t split_stride;
+  int splits;
+  int Cout, Cin, ldw;
+  int perm_split, off_lo, off_hi;
+} radmmm_wnb_item;
+int radmmm_weightnorm_bwd_multi(const radmmm_wnb_item* items, int n, int taps, const float* poison, radmmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * WN input assembly (cat((z0, context), 1), common.py:819) in channels-last, K-padded:
@@ -622,6 +641,29 @@ int radmmm_wgrad_rmh_shift(const void* GYh, int ldg, int g_col0, const void* Xh,
 int radmmm_wgrad_rm_shift(const void* GYh, const void* GYl, int ldg, int g_col0, const void* Xh, const void* Xl, int ldx, int x_col0,
                           int shift0, int R, int T, const int32_t* lens, int x_mask, float* P, int ldp, int64_t split_stride,
                           int Mc, int Nc, int taps, int dil, int splits, float acc_scale, radmmm_stream_t stream);
+
+/* Up to 8 one-product weight gradients (radmmm_wgrad_rmh_shift jobs) as ONE launch: the jobs share R, T, taps, dil, lens /
+ * x_mask, shift0, splits and acc_scale; each owns its operands, column origins, extents and slabs.  Job k contributes
+ * radmmm_wgrad_rm_tiles(Mc, Nc, taps) * splits workgroups, laid out one job after the other; a workgroup finds its job through
+ * a table of first tiles in the kernel arguments and from there runs the single launch's code with that job's values: the
+ * tiles of a job are decoded as a launch of that job alone with the same `splits` decodes them, and its slabs are those
+ * launches' slabs bit for bit.  For contractions whose operands are ready at the same moment and whose single launches are
+ * too short to fill the machine without a large split factor (the four res/skip 1x1 convs of a WN: 64 tiles, splits 4,
+ * instead of four launches of 16 tiles with splits 15 -- a quarter of the slab traffic).  Every job must pass
+ * radmmm_wgrad_rmh_shift's checks; 1 <= n <= 8.  Bad arguments return -1 before any HIP call.  Additive entry point of
+ * ABI 4. */
+typedef struct radmmm_wg_item {
+  const void* GYh; /* base of the [R][ldg] fp16 hi plane */
+  const void* Xh;  /* base of the [R][ldx] fp16 hi plane */
+  float* P;        /* slabs [splits][taps][Mc][ldp], split_stride floats apart */
+  int64_t split_stride;
+  int ldg, g_col0;
+  int ldx, x_col0;
+  int Mc, Nc;
+  int ldp;
+} radmmm_wg_item;
+int radmmm_wgrad_rmh_group(const radmmm_wg_item* items, int n, int shift0, int R, int T, const int32_t* lens, int x_mask, int taps,
+                           int dil, int splits, float acc_scale, radmmm_stream_t stream);
 
 /* fp16 hi (and, unless lo is NULL, lo) planes of `groups` column groups of x [rows][ld]: group g holds columns
  * [g * gcols, (g + 1) * gcols) of x, scaled, at columns [g * gpitch, g * gpitch + gcols) of hi / lo [rows][ldh]; every other

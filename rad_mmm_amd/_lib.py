@@ -76,6 +76,20 @@ class DactItem(C.Structure):
     _fields_ = [("saved", C.c_void_p), ("yh", C.c_void_p), ("yl", C.c_void_p), ("ylo16", C.c_void_p), ("part", C.c_void_p)]
 
 
+class WgItem(C.Structure):
+    """radmmm_wg_item: one job of radmmm_wgrad_rmh_group (operands, column origins, extents, slabs)"""
+    _fields_ = [("GYh", C.c_void_p), ("Xh", C.c_void_p), ("P", C.c_void_p), ("split_stride", C.c_int64),
+                ("ldg", C.c_int), ("g_col0", C.c_int), ("ldx", C.c_int), ("x_col0", C.c_int), ("Mc", C.c_int), ("Nc", C.c_int),
+                ("ldp", C.c_int)]
+
+
+class WnbItem(C.Structure):
+    """radmmm_wnb_item: one tensor of radmmm_weightnorm_bwd_multi"""
+    _fields_ = [("v", C.c_void_p), ("g", C.c_void_p), ("inv_norm", C.c_void_p), ("dW", C.c_void_p), ("dv", C.c_void_p),
+                ("dg", C.c_void_p), ("split_stride", C.c_int64), ("splits", C.c_int), ("Cout", C.c_int), ("Cin", C.c_int),
+                ("ldw", C.c_int), ("perm_split", C.c_int), ("off_lo", C.c_int), ("off_hi", C.c_int)]
+
+
 class SplitOpts(C.Structure):
     """radmmm_split_opts: format of a split producer's second array (SPLIT_F16 / SPLIT_X8A / SPLIT_X8B), exponent of its
     8-bit parts, optional device saturation flag."""
@@ -174,6 +188,8 @@ def _load() -> C.CDLL:
         "radmmm_wgrad_rm8": [p, p, i, i, p, p, i, i, i, i, p, i, p, i, i64, i, i, i, i, i, f, p],
         "radmmm_wgrad_rmh": [p, i, p, i, i, i, p, i, p, i, i64, i, i, i, i, i, f, p],
         "radmmm_wgrad_rmh_shift": [p, i, i, p, i, i, i, i, i, p, i, p, i, i64, i, i, i, i, i, f, p],
+        "radmmm_wgrad_rmh_group": [C.POINTER(WgItem), i, i, i, i, p, i, i, i, i, f, p],
+        "radmmm_weightnorm_bwd_multi": [C.POINTER(WnbItem), i, i, p, p],
         "radmmm_wgrad_rm_shift": [p, p, i, i, p, p, i, i, i, i, i, p, i, p, i, i64, i, i, i, i, i, f, p],
         "radmmm_split_f16_groups": [p, i, p, p, i, i, i, i, i, f, p, p],
         "radmmm_betabinom_prior": [i, i, C.c_double, p, p],

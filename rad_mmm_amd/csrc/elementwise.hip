@@ -133,13 +133,12 @@ __global__ __launch_bounds__(256) void weightnorm_bwd_lds_kernel(
 // which is what a launch with one workgroup per output channel costs (20 us for a 1x1 conv's 12 MB, 32 us for a 5-tap
 // conv's 100 MB); here the only dependency is the block sum.  Needs the 16-byte conditions of the VEC path.
 template <int TAPS>
-__global__ __launch_bounds__(256) void weightnorm_bwd_reg_kernel(
+__device__ __forceinline__ void weightnorm_bwd_reg_row(
     const float* __restrict__ v, const float* __restrict__ g, const float* __restrict__ inv_norm,
     const float* __restrict__ dW, int splits, long long split_stride, float* __restrict__ dv,
     float* __restrict__ dg, int Cout, int Cin, int ldw, int perm_split, int off_lo, int off_hi,
-    const float* __restrict__ poison) {
+    const float* __restrict__ poison, int co) {
   __shared__ float sh[17];
-  const int co = blockIdx.x;
   const long long n = (long long)Cin * TAPS;
   const float inv = inv_norm[co], gg = g[co], pz = poison ? poison[0] : 0.f;
   constexpr int MAXJ = 2;                                           // Cin <= 2048 (the host checks)
@@ -194,6 +193,36 @@ __global__ __launch_bounds__(256) void weightnorm_bwd_reg_kernel(
       for (int k = 0; k < TAPS; ++k) *reinterpret_cast<float4*>(dp + 4 * k) = make_float4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
     }
   }
+}
+
+template <int TAPS>
+__global__ __launch_bounds__(256) void weightnorm_bwd_reg_kernel(
+    const float* __restrict__ v, const float* __restrict__ g, const float* __restrict__ inv_norm,
+    const float* __restrict__ dW, int splits, long long split_stride, float* __restrict__ dv,
+    float* __restrict__ dg, int Cout, int Cin, int ldw, int perm_split, int off_lo, int off_hi,
+    const float* __restrict__ poison) {
+  weightnorm_bwd_reg_row<TAPS>(v, g, inv_norm, dW, splits, split_stride, dv, dg, Cout, Cin, ldw, perm_split, off_lo, off_hi, poison, blockIdx.x);
+}
+
+// Up to WNB_MAX tensors in one launch (radmmm_weightnorm_bwd_multi): workgroup b belongs to the item whose run of output
+// channels [first[k], first[k + 1]) holds b and runs the register kernel's code on that item's values -- the same
+// instructions in the same order as the single launch, so dv / dg are its results bit for bit.
+constexpr int WNB_MAX = 8;
+struct WnbGroup {
+  radmmm_wnb_item it[WNB_MAX];
+  int first[WNB_MAX + 1];                // first[k]: output channels of the items before k; first[n .. WNB_MAX] = all
+  const float* poison;
+};
+template <int TAPS>
+__global__ __launch_bounds__(256) void weightnorm_bwd_multi_kernel(const WnbGroup m) {
+  const int b = blockIdx.x;
+  int k = 0;
+#pragma unroll
+  for (int q = 1; q < WNB_MAX; ++q) k += b >= m.first[q] ? 1 : 0;
+  k = __builtin_amdgcn_readfirstlane(k);
+  const radmmm_wnb_item& t = m.it[k];
+  weightnorm_bwd_reg_row<TAPS>(t.v, t.g, t.inv_norm, t.dW, t.splits, (long long)t.split_stride, t.dv, t.dg, t.Cout, t.Cin, t.ldw,
+                               t.perm_split, t.off_lo, t.off_hi, m.poison, b - m.first[k]);
 }
 
 // ------------------------------------------------------------------ WN input assembly
@@ -624,6 +653,32 @@ extern "C" int radmmm_weightnorm_bwd(const float* v, const float* g, const float
                        off_lo, off_hi, poison);
   }
   return radmmm::check_launch("weightnorm_bwd");
+}
+
+extern "C" int radmmm_weightnorm_bwd_multi(const radmmm_wnb_item* items, int n, int taps, const float* poison,
+                                           radmmm_stream_t stream) {
+  RADMMM_REQUIRE(items, "weightnorm_bwd_multi: null items");
+  RADMMM_REQUIRE(n >= 1 && n <= WNB_MAX, "weightnorm_bwd_multi: n=%d items (1 .. %d)", n, WNB_MAX);
+  RADMMM_REQUIRE(taps == 1, "weightnorm_bwd_multi: taps=%d (one-tap tensors only)", taps);
+  WnbGroup m = {};
+  long long total = 0;
+  auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  for (int k = 0; k < n; ++k) {
+    const radmmm_wnb_item& t = items[k];
+    RADMMM_REQUIRE(t.v && t.g && t.inv_norm && t.dW && t.dv && t.dg, "weightnorm_bwd_multi: null pointer (item %d)", k);
+    RADMMM_REQUIRE(t.Cout > 0 && t.Cin > 0 && t.ldw >= t.Cin && t.splits >= 1, "weightnorm_bwd_multi: bad dims (item %d)", k);
+    RADMMM_REQUIRE(t.Cin % 4 == 0 && t.Cin <= 2048 && t.perm_split % 4 == 0 && t.off_lo % 4 == 0 && t.off_hi % 4 == 0 &&
+                       t.ldw % 4 == 0 && t.split_stride % 4 == 0 && a16(t.dW) && a16(t.v) && a16(t.dv),
+                   "weightnorm_bwd_multi: item %d is not on the register path (Cin %% 4 == 0, Cin <= 2048, 16-byte conditions)", k);
+    m.it[k] = t;
+    m.first[k] = (int)total;
+    total += t.Cout;
+    RADMMM_REQUIRE(total < 0x7fffffffLL, "weightnorm_bwd_multi: too many output channels");
+  }
+  for (int k = n; k <= WNB_MAX; ++k) m.first[k] = (int)total;
+  m.poison = poison;
+  hipLaunchKernelGGL(weightnorm_bwd_multi_kernel<1>, dim3((unsigned)total), dim3(256), 0, ST(stream), m);
+  return radmmm::check_launch("weightnorm_bwd_multi");
 }
 
 extern "C" int radmmm_wn_input_fwd(const float* ctx, int ldctx, const float* z, int ldz, float* X0,

@@ -25,6 +25,10 @@
 // leaves of the step, whose rounding feeds nothing else.  The same tile machine (tiles, tile order, split-K ranges, masks,
 // tap shifts, accumulation order k block 0, k block 1 per step, stores) without the lo8 planes: a stage is the two hi arrays
 // (32 KiB), a wave issues 8 DMA pieces per step, and there are no 8-bit fragments, conversions or scaled MFMAs (hh_steps).
+//
+// GROUPED launch (wgrad_rmh_group_kernel, radmmm_wgrad_rmh_group): up to 8 one-product contractions over the same frames as one
+// launch -- a job table in front of the same tile code (wgrad_rm8_tile), so that short contractions fill the machine together
+// with a small split factor instead of each with a large one.
 #include <cstdlib>
 #include <type_traits>
 
@@ -251,8 +255,17 @@ __device__ __forceinline__ void hh_steps(f32x16 (&acc)[8][2], unsigned sm_base, 
   __syncthreads();                                                 // the trailing (out-of-range) pieces and look-ahead reads
 }
 
+// XCD-aware tile order of a launch of nt workgroups: workgroup wg runs on XCD wg & 7 and takes the (wg >> 3)-th tile of that
+// XCD's contiguous run of tiles
+__device__ __forceinline__ int xcd_tile_id(int nt, int wg) {
+  const int xcd = wg & 7, loc = wg >> 3, qq = nt >> 3, r8 = nt & 7;
+  return (xcd < r8 ? xcd * (qq + 1) : r8 * (qq + 1) + (xcd - r8) * qq) + loc;
+}
+
+// The workgroup's whole work on tile `id` (tn, tm, tap, split: tn fastest) of the contraction `a`: the body of the plain
+// launches (id = the launch's XCD-ordered tile) and of the grouped launch (id = the tile within the workgroup's job).
 template <int PR>
-__global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
+__device__ __forceinline__ void wgrad_rm8_tile(const Rm8Args& a, int id) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
   constexpr int STAGE = stage_bytes(PR);
   constexpr int NPIECE = PR == 2 ? 12 : 8;                              // DMA pieces of one wave per stage
@@ -260,9 +273,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntm = (a.Mc + TM - 1) / TM, ntn = (a.Nc + TN - 1) / TN;
-  const int nt = ntm * ntn * a.taps * a.splits, wg = blockIdx.x;
-  const int xcd = wg & 7, loc = wg >> 3, qq = nt >> 3, r8 = nt & 7;
-  int id = (xcd < r8 ? xcd * (qq + 1) : r8 * (qq + 1) + (xcd - r8) * qq) + loc;
   const int tn = id % ntn; id /= ntn;
   const int tm = id % ntm; id /= ntm;
   const int tap = id % a.taps;
@@ -579,6 +589,51 @@ __global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
   }
 }
 
+template <int PR>
+__global__ __launch_bounds__(256, 1) void wgrad_rm8_kernel(const Rm8Args a) {
+  const int nt = ((a.Mc + TM - 1) / TM) * ((a.Nc + TN - 1) / TN) * a.taps * a.splits;
+  wgrad_rm8_tile<PR>(a, xcd_tile_id(nt, blockIdx.x));
+}
+
+// ---- The grouped launch (radmmm_wgrad_rmh_group): up to WG_MAX one-product contractions that share the frames (R, T, lens),
+// the taps and the split factor.  Job k owns the tiles [first[k], first[k + 1]) of the launch; a workgroup takes its tile in
+// the XCD-aware order of the WHOLE launch, finds the job (uniform: scalar compares against the table in the kernel
+// arguments), puts that job's operands, extents and buffer sizes into an Rm8Args view and runs the plain launch's code on
+// the tile's number WITHIN the job -- so a job's tiles are decoded as a launch of that job alone decodes them, each slab
+// element is computed by the same instructions in the same order, and the slabs are those launches' bit for bit.  Nothing
+// is shared between workgroups: no new synchronisation, no atomics.
+constexpr int WG_MAX = 8;
+struct Rm8Job {
+  const _Float16 *GYh, *Xh;
+  float* P;
+  long long split_stride;
+  int ldg, ldx, Mc, Nc, ldp, g_bytes, x_bytes, g_col0, x_col0;
+};
+struct Rm8Group {
+  Rm8Job job[WG_MAX];
+  int first[WG_MAX + 1];                 // first[k]: tiles of the jobs before k; first[n .. WG_MAX] = all tiles
+  const int* lens;
+  int x_mask, R, T, taps, dil, splits, shift0;
+  float acc_scale;
+};
+
+__global__ __launch_bounds__(256, 1) void wgrad_rmh_group_kernel(const Rm8Group g) {
+  const int id = xcd_tile_id(g.first[WG_MAX], blockIdx.x);
+  int k = 0;
+#pragma unroll
+  for (int q = 1; q < WG_MAX; ++q) k += id >= g.first[q] ? 1 : 0;      // (jobs behind the last one start at the total)
+  k = __builtin_amdgcn_readfirstlane(k);
+  const Rm8Job& jb = g.job[k];
+  Rm8Args a = {};
+  a.GYh = jb.GYh; a.Xh = jb.Xh;
+  a.lens = g.lens; a.x_mask = g.x_mask;
+  a.R = g.R; a.T = g.T; a.ldg = jb.ldg; a.ldx = jb.ldx; a.Mc = jb.Mc; a.Nc = jb.Nc; a.taps = g.taps; a.dil = g.dil; a.splits = g.splits;
+  a.P = jb.P; a.ldp = jb.ldp; a.split_stride = jb.split_stride; a.acc_scale = g.acc_scale;
+  a.g_bytes = jb.g_bytes; a.x_bytes = jb.x_bytes;
+  a.g_col0 = jb.g_col0; a.x_col0 = jb.x_col0; a.shift0 = g.shift0;
+  wgrad_rm8_tile<1>(a, id - g.first[k]);
+}
+
 }  // namespace
 
 // GYh / Xh [R][ldg / ldx] row-major fp16 hi planes of scale_g * gy and of x; GYx / Xx the tensors' 8-bit cross arrays
@@ -625,12 +680,9 @@ extern "C" int radmmm_wgrad_rm8(const void* GYh, const void* GYx, int ldg, int g
 
 namespace {
 
-// ONE product: the launch behind radmmm_wgrad_rmh (origins and shift0 all zero) and radmmm_wgrad_rmh_shift.  GYh / Xh are
-// the BASE pointers of the two planes: the buffer resources cover exactly R rows of ldg / ldx halves, and a piece's column
-// test is made on the column within the row (origin included), so no piece reaches beyond the planes.
-int launch_rmh(const char* who, const void* GYh, int ldg, int g_col0, const void* Xh, int ldx, int x_col0, int shift0, int R, int T,
-               const int32_t* lens, int x_mask, float* P, int ldp, int64_t split_stride, int Mc, int Nc, int taps, int dil,
-               int splits, float acc_scale, radmmm_stream_t stream) {
+// ONE product: what a contraction must satisfy (no HIP call) -- shared by the single launches and, per job, by the grouped one
+int check_rmh(const char* who, const void* GYh, int ldg, int g_col0, const void* Xh, int ldx, int x_col0, int shift0, int R, int T,
+              const float* P, int ldp, int Mc, int Nc, int taps, int dil, int splits) {
   RADMMM_REQUIRE(GYh && Xh && P, "%s: null pointer", who);
   RADMMM_REQUIRE(Mc > 0 && Nc > 0 && taps >= 1 && dil >= 1 && splits >= 1 && R > 0 && T > 0 && R % T == 0 && ldg >= Mc &&
                      ldx >= Nc && ldg % 32 == 0 && ldx % 32 == 0 && ldp >= Nc && T >= BK && R / T <= 1024,
@@ -643,6 +695,17 @@ int launch_rmh(const char* who, const void* GYh, int ldg, int g_col0, const void
   RADMMM_REQUIRE(radmmm::aligned16(GYh) && radmmm::aligned16(Xh), "%s: 16-byte aligned operands", who);
   const long long g_bytes = (long long)R * ldg * 2, x_bytes = (long long)R * ldx * 2;
   RADMMM_REQUIRE(g_bytes < 0x7fffffffLL && x_bytes < 0x7fffffffLL, "%s: operand >= 2 GiB", who);
+  return 0;
+}
+
+// The launch behind radmmm_wgrad_rmh (origins and shift0 all zero) and radmmm_wgrad_rmh_shift.  GYh / Xh are the BASE
+// pointers of the two planes: the buffer resources cover exactly R rows of ldg / ldx halves, and a piece's column test is
+// made on the column within the row (origin included), so no piece reaches beyond the planes.
+int launch_rmh(const char* who, const void* GYh, int ldg, int g_col0, const void* Xh, int ldx, int x_col0, int shift0, int R, int T,
+               const int32_t* lens, int x_mask, float* P, int ldp, int64_t split_stride, int Mc, int Nc, int taps, int dil,
+               int splits, float acc_scale, radmmm_stream_t stream) {
+  if (const int bad = check_rmh(who, GYh, ldg, g_col0, Xh, ldx, x_col0, shift0, R, T, P, ldp, Mc, Nc, taps, dil, splits)) return bad;
+  const long long g_bytes = (long long)R * ldg * 2, x_bytes = (long long)R * ldx * 2;
   static int once = [] {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_rm8_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        smem_bytes(1) + 4096);
@@ -684,4 +747,45 @@ extern "C" int radmmm_wgrad_rmh_shift(const void* GYh, int ldg, int g_col0, cons
                                       int Nc, int taps, int dil, int splits, float acc_scale, radmmm_stream_t stream) {
   return launch_rmh("wgrad_rmh_shift", GYh, ldg, g_col0, Xh, ldx, x_col0, shift0, R, T, lens, x_mask, P, ldp, split_stride, Mc, Nc,
                     taps, dil, splits, acc_scale, stream);
+}
+
+// Up to 8 such contractions as ONE launch (wgrad_rmh_group_kernel): every job passes the single launch's checks before any
+// HIP call; job k's buffer resources cover exactly its own planes.
+extern "C" int radmmm_wgrad_rmh_group(const radmmm_wg_item* items, int n, int shift0, int R, int T, const int32_t* lens, int x_mask,
+                                      int taps, int dil, int splits, float acc_scale, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(items, "wgrad_rmh_group: null items");
+  RADMMM_REQUIRE(n >= 1 && n <= WG_MAX, "wgrad_rmh_group: n=%d jobs (1 .. %d)", n, WG_MAX);
+  Rm8Group g = {};
+  long long total = 0;
+  for (int k = 0; k < n; ++k) {
+    const radmmm_wg_item& t = items[k];
+    if (const int bad = check_rmh("wgrad_rmh_group", t.GYh, t.ldg, t.g_col0, t.Xh, t.ldx, t.x_col0, shift0, R, T, t.P, t.ldp, t.Mc,
+                                  t.Nc, taps, dil, splits))
+      return bad;
+    Rm8Job& jb = g.job[k];
+    jb.GYh = static_cast<const _Float16*>(t.GYh); jb.Xh = static_cast<const _Float16*>(t.Xh);
+    jb.P = t.P; jb.split_stride = t.split_stride;
+    jb.ldg = t.ldg; jb.ldx = t.ldx; jb.Mc = t.Mc; jb.Nc = t.Nc; jb.ldp = t.ldp;
+    jb.g_bytes = (int)((long long)R * t.ldg * 2); jb.x_bytes = (int)((long long)R * t.ldx * 2);
+    jb.g_col0 = t.g_col0; jb.x_col0 = t.x_col0;
+    g.first[k] = (int)total;
+    total += (long long)((t.Mc + TM - 1) / TM) * ((t.Nc + TN - 1) / TN) * taps * splits;
+    RADMMM_REQUIRE(total < 0x7fffffffLL, "wgrad_rmh_group: too many workgroups");
+  }
+  for (int k = n; k <= WG_MAX; ++k) g.first[k] = (int)total;
+  g.lens = lens; g.x_mask = x_mask;
+  g.R = R; g.T = T; g.taps = taps; g.dil = dil; g.splits = splits; g.shift0 = shift0;
+  g.acc_scale = acc_scale;
+  static int once = [] {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_rmh_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       smem_bytes(1) + 4096);
+    if (e != hipSuccess) {
+      radmmm::set_error("hipFuncSetAttribute(wgrad_rmh_group): %s", hipGetErrorString(e));
+      return -2;
+    }
+    return 0;
+  }();
+  if (once) return once;
+  hipLaunchKernelGGL(wgrad_rmh_group_kernel, dim3((unsigned)total), dim3(256), smem_bytes(1) + 4096, static_cast<hipStream_t>(stream), g);
+  return radmmm::check_launch("wgrad_rmh_group");
 }

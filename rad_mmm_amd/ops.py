@@ -976,6 +976,44 @@ def wgrad_rmh_slabs(gh, xh, B, T, Mc, Nc, taps, dil, acc_scale, lens=None):
     return P
 
 
+def wgrad_rmh_group_slabs(jobs, B, T, taps, dil, acc_scale, lens=None, splits=None, shift0=0):
+    """Up to 8 one-product weight gradients in ONE launch (radmmm_wgrad_rmh_group).  jobs: (gh, xh, Mc, Nc) or
+    (gh, xh, Mc, Nc, g_col0, x_col0) per contraction, the planes as wgrad_rmh_slabs / wgrad_rmh_shift_slabs take them
+    -> list of P [S, taps, Mc, Nc], one per job, with ONE split factor for the launch: pick_splits over the tiles of all
+    jobs unless `splits` says otherwise.  Each P is what a single launch of its job with that split factor writes."""
+    R = B * T
+    jobs = [tuple(j) + (0, 0) * (len(j) == 4) for j in jobs]
+    for gh, xh, Mc, Nc, g0, x0 in jobs:
+        assert gh.shape[0] >= R and xh.shape[0] >= R and gh.dtype == torch.float16 and xh.dtype == torch.float16
+        assert gh.stride(1) == 1 and xh.stride(1) == 1
+    tiles = sum(int(lib.radmmm_wgrad_rm_tiles(Mc, Nc, taps)) for _, _, Mc, Nc, _, _ in jobs)
+    S = splits or pick_splits(tiles, R, slots=int(lib.radmmm_gemm_cu_slots()))
+    Ps = [torch.empty(S, taps, Mc, Nc, device=gh.device, dtype=torch.float32) for gh, _, Mc, Nc, _, _ in jobs]
+    items = (L.WgItem * len(jobs))(*[L.WgItem(ptr(gh), ptr(xh), ptr(P), P.stride(0), gh.stride(0), g0, xh.stride(0), x0, Mc, Nc, Nc)
+                                     for (gh, xh, Mc, Nc, g0, x0), P in zip(jobs, Ps)])
+    check(lib.radmmm_wgrad_rmh_group(items, len(jobs), shift0, R, T, ptr(lens), 1 if lens is not None else 0, taps, dil, S,
+                                     acc_scale, stream()), "wgrad_rmh_group")
+    return Ps
+
+
+def weightnorm_bwd_multi(vs, gs, invs, slabs, ldw: int, poison: Optional[torch.Tensor] = None):
+    """weightnorm_bwd of several one-tap tensors in ONE launch (radmmm_weightnorm_bwd_multi) -> list of (dv, dg).  Tensors the
+    grouped kernel does not take (its register path's conditions) go through one weightnorm_bwd launch each."""
+    dvs, dgs = [grad_out(v) for v in vs], [grad_out(g) for g in gs]
+    items = (L.WnbItem * len(vs))(*[L.WnbItem(ptr(v), ptr(g), ptr(inv), ptr(P), ptr(dv), ptr(dg), P.stride(0), P.shape[0],
+                                              v.shape[0], v.shape[1], ldw, 0, 0, 0)
+                                    for v, g, inv, P, dv, dg in zip(vs, gs, invs, slabs, dvs, dgs)])
+    one_tap = all(v.shape[2] == 1 for v in vs)
+    rc = lib.radmmm_weightnorm_bwd_multi(items, len(vs), 1, ptr(poison), stream()) if one_tap else -1
+    if not one_tap or (rc == -1 and b"register path" in lib.radmmm_last_error()):
+        for v, g, inv, P, dv, dg in zip(vs, gs, invs, slabs, dvs, dgs):
+            check(lib.radmmm_weightnorm_bwd(ptr(v), ptr(g), ptr(inv), ptr(P), P.shape[0], P.stride(0), ptr(dv), ptr(dg), v.shape[0],
+                                            v.shape[1], v.shape[2], ldw, 0, 0, 0, ptr(poison), stream()), "weightnorm_bwd")
+    else:
+        check(rc, "weightnorm_bwd_multi")
+    return list(zip(dvs, dgs))
+
+
 def split_f16_groups(x, gcols, groups, scale=1.0, gpitch=None, with_lo=True, sat_flag=None):
     """fp16 hi / lo planes [rows, groups * gpitch] of x [rows, >= groups * gcols]: column group g of x (gcols wide) lands at
     columns g * gpitch .. of the planes, zeros in between (radmmm_split_f16_groups; the bits of split_f16).  gpitch defaults to
@@ -1692,6 +1730,18 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
             gq_sums = dact_mul_rows_multi(gOUT, [R[j] for j in range(nl)], Wc, B, T, act, SG, gq_dst, [None] * nl, fa, GE, flag,
                                           [grad_out(res_p[3 * j + 2]) for j in range(nl)], defer=batch)
             gq_pre = (gq_dst, gq_sums)
+        # All nl res/skip weight gradients dW_res[j] = gQ_j^T H_{j+1} are ready here (the gQ_j just written, the H_{j+1} saved
+        # by forward) and nothing downstream reads them: ONE grouped launch (radmmm_wgrad_rmh_group) whose split factor is
+        # picked for the tiles of all of them -- a quarter of the slabs of nl launches -- and ONE weight-norm backward
+        # (DESIGN 4.8).  One-product weight gradients only; RADMMM_WGRAD_GROUP=0 (RADMMM_DEBUG): per-layer launches as before.
+        grouped = bool(multi and pair_only and plan.wgrad_products == 1 and debug_env("RADMMM_WGRAD_GROUP", "1") != "0")
+        if grouped:
+            res_slabs = wgrad_rmh_group_slabs([(gq_dst[j][0], Hpair[j + 1][0], Wc, Wc) for j in range(nl)], B, T, 1, 1, 1.0 / SG)
+            res_g = weightnorm_bwd_multi([res_p[3 * j] for j in range(nl)], [res_p[3 * j + 1] for j in range(nl)],
+                                         [inv_r[j] for j in range(nl)], res_slabs, Wc, poison=poison)
+            for j in range(nl):
+                g_res[3 * j], g_res[3 * j + 1] = res_g[j]
+            del res_slabs
         for j in range(nl - 1, -1, -1):
             d = 2 ** j
             kt = in_p[3 * j].shape[2]
@@ -1708,15 +1758,18 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
                 # operand, as the weight gradient's transposed split operand and as bias sums in one pass (no fp32 gQ)
                 gy_t, g_res[3 * j + 2] = dact_mul_transposed(gOUT, R[j], Wc, B, T, act, SG, None if use_rm else "gy", gQh, gQl, fa,
                                                              GE, flag, sum_out=grad_out(res_p[3 * j + 2]), defer=batch)
-            if use_rm:
+            if grouped:
+                slabs = None                         # (g_res[3 j], g_res[3 j + 1]: the grouped launches above)
+            elif use_rm:
                 slabs = wg_rm((gQh, gQl), Hpair[j + 1], Wc, Wc, 1, 1)
             else:
                 # H[j+1]'s transposed copy may still be in the pool from layer j+1's in_layer weight gradient (x_prev, set
                 # below only when that length-masked copy is IDENTICAL to the unmasked one this gradient needs)
                 x_t = x_prev if x_prev is not None else transpose_split_act(H[j + 1], Wc, B, T, None, 0, 1.0, "x")
                 slabs = wgrad_h3_slabs(gy_t, x_t, Wc, Wc, Wc, 1, 1, 1.0 / SG, WPR)
-            g_res[3 * j], g_res[3 * j + 1] = weightnorm_bwd(res_p[3 * j], res_p[3 * j + 1], inv_r[j], slabs, Wc, poison=poison)
-            keep_pair = j > 0                        # g_conv_j's split copy becomes the first half of the next pair
+            if not grouped:
+                g_res[3 * j], g_res[3 * j + 1] = weightnorm_bwd(res_p[3 * j], res_p[3 * j + 1], inv_r[j], slabs, Wc, poison=poison)
+            keep_pair = j > 0                       # g_conv_j's split copy becomes the first half of the next pair
             nh, nlo = pre_pairs[j] if (keep_pair and j in pre_pairs) else _halves(2 * N if keep_pair else N, Wc, like=z_in)
             gch, gcl = nh[:N], nlo[:N]
             # the fp32 copy of the pre-activation gradient is read by nobody when its bias sums come out of the epilogue

@@ -2,9 +2,12 @@
 """radmmm_wgrad_rm8 (--products 2, the default) or radmmm_wgrad_rmh (--products 1: the hi planes alone) at the benchmark shapes
 (12 800 frames, 1024 x 1024; 5 taps dil 2 = the in_layer conv, 1 tap = res_skip): launch time, and -- for A/B builds of the
 library (RADMMM_LIB_PATH) -- a dump / bit comparison of the results.  --lstm: the context LSTM's weight-gradient shapes instead
-(4192 x 1048, and 2096 x 524 with the frame shift -1 / +1, on three products and on one; lstm_shapes).
+(4192 x 1048, and 2096 x 524 with the frame shift -1 / +1, on three products and on one; lstm_shapes).  --group: a flow step's
+four res_skip weight gradients with their weight-norm backward, grouped (radmmm_wgrad_rmh_group + radmmm_weightnorm_bwd_multi)
+against four single launches each (group_row).
     python tools/wgrad8_probe.py [--products 1] [--dump FILE | --compare FILE] [--reps 30] [--loop N]   (--loop: launches only, for rocprofv3 --pmc)
-    python tools/wgrad8_probe.py --lstm [--reps 30]"""
+    python tools/wgrad8_probe.py --lstm [--reps 30]
+    python tools/wgrad8_probe.py --group"""
 import argparse
 import json
 import os
@@ -77,9 +80,54 @@ def lstm_shapes(args, ops, dev, B, T, I=1048, H=524):
         print(json.dumps({"case": name, "us": round(us, 1), "fp32_equiv_tflops": round(2.0 * R * mn / us / 1e6, 1)}), flush=True)
 
 
+def group_row(ops, dev, B, T, C, SG, gh, xh, reps=50):
+    """A flow step's four res/skip weight gradients (1 tap, 1024 x 1024, 12 800 rows, four operand pairs): four
+    radmmm_wgrad_rmh launches + four radmmm_weightnorm_bwd against one radmmm_wgrad_rmh_group + one
+    radmmm_weightnorm_bwd_multi, event-timed over 50 repetitions; the grouped slabs against single launches at the grouped
+    split factor (bit for bit) and the summed gradients against the per-conv split factor."""
+    g = torch.Generator().manual_seed(2)
+    pairs = [(gh, xh)] + [((torch.randn(B * T, C, generator=g) * 3e-3 * SG).half().to(dev),
+                           torch.nn.functional.softplus(torch.randn(B * T, C, generator=g) * 2).half().to(dev)) for _ in range(3)]
+    vs = [torch.randn(C, C, 1, generator=g).to(dev) for _ in range(4)]
+    gs = [torch.randn(C, 1, 1, generator=g).to(dev) for _ in range(4)]
+    invs = [(1.0 / v.flatten(1).norm(dim=1)).contiguous() for v in vs]
+    jobs = [(a, b, C, C) for a, b in pairs]
+
+    def singles():
+        return [ops.wgrad_rmh_slabs(a, b, B, T, C, C, 1, 1, 1.0 / SG) for a, b in pairs]
+
+    def grouped():
+        return ops.wgrad_rmh_group_slabs(jobs, B, T, 1, 1, 1.0 / SG)
+
+    Ps, Pg = singles(), grouped()
+    Sg = int(Pg[0].shape[0])
+    at_sg = [ops.wgrad_rmh_group_slabs([j], B, T, 1, 1, 1.0 / SG, splits=Sg)[0] for j in jobs]
+    same = all(torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip(Pg, at_sg))
+    rel = max(float((p.sum(0) - q.sum(0)).abs().max() / q.sum(0).abs().max()) for p, q in zip(Pg, Ps))
+    print(f"grouped slabs vs single launches at S = {Sg}: {'bit-identical' if same else 'DIFFERENT'}; summed gradient vs S = "
+          f"{int(Ps[0].shape[0])}: max rel diff {rel:.2e}")
+    cases = [("4 x wgrad_rmh", singles), ("wgrad_rmh_group", grouped),
+             ("4 x weightnorm_bwd", lambda: [ops.weightnorm_bwd(v, gg, inv, P, C) for v, gg, inv, P in zip(vs, gs, invs, Ps)]),
+             ("weightnorm_bwd_multi", lambda: ops.weightnorm_bwd_multi(vs, gs, invs, Pg, C)),
+             ("4 x (wgrad_rmh + weightnorm_bwd)", lambda: [ops.weightnorm_bwd(v, gg, inv, P, C) for v, gg, inv, P in zip(vs, gs, invs, singles())]),
+             ("wgrad_rmh_group + weightnorm_bwd_multi", lambda: ops.weightnorm_bwd_multi(vs, gs, invs, grouped(), C))]
+    for name, fn in cases:
+        fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        splits = Sg if "group" in name or "multi" in name else int(Ps[0].shape[0])
+        print(json.dumps({"case": name, "splits": splits, "us": round(e0.elapsed_time(e1) * 1e3 / reps, 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lstm", action="store_true", help="the context LSTM's weight-gradient shapes instead of the WN convs'")
+    ap.add_argument("--group", action="store_true", help="four res_skip jobs: one grouped launch against four single launches")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--dump")
     ap.add_argument("--compare")
@@ -99,6 +147,9 @@ def main():
     xh, xx = ops.split_f16(x, C, 1.0, C, 2, ops.X8_ACT_EXP)
     if args.lstm:
         lstm_shapes(args, ops, dev, B, T)
+        return
+    if args.group:
+        group_row(ops, dev, B, T, C, SG, gh, xh)
         return
     cases = [("in_layer (5 taps, dil 2, masked)", 5, 2, lens), ("res_skip (1 tap)", 1, 1, None), ("5 taps, dil 1, masked", 5, 1, lens)]
     outs = {}

@@ -1059,6 +1059,59 @@ int radmmm_stftloss_bwd(const float* spec_x, const float* spec_y, int lds, const
 int radmmm_stftloss_unframe(const float* dA, int ldk, const int32_t* frames, float* dx, int lddx, int B, int T, int F,
                             int n_fft, int hop, int win, int accum, radmmm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Differentiable log-mel and the mel L1 loss (audio_processing.py: TacotronSTFT.mel_spectrogram, STFT.transform, applied to
+ * each item alone, under F.l1_loss over the valid frames), forward and backward (additive entry points of ABI 4).  The
+ * three dense products are radmmm_rowgemm_f32 launches (frames x forward_basis, mag x mel_basis^T; dmelp x mel_basis and
+ * dspec x forward_basis with b_layout 1); these entry points are what surrounds them.  Geometry: n_fft (a multiple of 4),
+ * hop >= 1, h = n_fft/2, cutoff = n_fft/2 + 1, B items of at most S samples (S > h), F = 1 + S/hop rows per item, r = b*F + f.
+ * `lens` is an int32 device array [B] of samples per item, read clamped into [1, S] (NULL: S everywhere): item b is
+ * reflect-padded by h about 0 and about lens[b] - 1 and has 1 + lens[b]/hop frames.  The caller keeps lens[b] > h; below
+ * that every reflected index is clamped into [0, lens[b] - 1], so nothing is read or written outside an item and the
+ * item's numbers are unspecified but finite.  A mel in the reference layout is [B][n_mel][Ft].  `frames` (int32 device
+ * array [B] or NULL) caps the frames of an item that enter the loss: n[b] = min(1 + lens[b]/hop, Ft, frames[b] clamped into
+ * [0, min(F, Ft)]).  No atomics, fixed reduction orders.
+ *   melloss_frame    A[r*n_fft + j] = x[b*ldx + reflect(f*hop + j - h)] for f < 1 + lens[b]/hop; zeros in the other rows
+ *                    (x not read there, nor at or past lens[b]).  A 16B aligned, B*F*n_fft*4 < 2 GiB.
+ *   melloss_mag      spec [B*F][lds], re in columns [0, cutoff), im in [cutoff, 2 cutoff) -> mag[r*ldm + k] =
+ *                    sqrt(re^2 + im^2) (no clamp); 0 for cutoff <= k < ldm and in rows past an item's frames (spec not read
+ *                    there).  lds, ldm % 4 == 0.
+ *   melloss_terms    melp [B*F][ldn] -> mel = log(max(melp, clip)), the log taken in double and rounded once (melloss_bwd
+ *                    forms the same bits).  mel_out (or NULL) [B][n_mel][F]: the mel, exact zeros
+ *                    past an item's frames.  target [B][n_mel][Ft] with part [B*F] (both or neither): part[r] =
+ *                    sum_c |mel - target[b][c][f]| for f < n[b], else 0; lane l of the row's wave adds channels l, l+64, ...
+ *                    in order, then a xor butterfly.  melp is not read in rows past an item's frames or in columns
+ *                    >= n_mel, target not at frames >= n[b].
+ *   melloss_finish   one workgroup, fp64: norm[0] = sum_b n[b]; out[0] = sum_{f < n[b]} part / (n_mel * norm[0]), 0 when
+ *                    norm[0] == 0.
+ *   melloss_bwd      dmelp [B*F][ldn].  With target (and norm, g; dmel NULL): g[0] * sign(mel - target) / (n_mel * norm[0])
+ *                    / melp for f < n[b], the sign recomputed from melp and target as melloss_terms formed it, sign(0) = 0.
+ *                    With dmel [B][n_mel][F] (target NULL): dmel[b][c][f] / melp for f < 1 + lens[b]/hop.  In both: 0 where
+ *                    melp < clip, in every other row and in columns n_mel <= c < ldn.
+ *   melloss_dspec    dspec[r] = (dmag * re/mag | dmag * im/mag) with mag recomputed from spec as melloss_mag forms it; 0
+ *                    where mag == 0, in rows past an item's frames (nothing read there) and in columns 2 cutoff <= c < lds.
+ *   melloss_unframe  the adjoint of melloss_frame in gather form: dx[b*lddx + s], s < lens[b], is the sum of dA [B*F][n_fft]
+ *                    over the item's frames (ascending) that hold padded position s + h, then h - s for 1 <= s <= h, then
+ *                    h + 2(lens[b]-1) - s for lens[b]-1-h <= s <= lens[b]-2; with accum the sum is added to dx (last).
+ *                    Samples lens[b] <= s < S get 0 (left as they are with accum).
+ * ------------------------------------------------------------------------------------ */
+int radmmm_melloss_frame(const float* x, int ldx, const int32_t* lens, float* A, int B, int S, int F, int n_fft, int hop,
+                         radmmm_stream_t stream);
+int radmmm_melloss_mag(const float* spec, int lds, const int32_t* lens, float* mag, int ldm, int B, int S, int F, int hop,
+                       int cutoff, radmmm_stream_t stream);
+int radmmm_melloss_terms(const float* melp, int ldn, const int32_t* lens, const int32_t* frames, const float* target, int Ft,
+                         float* mel_out, float* part, int B, int S, int F, int hop, int n_mel, float clip,
+                         radmmm_stream_t stream);
+int radmmm_melloss_finish(const float* part, const int32_t* lens, const int32_t* frames, float* out, double* norm, int B,
+                          int S, int F, int Ft, int hop, int n_mel, radmmm_stream_t stream);
+int radmmm_melloss_bwd(const float* melp, int ldn, const int32_t* lens, const int32_t* frames, const float* target, int Ft,
+                       const double* norm, const float* g, const float* dmel, float* dmelp, int B, int S, int F, int hop,
+                       int n_mel, float clip, radmmm_stream_t stream);
+int radmmm_melloss_dspec(const float* dmag, int ldm, const float* spec, int lds, const int32_t* lens, float* dspec, int B,
+                         int S, int F, int hop, int cutoff, radmmm_stream_t stream);
+int radmmm_melloss_unframe(const float* dA, const int32_t* lens, float* dx, int lddx, int B, int S, int F, int n_fft, int hop,
+                           int accum, radmmm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -270,6 +270,13 @@ def _load() -> C.CDLL:
         "radmmm_stftloss_finish": [p, p, p, p, i, i, i, p],
         "radmmm_stftloss_bwd": [p, p, i, p, p, p, p, p, f, p, p, i, i, i, i, p],
         "radmmm_stftloss_unframe": [p, i, p, p, i, i, i, i, i, i, i, i, p],
+        "radmmm_melloss_frame": [p, i, p, p, i, i, i, i, i, p],
+        "radmmm_melloss_mag": [p, i, p, p, i, i, i, i, i, i, p],
+        "radmmm_melloss_terms": [p, i, p, p, p, i, p, p, i, i, i, i, i, f, p],
+        "radmmm_melloss_finish": [p, p, p, p, p, i, i, i, i, i, i, p],
+        "radmmm_melloss_bwd": [p, i, p, p, p, i, p, p, p, p, i, i, i, i, i, f, p],
+        "radmmm_melloss_dspec": [p, i, p, i, p, p, i, i, i, i, i, p],
+        "radmmm_melloss_unframe": [p, p, p, i, i, i, i, i, i, i, p],
     }
     missing = [n for n in sig if not hasattr(lib, n)]
     if missing:

@@ -4,6 +4,7 @@
     python tools/vocoder_bench.py [--iters 5] [--warmup 2] [--no-torch]
     python tools/vocoder_bench.py --train [--iters 5] [--warmup 2]
     python tools/vocoder_bench.py --stft-loss [--iters 5] [--warmup 2] [--out profiles/stft_loss.json]
+    python tools/vocoder_bench.py --mel-loss [--iters 5] [--warmup 2] [--out profiles/mel_loss.json]
 
 Generator and denoiser ms per call at (B, T) = (32, 800) and (1, 800) for the V1 and V3 configs (random weights
 from a seed), the real-time factor (seconds of 22.05 kHz audio per second of compute), per-stage ms of the generator
@@ -22,7 +23,18 @@ one process: the HIP module, a stock-torch implementation with torch.stft and ve
 host read: the strongest stock alternative) and the per-item loop as the reference writes it.  Median of --iters runs
 after --warmup; per form the device launches of one step (torch.profiler) and the host synchronisations
 (torch.cuda.set_sync_debug_mode("warn")).  Then the V1 training step of --train with this loss in place of the quadratic
-one (HIP generator; HIP loss, stock vectorised loss, and the quadratic loss for scale).  The JSON also goes to --out."""
+one (HIP generator; HIP loss, stock vectorised loss, and the quadratic loss for scale).  The JSON also goes to --out.
+
+--mel-loss: the mel L1 loss (rad_mmm_amd/mel_loss.py, TacotronSTFT(1024, 256, 1024, 80, 22050, 0, 8000), ragged sample
+counts on the device), forward plus backward with respect to the prediction, at 16 x 8192 and 32 x 8192 samples, in one
+process, against the same loss written with torch.stft and vectorised masking in fp32.  Per-item reflection is impossible
+for that stock form without a loop over the items, so it reflects every item at the padded length S (torch.stft
+center=True) and masks the frames past 1 + lens[b] // hop: an item's last n_fft / (2 hop) = 2 frames see the zeros behind
+it instead of its mirror image; and it takes sqrt(re^2 + im^2 + 1e-9), as upstream HiFi-GAN's mel does, because torch's
+gradient of sqrt at the all-zero frames behind an item is NaN, which masking cannot remove.  Median of --iters runs after
+--warmup, device launches and host synchronisations of one step as for --stft-loss.  Then the V1 training step of --train
+with 45 * mel + sc + mag (HIP STFT loss in both) through the HIP mel loss and through the stock one.  The JSON also goes
+to --out."""
 import argparse
 import json
 import os
@@ -284,6 +296,98 @@ def stft_loss_bench(args, dev):
     print(json.dumps(res))
 
 
+def stock_mel_loss(stft, dev):
+    """the mel L1 loss with torch.stft and vectorised masking in fp32 (see the module docstring for its two approximations)"""
+    s = stft.stft_fn
+    n_fft, hop, win = s.filter_length, s.hop_length, s.win_length
+    window = torch.hann_window(win, device=dev)
+    mel_basis = stft.mel_basis
+
+    def fn(x, target, lens, frames=None):
+        z = torch.stft(x, n_fft, hop, win, window, center=True, pad_mode="reflect", return_complex=True)
+        mag = torch.sqrt(z.real ** 2 + z.imag ** 2 + 1e-9)
+        mel = torch.log(torch.clamp(torch.matmul(mel_basis, mag), min=1e-5))
+        k = min(mel.shape[2], target.shape[2])
+        n = torch.clamp(1 + torch.div(lens, hop, rounding_mode="floor"), max=k)
+        if frames is not None:
+            n = torch.minimum(n, torch.clamp(frames, min=0, max=k))
+        mask = (torch.arange(k, device=dev)[None, :] < n[:, None]).to(mel.dtype)[:, None, :]
+        return ((mel[:, :, :k] - target[:, :, :k]).abs() * mask).sum() / (mel.shape[1] * n.sum())
+    return fn
+
+
+def mel_loss_bench(args, dev):
+    from rad_mmm_amd.mel_loss import MelSpectrogramLoss, mel_spectrogram
+    from rad_mmm_amd.stft_loss import MultiResolutionSTFTLoss
+    hip = MelSpectrogramLoss().to(dev)
+    stock = stock_mel_loss(hip.stft, dev)
+    hop = hip.stft.stft_fn.hop_length
+    res = {"metric": "mel_loss_fwd_bwd_ms", "stft": [1024, 256, 1024, 80, 22050, 0.0, 8000.0], "iters": args.iters,
+           "warmup": args.warmup, "device": torch.cuda.get_device_name(0),
+           "note": "one GPU, one process, one session; forward + backward with respect to the prediction; ragged sample "
+                   "counts on the device; median of iters after warmup.  torch_vectorised reflects at the padded length and "
+                   "adds 1e-9 under the square root (tools/vocoder_bench.py docstring), so its loss and gradient differ from "
+                   "the HIP module's by that approximation", "shapes": {}}
+    g = torch.Generator().manual_seed(12)
+    for B in (16, 32):
+        S = 8192
+        lengths = torch.linspace(S // 3, S, B).round().long()
+        lens = lengths.to(dev)
+        keep = (torch.arange(S)[None, :] < lengths[:, None]).float()
+        clean = (0.3 * torch.randn(B, S, generator=g) * keep).to(dev)
+        pred = ((clean.cpu() + 0.1 * torch.randn(B, S, generator=g)) * keep).clamp(-1, 1).to(dev)
+        with torch.no_grad():
+            target = mel_spectrogram(clean, hip.stft, lens)
+        row, grads = {}, {}
+        for key, fn in (("hip", hip), ("torch_vectorised", stock)):
+            def step():
+                p = pred.detach().requires_grad_(True)
+                loss = fn(p, target, lens)
+                loss.backward()
+                return loss.detach(), p.grad
+            ms = timed(step, args.iters, args.warmup)
+            launches, syncs = count_launches_and_syncs(step)
+            loss, grads[key] = step()
+            row[key] = {"fwd_bwd_ms": round(ms, 3), "launches": launches, "host_syncs": syncs, "loss": float(loss)}
+        row["torch_vectorised"]["over_hip"] = round(row["torch_vectorised"]["fwd_bwd_ms"] / row["hip"]["fwd_bwd_ms"], 3)
+        row["torch_vectorised"]["grad_rel_l2_vs_hip"] = float((grads["torch_vectorised"] - grads["hip"]).norm() / grads["hip"].norm())
+        res["shapes"][f"B{B}_S{S}"] = row
+        print(json.dumps({f"B{B}_S{S}": row}), file=sys.stderr, flush=True)
+    # the V1 training step of --train with 45 * mel + sc + mag (HIP STFT loss in both forms)
+    gen = HiFiGANGenerator(V1)
+    gen.load_state_dict(random_state(gen, 5, 0.2, 0.6))
+    gen = gen.to(dev).train()
+    stft_loss = MultiResolutionSTFTLoss().to(dev)
+    res["train_step"] = {}
+    for B in (16, 32):
+        Tm = 32
+        S = Tm * gen.hop
+        mel = (torch.randn(B, 80, Tm, generator=g) - 2.0).to(dev)
+        target = (torch.rand(B, S, generator=g) * 2 - 1).to(dev)
+        lens = torch.linspace(Tm // 3, Tm, B).round().long().tolist()
+        frames = torch.tensor(lens, device=dev, dtype=torch.int32)
+        samples = frames * gen.hop
+        ratios = samples.float() / S
+        row = {}
+        for key, mel_fn in (("hip_mel_loss", hip), ("torch_vectorised_mel_loss", stock)):
+            def step():
+                gen.zero_grad(set_to_none=True)
+                audio = gen(mel, lens)[:, 0]
+                sc, mag = stft_loss(audio, target, ratios)
+                (45 * mel_fn(audio, mel, samples, frames) + sc + mag).backward()
+            row[key + "_step_ms"] = round(timed(step, args.iters, args.warmup), 3)
+            row[key + "_launches"], row[key + "_host_syncs"] = count_launches_and_syncs(step)
+        row["torch_over_hip"] = round(row["torch_vectorised_mel_loss_step_ms"] / row["hip_mel_loss_step_ms"], 3)
+        res["train_step"][f"B{B}_T{Tm}"] = row
+        print(json.dumps({f"train_B{B}_T{Tm}": row}), file=sys.stderr, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
@@ -291,8 +395,12 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--train", action="store_true", help="time one V1 training step against stock torch autograd")
     ap.add_argument("--stft-loss", action="store_true", help="time the multi-resolution STFT loss against stock torch")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stft_loss.json"), help="--stft-loss: result file")
+    ap.add_argument("--mel-loss", action="store_true", help="time the mel L1 loss against stock torch")
+    ap.add_argument("--out", default=None, help="--stft-loss / --mel-loss: result file (default profiles/stft_loss.json / "
+                                                "profiles/mel_loss.json)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "mel_loss.json" if args.mel_loss else "stft_loss.json")
     dev = torch.device("cuda:0")
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
@@ -300,6 +408,8 @@ def main():
         return train_bench(args, dev)
     if args.stft_loss:
         return stft_loss_bench(args, dev)
+    if args.mel_loss:
+        return mel_loss_bench(args, dev)
     res = {"metric": "vocoder_ms", "configs": {}}
     for name, cfg in (("V1", V1), ("V3", V3)):
         gen = HiFiGANGenerator(cfg)

@@ -1112,6 +1112,74 @@ int radmmm_melloss_dspec(const float* dmag, int ldm, const float* spec, int lds,
 int radmmm_melloss_unframe(const float* dA, const int32_t* lens, float* dx, int lddx, int B, int S, int F, int n_fft, int hop,
                            int accum, radmmm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * HiFi-GAN multi-period discriminator (hifigan_models.py: DiscriminatorP, MultiPeriodDiscriminator) and the GAN losses of
+ * loss.py (gan_feature_loss, gan_discriminator_loss, gan_generator_loss), forward and backward (additive entry points of
+ * ABI 4).  Every convolution but conv_post is a radmmm_rowgemm_f32 launch in its framed form, every weight gradient a
+ * radmmm_wgrad_f32 launch over an explicit frame matrix, every bias gradient a radmmm_colsum; these entry points are what
+ * surrounds them.  Geometry of one discriminator of period p on B items of T samples, real and generated stacked:
+ *   H = ceil(T / p) rows of the fold x[b][h][w] = audio[b][refl(h*p + w)], refl(t) = t < T ? t : 2(T-1) - t  (T > H*p - T);
+ *   S = 2*B*p sequences, s = (sig*B + b)*p + w, sig 0 real, 1 generated;
+ *   a conv of 5 taps, stride st, zero pad 2 maps H rows to Ho = (H-1)/st + 1 rows: out[h'] = sum_k W[k] . in[st*h' - 2 + k];
+ *   a PADDED map is [S][H + 4][C] floats, rows 2 .. H + 1 the map, the other four rows zero, C % 4 == 0: the window of
+ *   output row h' is the 5*C contiguous floats at padded row st*h';  a DENSE matrix is [S*H][C];  the discriminator
+ *   output is [2B][H][p], real half first (the reference's flatten: position h*p + w).
+ * `cnt` is an int32 device array [7][B] or NULL (everything counts): row l < 6 the rows of map l that count for item b
+ * (read clamped to [0, H_l]), row 6 the positions of the flattened output that count (clamped to [0, H_5 * p]).
+ * lrelu(v) = v > 0 ? v : slope * v; its derivative is taken from the saved OUTPUT y: y > 0 ? 1 : slope.
+ *   mpd_fold_frame       F[(s*H1 + h')*8 + k] = x_s[3h' - 2 + k] for k < 5 and the row inside [0, H), else 0 (k = 5 .. 7 pad
+ *                        the row to 8 floats).  A copy.  H1 = (H-1)/3 + 1.
+ *   mpd_repad            X[s][r][c] = lrelu(Z[(s*H + r - 2)*ldz + c]) for 2 <= r < H + 2, else 0.
+ *   mpd_frame            F[(s*Ho + h')*5C + j] = X[s][st*h'][j], j < 5C.  A copy.  st*(Ho-1) + 5 <= H + 4.
+ *   mpd_unframe          dZ[(s*H + h)*C + c] = (sum_h' dF[(s*Ho + h')*5C + (h + 2 - st*h')*C + c] + add[s][h + 2][c]) *
+ *                        lrelu'(X[s][h + 2][c]) over the windows 0 <= h' < Ho that hold row h, ascending; add (padded
+ *                        layout, its pad rows never read) may be NULL.
+ *   mpd_conv_post        out[(s2*H + h)*p + w] = bias[0] + sum_{k<3} sum_c X[s2*p + w][h + 1 + k][c] * W[k*C + c]  (3 taps,
+ *                        zero pad 1); one wave per output, lane l adds columns 4l .. 4l+3, 4l+256 .. per tap, then a xor butterfly.
+ *   mpd_conv_post_dgrad  dZ[(s*H + h)*C + c] = (sum_k dOut[s2][h + 1 - k][w] * W[k*C + c] + add[s][h + 2][c]) *
+ *                        lrelu'(X[s][h + 2][c]), rows outside [0, H) skipped.
+ *   mpd_conv_post_wgrad  part [mpd_conv_post_wgrad_parts][3C + 1]: per chunk of 64 rows (s, h), ascending,
+ *                        part[j][k*C + c] = sum dOut[s2][h][w] * X[s][h + 1 + k][c], part[j][3C] = sum dOut;
+ *                        radmmm_colsum_final(part, out, parts, 3C + 1) adds the chunks.
+ *   mpd_unfold_audio     g[b*ldg + t] = G(t) + (T <= 2(T-1) - t < H*p ? G(2(T-1) - t) : 0), G(u) = sum over the windows h'
+ *                        (ascending) that hold row u/p of dF[(s*H1 + h')*8 + u/p + 2 - 3h'], s = (sig*B + b)*p + u%p.
+ *   mpd_fm_terms         part [mpd_fm_terms_parts] partial sums of |r - g| over the elements (b, w, h < cnt[b], c) of one map
+ *                        (padded != 0: a padded map; 0: the dense output with C = 1); cnt is the map's own row [B].
+ *   mpd_finish           one workgroup, fp64.  part holds the six maps' partials, map l at [off[l], off[l+1]) (off, C, H are
+ *                        HOST arrays of 7, 6, 6 ints).  norm[l] = sum_b cnt[l][b] * C_l * p, norm[6] = sum_b cnt[6][b];
+ *                        res = (sum_l sum(part_l) / norm[l], sum m (1-dr)^2 / norm[6], sum m dg^2 / norm[6],
+ *                        sum m (1-dg)^2 / norm[6]), m = [h*p + w < cnt[6][b]].
+ *   mpd_fm_grad          G (padded, pad rows not written) = +-(up[0] / norm[0]) * sign(r - g) * [h < cnt[b]], + on the real
+ *                        half, sign(0) = 0; cnt and norm are the map's own.
+ *   mpd_out_grad         dOut real = -2 (1-dr) m up[1] / norm[6] + f, generated = (2 dg up[2] - 2 (1-dg) up[3]) m / norm[6] - f,
+ *                        f = up[0] / norm[5] * sign(dr - dg) * [h < cnt[5][b]]; up is a device array of 4 floats.
+ * No atomics, fixed reduction orders.
+ * ------------------------------------------------------------------------------------ */
+int radmmm_mpd_fold_frame(const float* y, const float* y_hat, int ldy, float* F, int B, int T, int p, int H, int H1,
+                          radmmm_stream_t stream);
+int radmmm_mpd_repad(const float* Z, int ldz, float* X, int S, int H, int C, float slope, radmmm_stream_t stream);
+int radmmm_mpd_frame(const float* X, float* F, int S, int H, int C, int Ho, int stride, radmmm_stream_t stream);
+int radmmm_mpd_unframe(const float* dF, const float* add, const float* X, float* dZ, int S, int H, int C, int Ho, int stride,
+                       float slope, radmmm_stream_t stream);
+int radmmm_mpd_conv_post(const float* X, const float* W, const float* bias, float* out, int B2, int p, int H, int C,
+                         radmmm_stream_t stream);
+int radmmm_mpd_conv_post_dgrad(const float* dOut, const float* W, const float* add, const float* X, float* dZ, int B2, int p,
+                               int H, int C, float slope, radmmm_stream_t stream);
+int64_t radmmm_mpd_conv_post_wgrad_parts(int B2, int p, int H);
+int radmmm_mpd_conv_post_wgrad(const float* dOut, const float* X, float* part, int B2, int p, int H, int C,
+                               radmmm_stream_t stream);
+int radmmm_mpd_unfold_audio(const float* dF, float* g, int ldg, int B, int T, int p, int H, int H1, int sig,
+                            radmmm_stream_t stream);
+int64_t radmmm_mpd_fm_terms_parts(int B, int p, int H, int C);
+int radmmm_mpd_fm_terms(const float* X, const int32_t* cnt, float* part, int B, int p, int H, int C, int padded,
+                        radmmm_stream_t stream);
+int radmmm_mpd_finish(const float* part, const int32_t* off, const int32_t* C, const int32_t* H, const float* out,
+                      const int32_t* cnt, float* res, double* norm, int B, int p, radmmm_stream_t stream);
+int radmmm_mpd_fm_grad(const float* X, const int32_t* cnt, const double* norm, const float* up, float* G, int B, int p, int H,
+                       int C, radmmm_stream_t stream);
+int radmmm_mpd_out_grad(const float* out, const int32_t* cnt, const double* norm, const float* up, float* dOut, int B, int p,
+                        int H, radmmm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

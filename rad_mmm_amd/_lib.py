@@ -277,6 +277,18 @@ def _load() -> C.CDLL:
         "radmmm_melloss_bwd": [p, i, p, p, p, i, p, p, p, p, i, i, i, i, i, f, p],
         "radmmm_melloss_dspec": [p, i, p, i, p, p, i, i, i, i, i, p],
         "radmmm_melloss_unframe": [p, p, p, i, i, i, i, i, i, i, p],
+        "radmmm_mpd_fold_frame": [p, p, i, p, i, i, i, i, i, p],
+        "radmmm_mpd_repad": [p, i, p, i, i, i, f, p],
+        "radmmm_mpd_frame": [p, p, i, i, i, i, i, p],
+        "radmmm_mpd_unframe": [p, p, p, p, i, i, i, i, i, f, p],
+        "radmmm_mpd_conv_post": [p, p, p, p, i, i, i, i, p],
+        "radmmm_mpd_conv_post_dgrad": [p, p, p, p, p, i, i, i, i, f, p],
+        "radmmm_mpd_conv_post_wgrad": [p, p, p, i, i, i, i, p],
+        "radmmm_mpd_unfold_audio": [p, p, i, i, i, i, i, i, i, p],
+        "radmmm_mpd_fm_terms": [p, p, p, i, i, i, i, i, p],
+        "radmmm_mpd_finish": [p, p, p, p, p, p, p, p, i, i, p],
+        "radmmm_mpd_fm_grad": [p, p, p, p, p, i, i, i, i, p],
+        "radmmm_mpd_out_grad": [p, p, p, p, p, i, i, i, p],
     }
     missing = [n for n in sig if not hasattr(lib, n)]
     if missing:
@@ -294,6 +306,7 @@ def _load() -> C.CDLL:
                        "radmmm_lstm_scratch_bytes": [i, i, i], "radmmm_lstm_hseq_bytes": [i, i, i],
                        "radmmm_wg_outer_reduce_scratch_floats": [i, i, i],
                        "radmmm_voc_conv_post_bwd_scratch_floats": [i, i, i, i],
+                       "radmmm_mpd_conv_post_wgrad_parts": [i, i, i], "radmmm_mpd_fm_terms_parts": [i, i, i, i],
                        "radmmm_sumsq_scratch_floats": []}.items():
         fn = getattr(lib, name)
         fn.argtypes = args

@@ -5,6 +5,7 @@
     python tools/vocoder_bench.py --train [--iters 5] [--warmup 2]
     python tools/vocoder_bench.py --stft-loss [--iters 5] [--warmup 2] [--out profiles/stft_loss.json]
     python tools/vocoder_bench.py --mel-loss [--iters 5] [--warmup 2] [--out profiles/mel_loss.json]
+    python tools/vocoder_bench.py --mpd [--iters 5] [--warmup 2] [--out profiles/mpd.json]
 
 Generator and denoiser ms per call at (B, T) = (32, 800) and (1, 800) for the V1 and V3 configs (random weights
 from a seed), the real-time factor (seconds of 22.05 kHz audio per second of compute), per-stage ms of the generator
@@ -34,7 +35,17 @@ it instead of its mirror image; and it takes sqrt(re^2 + im^2 + 1e-9), as upstre
 gradient of sqrt at the all-zero frames behind an item is NaN, which masking cannot remove.  Median of --iters runs after
 --warmup, device launches and host synchronisations of one step as for --stft-loss.  Then the V1 training step of --train
 with 45 * mel + sc + mag (HIP STFT loss in both) through the HIP mel loss and through the stock one.  The JSON also goes
-to --out."""
+to --out.
+
+--mpd: the multi-period discriminator and its GAN losses (rad_mmm_amd/discriminators.py, the reference's widths, ragged
+len_ratios on the device) at 16 x 8192 and 32 x 8192 samples, in one process: the D step (discriminator loss forward plus
+parameter gradients, y_hat detached) and the G side (feature + generator loss forward plus the gradient of y_hat, parameters
+frozen), through the HIP module, through the same discriminator written with torch.nn.functional.conv2d in fp32 under torch
+autograd (real and generated audio stacked in one pass, vectorised masks, no host read), and through the reference's form
+(one pass per signal, its mask builder's and gan_discriminator_loss's .item() calls).  Each stock step computes only the
+losses of that step: the D step the discriminator loss, the G side the feature and generator losses.  Per form and
+step: median ms of --iters runs after --warmup, device launches, host synchronisations, peak allocated memory.  The JSON
+also goes to --out (profiles/mpd.json)."""
 import argparse
 import json
 import os
@@ -388,6 +399,140 @@ def mel_loss_bench(args, dev):
     print(json.dumps(res))
 
 
+def stock_mpd(mpd, dev):
+    """the multi-period discriminator and its three losses with torch.nn.functional.conv2d in fp32 under torch autograd, on
+    the HIP module's own parameters -> {"vectorised": (d_loss, g_losses), "reference_form": (d_loss, g_losses)} with
+    d_loss(y, y_hat, ratios) -> the discriminator loss alone and g_losses(y, y_hat, ratios) -> (fm, gen) alone, so that each
+    step runs what that step needs and nothing else.  vectorised: real and generated audio stacked in one pass, masks from
+    the formula, nothing read back.  reference_form: one pass per signal as MultiPeriodDiscriminator.forward writes it, the
+    reference's mask builder with its .item() (get_mask_from_lengths) and gan_discriminator_loss's two .item() calls per
+    discriminator; gan_generator_loss and gan_feature_loss have none of their own."""
+    import torch.nn.functional as F
+    from rad_mmm_amd.vocoder import fold_weight_norm
+
+    def forward(x):
+        outs, fmaps = [], []
+        for d in mpd.discriminators:
+            p = d.period
+            h = x
+            if h.shape[2] % p:
+                h = F.pad(h, (0, p - h.shape[2] % p), "reflect")
+            h = h.view(h.shape[0], 1, h.shape[2] // p, p)
+            fm = []
+            for i, m in enumerate(d.convs):
+                h = F.leaky_relu(F.conv2d(h, fold_weight_norm(m.weight_v, m.weight_g), m.bias, (3 if i < 4 else 1, 1), (2, 0)), 0.1)
+                fm.append(h)
+            m = d.conv_post
+            h = F.conv2d(h, fold_weight_norm(m.weight_v, m.weight_g), m.bias, 1, (1, 0))
+            fm.append(h)
+            outs.append(h.flatten(1))
+            fmaps.append(fm)
+        return outs, fmaps
+
+    def both(y, y_hat, item):
+        if item:
+            return forward(y) + forward(y_hat)
+        B = y.shape[0]
+        outs, fmaps = forward(torch.cat([y, y_hat], 0))
+        return ([o[:B] for o in outs], [[m[:B] for m in fm] for fm in fmaps],
+                [o[B:] for o in outs], [[m[B:] for m in fm] for fm in fmaps])
+
+    def mask_of(ratios, size, item):
+        n = (ratios * size).ceil().long()
+        if item:
+            size = int(n.max().item())                        # get_mask_from_lengths of the reference
+        return (torch.arange(size, device=dev)[None, :] < n[:, None]).float()
+
+    def d_loss(y, y_hat, ratios, item):
+        rs, _, gs, _ = both(y, y_hat, item)
+        disc = 0.0
+        for dr, dg in zip(rs, gs):
+            m = mask_of(ratios, dr.shape[1], item)
+            r_loss, g_loss = (((1 - dr) ** 2) * m).sum() / m.sum(), ((dg ** 2) * m).sum() / m.sum()
+            if item:
+                r_loss.item(), g_loss.item()
+            disc = disc + r_loss + g_loss
+        return disc
+
+    def g_losses(y, y_hat, ratios, item):
+        _, frs, gs, fgs = both(y, y_hat, item)
+        fm = gen = 0.0
+        for dg, fr, fg in zip(gs, frs, fgs):
+            for r, g in zip(fr, fg):
+                m = mask_of(ratios, r.shape[2], item)[:, None, :, None]
+                fm = fm + ((r - g).abs() * m).sum() / (m.sum() * r.shape[1] * r.shape[3])
+            m = mask_of(ratios, dg.shape[1], item)
+            gen = gen + (((1 - dg) ** 2) * m).sum() / m.sum()
+        return fm, gen
+    return {"vectorised": (lambda y, yh, r: d_loss(y, yh, r, False), lambda y, yh, r: g_losses(y, yh, r, False)),
+            "reference_form": (lambda y, yh, r: d_loss(y, yh, r, True), lambda y, yh, r: g_losses(y, yh, r, True))}
+
+
+def mpd_bench(args, dev):
+    from rad_mmm_amd.discriminators import MultiPeriodDiscriminator
+    torch.manual_seed(3)
+    mpd = MultiPeriodDiscriminator().to(dev).train()
+    stock = stock_mpd(mpd, dev)
+    res = {"metric": "mpd_step_ms", "iters": args.iters, "warmup": args.warmup, "device": torch.cuda.get_device_name(0),
+           "note": "one GPU, one process, one session; fp32; ragged len_ratios on the device (the last item full); median of "
+                   "iters after warmup.  d_step: discriminator loss forward + parameter gradients, y_hat detached.  g_side: "
+                   "feature + generator loss forward + gradient of y_hat, parameters frozen.  torch_*: the same "
+                   "discriminator with torch.nn.functional.conv2d (MIOpen) under torch autograd, each step computing only "
+                   "the losses of that step; torch_vectorised stacks real and generated audio in one pass", "shapes": {}}
+    g = torch.Generator().manual_seed(13)
+    for B in (16, 32):
+        T = 8192
+        ratios = (torch.linspace(T // 3, T, B).round() / T).to(dev)
+        y = (torch.rand(B, 1, T, generator=g) * 2 - 1).to(dev)
+        y_hat = (y.cpu() + 0.3 * torch.randn(B, 1, T, generator=g)).clamp(-1, 1).to(dev)
+        row = {}
+        for key, fn in (("hip", None), ("torch_vectorised", stock["vectorised"]), ("torch_reference_form", stock["reference_form"])):
+            def d_step():
+                mpd.zero_grad(set_to_none=True)
+                loss = mpd.discriminator_loss(y, y_hat, ratios)[0] if fn is None else fn[0](y, y_hat, ratios)
+                loss.backward()
+                return loss.detach()
+
+            def g_side():
+                p = y_hat.detach().requires_grad_(True)
+                fm, gen = mpd.generator_losses(y, p, ratios) if fn is None else fn[1](y, p, ratios)
+                (fm + gen).backward()
+                return fm.detach(), gen.detach(), p.grad
+            out = {}
+            for name, step, frozen in (("d_step", d_step, False), ("g_side", g_side, True)):
+                for q in mpd.parameters():
+                    q.requires_grad_(not frozen)
+                ms = timed(step, args.iters, args.warmup)
+                launches, syncs = count_launches_and_syncs(step)
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                got = step()
+                torch.cuda.synchronize()
+                out[name] = {"ms": round(ms, 3), "launches": launches, "host_syncs": syncs,
+                             "peak_allocated_mb": round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)}
+                if name == "d_step":
+                    out[name]["loss"] = float(got)
+                else:
+                    out[name].update(fm=float(got[0]), gen=float(got[1]))
+                    out["_grad"] = got[2]
+            row[key] = out
+            torch.cuda.empty_cache()
+        for key in ("torch_vectorised", "torch_reference_form"):
+            for name in ("d_step", "g_side"):
+                row[key][name]["over_hip"] = round(row[key][name]["ms"] / row["hip"][name]["ms"], 3)
+            row[key]["g_side"]["grad_rel_l2_vs_hip"] = float((row[key]["_grad"] - row["hip"]["_grad"]).norm() / row["hip"]["_grad"].norm())
+        for key in row:
+            del row[key]["_grad"]
+        res["shapes"][f"B{B}_T{T}"] = row
+        print(json.dumps({f"B{B}_T{T}": row}), file=sys.stderr, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
@@ -396,11 +541,13 @@ def main():
     ap.add_argument("--train", action="store_true", help="time one V1 training step against stock torch autograd")
     ap.add_argument("--stft-loss", action="store_true", help="time the multi-resolution STFT loss against stock torch")
     ap.add_argument("--mel-loss", action="store_true", help="time the mel L1 loss against stock torch")
-    ap.add_argument("--out", default=None, help="--stft-loss / --mel-loss: result file (default profiles/stft_loss.json / "
-                                                "profiles/mel_loss.json)")
+    ap.add_argument("--mpd", action="store_true", help="time the multi-period discriminator's D step and G side against "
+                                                       "stock torch")
+    ap.add_argument("--out", default=None, help="--stft-loss / --mel-loss / --mpd: result file (default "
+                                                "profiles/stft_loss.json / profiles/mel_loss.json / profiles/mpd.json)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "mel_loss.json" if args.mel_loss else "stft_loss.json")
+        args.out = os.path.join(ROOT, "profiles", "mpd.json" if args.mpd else "mel_loss.json" if args.mel_loss else "stft_loss.json")
     dev = torch.device("cuda:0")
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
@@ -410,6 +557,8 @@ def main():
         return stft_loss_bench(args, dev)
     if args.mel_loss:
         return mel_loss_bench(args, dev)
+    if args.mpd:
+        return mpd_bench(args, dev)
     res = {"metric": "vocoder_ms", "configs": {}}
     for name, cfg in (("V1", V1), ("V3", V3)):
         gen = HiFiGANGenerator(cfg)

@@ -1180,6 +1180,68 @@ int radmmm_mpd_fm_grad(const float* X, const int32_t* cnt, const double* norm, c
 int radmmm_mpd_out_grad(const float* out, const int32_t* cnt, const double* norm, const float* up, float* dOut, int B, int p,
                         int H, radmmm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Grouped strided 1-d convolution on the fp32 matrix cores, forward and backward (additive entry points of ABI 4): the
+ * kernel family of the HiFi-GAN multi-scale discriminator's five grouped 41-tap layers (hifigan_models.py: DiscriminatorS).
+ * Geometry: S sequences, G groups, C_in = G*Cin_g, C_out = G*Cout_g, k taps (odd, <= 41), stride st in {1, 2, 4}, zero pad
+ * k/2, Hout = (Hin-1)/st + 1; Cin_g and Cout_g multiples of 4 in [4, 64].  Anything else returns -1 before any HIP call.
+ *   a PADDED map is [S][pad + H + pad][C] floats, the 2*pad outer rows of every sequence zero; X is padded by k/2, so
+ *   window h' of group g is rows st*h' .. st*h' + k - 1, columns g*Cin_g .. (g+1)*Cin_g of X;  a DENSE matrix is [S*H][C];
+ *   W is packed [G][Cout_g][k*Cin_g], kk = tap*Cin_g + ci  (torch's [C_out, Cin_g, k] permuted to [C_out, k, Cin_g]).
+ * lrelu(v) = v > 0 ? v : slope*v; its derivative is taken from the saved OUTPUT y: y > 0 ? 1 : slope.
+ *   msd_gconv_fwd    Y[s][pad_out + h'][g*Cout_g + co] = lrelu(bias[g*Cout_g + co] + sum_kk X[s][st*h' + tap][g*Cin_g + ci] *
+ *                    W[g][co][kk]); Y is padded by pad_out (0 .. 20: the NEXT conv's k/2) and its pad rows are written as
+ *                    zeros.  One launch covers all groups; no frame matrix is written.  slope 1 leaves the sum as it is.
+ *   msd_gconv_dgrad  dX[(s*Hin + h)*C_in + g*Cin_g + ci] = (sum over the windows h' (ascending) and taps with st*h' + tap =
+ *                    h + k/2 of sum_co dY[(s*Hout + h')*C_out + g*Cout_g + co] * W[g][co][tap*Cin_g + ci]
+ *                    + add[s][h + k/2][..]) * lrelu'(X[s][h + k/2][..]).  dY, dX dense; add (X's padded layout, its pad
+ *                    rows never read) may be NULL; X is the saved padded input map.
+ *   msd_gconv_wgrad  P[split][g][co][tap*Cin_g + ci] = sum over the split's (s, h'), ascending, of
+ *                    dZ[(s*Hout + h')*C_out + g*Cout_g + co] * X[s][st*h' + tap][g*Cin_g + ci].  The rows are cut into units
+ *                    of 32 windows of one sequence; split i of n = msd_gconv_wgrad_splits(S, Hout, G, k) takes units
+ *                    [i*U/n, (i+1)*U/n).  radmmm_colsum_final(P, dW, n, G*Cout_g*k*Cin_g) adds the splits.
+ * Every contraction is a fixed chain of v_mfma_f32_16x16x4_f32; no atomics: equal inputs give equal bits.
+ * ------------------------------------------------------------------------------------ */
+int radmmm_msd_gconv_fwd(const float* X, const float* W, const float* bias, float* Y, int S, int Hin, int Hout, int G, int Cin_g,
+                         int Cout_g, int k, int stride, int pad_out, float slope, radmmm_stream_t stream);
+int radmmm_msd_gconv_dgrad(const float* dY, const float* W, const float* add, const float* X, float* dX, int S, int Hin, int Hout,
+                           int G, int Cin_g, int Cout_g, int k, int stride, float slope, radmmm_stream_t stream);
+int64_t radmmm_msd_gconv_wgrad_splits(int S, int Hout, int G, int k);
+int radmmm_msd_gconv_wgrad(const float* dZ, const float* X, float* P, int S, int Hin, int Hout, int G, int Cin_g, int Cout_g,
+                           int k, int stride, radmmm_stream_t stream);
+
+/* What surrounds the grouped convolutions in the multi-scale discriminator (hifigan_models.py: DiscriminatorS,
+ * MultiScaleDiscriminator).  One member sees S = 2B sequences, s = sig*B + b, sig 0 real, 1 generated; its dense 5-tap and
+ * conv_post layers are the multi-period entry points with p = 1 on maps padded by 2.
+ *   msd_avgpool     AvgPool1d(4, 2, padding 2), count_include_pad: out[(sig*B + b)*To + j] = (x[2j-2] + x[2j-1] + x[2j] +
+ *                   x[2j+1]) / 4 with x = 0 outside [0, T), To = T/2 + 1; both signals in one launch.
+ *   msd_avgpool_bwd its adjoint in gather form: gx[n*ldx + t] = (g[n*To + t/2] + g[n*To + t/2 + 1]) / 4, the second term
+ *                   only when t/2 + 1 < To; N rows.
+ *   msd_frame15     the first conv's frame matrix: F[(s*T + t)*16 + j] = x_s[t - 7 + j] for j < 15 inside [0, T), else 0
+ *                   (15 taps, zero pad 7, stride 1; column 15 pads the row to 16 floats).  A copy.
+ *   msd_unframe15   its adjoint: g[n*ldg + u] = sum over j = 14 .. 0 with 0 <= u + 7 - j < T of dF[(n*T + u + 7 - j)*16 + j].
+ *   msd_repad       X[s][r][c] = lrelu(Z[(s*H + r - pad)*ldz + c]) for pad <= r < pad + H, else 0  (mpd_repad with a pad
+ *                   parameter, 0 .. 20).
+ *   msd_fm_terms    mpd_fm_terms with p = 1 on a map [2B][pad + H + pad][C] (pad >= 0) or the dense output [2B][H] (pad < 0,
+ *                   C == 1); partial count: mpd_fm_terms_parts(B, 1, H, C).
+ *   msd_finish      mpd_finish with EIGHT maps (the seven convs and conv_post): off host [9], C and H host [8], cnt [9][B] (row
+ *                   8 the output's positions), norm [9].
+ *   msd_fm_grad     mpd_fm_grad with p = 1 and a pad parameter.
+ *   msd_out_grad    mpd_out_grad with p = 1 in the eight-map form: f uses norm[7] and cnt[7], the adversarial terms norm[8]
+ *                   and cnt[8]. */
+int radmmm_msd_avgpool(const float* y, const float* y_hat, int ldy, float* out, int B, int T, radmmm_stream_t stream);
+int radmmm_msd_avgpool_bwd(const float* g, float* gx, int ldx, int N, int T, radmmm_stream_t stream);
+int radmmm_msd_frame15(const float* y, const float* y_hat, int ldy, float* F, int B, int T, radmmm_stream_t stream);
+int radmmm_msd_unframe15(const float* dF, float* g, int ldg, int N, int T, radmmm_stream_t stream);
+int radmmm_msd_repad(const float* Z, int ldz, float* X, int S, int H, int C, int pad, float slope, radmmm_stream_t stream);
+int radmmm_msd_fm_terms(const float* X, const int32_t* cnt, float* part, int B, int H, int C, int pad, radmmm_stream_t stream);
+int radmmm_msd_finish(const float* part, const int32_t* off, const int32_t* C, const int32_t* H, const float* out,
+                      const int32_t* cnt, float* res, double* norm, int B, radmmm_stream_t stream);
+int radmmm_msd_fm_grad(const float* X, const int32_t* cnt, const double* norm, const float* up, float* G, int B, int H, int C,
+                       int pad, radmmm_stream_t stream);
+int radmmm_msd_out_grad(const float* out, const int32_t* cnt, const double* norm, const float* up, float* dOut, int B, int H,
+                        radmmm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -289,6 +289,18 @@ def _load() -> C.CDLL:
         "radmmm_mpd_finish": [p, p, p, p, p, p, p, p, i, i, p],
         "radmmm_mpd_fm_grad": [p, p, p, p, p, i, i, i, i, p],
         "radmmm_mpd_out_grad": [p, p, p, p, p, i, i, i, p],
+        "radmmm_msd_gconv_fwd": [p, p, p, p, i, i, i, i, i, i, i, i, i, f, p],
+        "radmmm_msd_gconv_dgrad": [p, p, p, p, p, i, i, i, i, i, i, i, i, f, p],
+        "radmmm_msd_gconv_wgrad": [p, p, p, i, i, i, i, i, i, i, i, p],
+        "radmmm_msd_avgpool": [p, p, i, p, i, i, p],
+        "radmmm_msd_avgpool_bwd": [p, p, i, i, i, p],
+        "radmmm_msd_frame15": [p, p, i, p, i, i, p],
+        "radmmm_msd_unframe15": [p, p, i, i, i, p],
+        "radmmm_msd_repad": [p, i, p, i, i, i, i, f, p],
+        "radmmm_msd_fm_terms": [p, p, p, i, i, i, i, p],
+        "radmmm_msd_finish": [p, p, p, p, p, p, p, p, i, p],
+        "radmmm_msd_fm_grad": [p, p, p, p, p, i, i, i, i, p],
+        "radmmm_msd_out_grad": [p, p, p, p, p, i, i, p],
     }
     missing = [n for n in sig if not hasattr(lib, n)]
     if missing:
@@ -307,6 +319,7 @@ def _load() -> C.CDLL:
                        "radmmm_wg_outer_reduce_scratch_floats": [i, i, i],
                        "radmmm_voc_conv_post_bwd_scratch_floats": [i, i, i, i],
                        "radmmm_mpd_conv_post_wgrad_parts": [i, i, i], "radmmm_mpd_fm_terms_parts": [i, i, i, i],
+                       "radmmm_msd_gconv_wgrad_splits": [i, i, i, i],
                        "radmmm_sumsq_scratch_floats": []}.items():
         fn = getattr(lib, name)
         fn.argtypes = args

@@ -21,6 +21,8 @@
 //   radmmm_mpd_finish           partial sums + outputs -> the four loss terms and the normalisers, one workgroup, fp64
 //   radmmm_mpd_fm_grad          gradient of the feature loss on one padded map
 //   radmmm_mpd_out_grad         gradient of the adversarial terms (+ the feature loss) on the discriminator output
+// The four loss kernels also serve the multi-scale discriminator (radmmm_msd_fm_terms / _finish / _fm_grad / _out_grad, DESIGN
+// 4.23): the same kernels with p = 1, a pad parameter in place of the fixed 2 and eight maps in place of six.
 // Every reduction has a fixed order and there are no atomics: equal inputs give equal bits.
 #include "common.h"
 
@@ -31,6 +33,7 @@ inline hipStream_t ST(radmmm_stream_t s) { return static_cast<hipStream_t>(s); }
 constexpr int kTermsMaxBlocks = 1024;
 constexpr int kFinishThreads = 1024;
 constexpr int kPostRows = 64;   // rows per partial of conv_post_wgrad
+constexpr int kMaxMaps = 8;     // maps of one discriminator, the output included
 
 inline int grid_for(long long total, int block, int cap = 8192) {
   long long g = (total + block - 1) / block;
@@ -316,12 +319,13 @@ __global__ void __launch_bounds__(256) fm_grad_kernel(const float* __restrict__ 
 
 struct FinishArgs {
   const float* part;   // the maps' partial sums, map l at [off[l], off[l + 1])
-  int off[7];
-  int C[6];            // channels of the maps (the last is conv_post's: 1)
-  int H[6];            // rows of the maps
-  const float* out;    // [2B][H5][p]
-  const int32_t* cnt;  // [7][B] or NULL: rows 0 .. 5 the maps' row counts, row 6 the output's count of flattened positions
+  int off[kMaxMaps + 1];
+  int C[kMaxMaps];     // channels of the maps (the last is conv_post's: 1)
+  int H[kMaxMaps];     // rows of the maps
+  const float* out;    // [2B][H_post][p]
+  const int32_t* cnt;  // [n + 1][B] or NULL: rows 0 .. n - 1 the maps' row counts, row n the output's count of flattened positions
   int B, p;
+  int n;               // maps: 6 (multi-period), 8 (multi-scale)
 };
 
 __device__ __forceinline__ double block_sum_f64(double v, double* sh) {
@@ -335,12 +339,13 @@ __device__ __forceinline__ double block_sum_f64(double v, double* sh) {
   return sh[0];
 }
 
-// res = (fm, mean (1 - dr)^2, mean dg^2, mean (1 - dg)^2), norm[l] = sum_b cnt[l][b] * C_l * p (l < 6), norm[6] = sum_b cnt[6][b]
+// res = (fm, mean (1 - dr)^2, mean dg^2, mean (1 - dg)^2), norm[l] = sum_b cnt[l][b] * C_l * p (l < n), norm[n] = sum_b cnt[n][b]
 __global__ void __launch_bounds__(kFinishThreads) finish_kernel(FinishArgs a, float* __restrict__ res, double* __restrict__ norm) {
   __shared__ double sh[kFinishThreads];
-  const int H5 = a.H[5], n = H5 * a.p;
+  const int H5 = a.H[a.n - 1], n = H5 * a.p;
+  const int32_t* cnt_out = a.cnt ? a.cnt + a.n * a.B : nullptr;
   double fm = 0.0;
-  for (int l = 0; l < 6; ++l) {
+  for (int l = 0; l < a.n; ++l) {
     double s = 0.0, c = 0.0;
     for (int i = a.off[l] + threadIdx.x; i < a.off[l + 1]; i += kFinishThreads) s += (double)a.part[i];
     for (int b = threadIdx.x; b < a.B; b += kFinishThreads) c += (double)clamp_count(a.cnt ? a.cnt + l * a.B : nullptr, b, a.H[l]);
@@ -353,19 +358,19 @@ __global__ void __launch_bounds__(kFinishThreads) finish_kernel(FinishArgs a, fl
   const long long total = (long long)a.B * n;
   for (long long i = threadIdx.x; i < total; i += kFinishThreads) {
     const int b = (int)(i / n), f = (int)(i - (long long)b * n);
-    if (f >= clamp_count(a.cnt ? a.cnt + 6 * a.B : nullptr, b, n)) continue;
+    if (f >= clamp_count(cnt_out, b, n)) continue;
     const double dr = (double)a.out[i], dg = (double)a.out[total + i];
     r1 += (1.0 - dr) * (1.0 - dr);
     g0 += dg * dg;
     g1 += (1.0 - dg) * (1.0 - dg);
   }
-  for (int b = threadIdx.x; b < a.B; b += kFinishThreads) c += (double)clamp_count(a.cnt ? a.cnt + 6 * a.B : nullptr, b, n);
+  for (int b = threadIdx.x; b < a.B; b += kFinishThreads) c += (double)clamp_count(cnt_out, b, n);
   r1 = block_sum_f64(r1, sh);
   g0 = block_sum_f64(g0, sh);
   g1 = block_sum_f64(g1, sh);
   c = block_sum_f64(c, sh);
   if (threadIdx.x == 0) {
-    norm[6] = c;
+    norm[a.n] = c;
     res[0] = (float)fm;
     res[1] = (float)(r1 / c);
     res[2] = (float)(g0 / c);
@@ -374,21 +379,21 @@ __global__ void __launch_bounds__(kFinishThreads) finish_kernel(FinishArgs a, fl
 }
 
 // dOut[sig][b][h][w]:  real = -2 (1 - dr) mf / n * up[1] + cf ;  generated = (2 dg up[2] - 2 (1 - dg) up[3]) mf / n - cf
-// mf = [h p + w < cnt[6][b]], n = norm[6], cf = up[0] / norm[5] * sign(dr - dg) * [h < cnt[5][b]]
+// mf = [h p + w < cnt[nm][b]], n = norm[nm], cf = up[0] / norm[nm - 1] * sign(dr - dg) * [h < cnt[nm - 1][b]]; nm maps (6 or 8)
 __global__ void __launch_bounds__(256) out_grad_kernel(const float* __restrict__ out, const int32_t* __restrict__ cnt,
                                                        const double* __restrict__ norm, const float* __restrict__ up,
-                                                       float* __restrict__ dOut, int B, int p, int H) {
+                                                       float* __restrict__ dOut, int B, int p, int H, int nm) {
   const int n = H * p;
   const long long total = (long long)B * n;
-  const float cfm = (float)((double)up[0] / norm[5]);
-  const double inv = 1.0 / norm[6];
+  const float cfm = (float)((double)up[0] / norm[nm - 1]);
+  const double inv = 1.0 / norm[nm];
   const float cr = (float)(-2.0 * (double)up[1] * inv), cg0 = (float)(2.0 * (double)up[2] * inv),
               cg1 = (float)(-2.0 * (double)up[3] * inv);
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int b = (int)(i / n), f = (int)(i - (long long)b * n);
     const float dr = out[i], dg = out[total + i];
-    const bool mf = f < clamp_count(cnt ? cnt + 6 * B : nullptr, b, n);
-    const bool mh = f / p < clamp_count(cnt ? cnt + 5 * B : nullptr, b, H);
+    const bool mf = f < clamp_count(cnt ? cnt + nm * B : nullptr, b, n);
+    const bool mh = f / p < clamp_count(cnt ? cnt + (nm - 1) * B : nullptr, b, H);
     const float cf = mh ? cfm * sign_of(dr - dg) : 0.f;
     dOut[i] = (mf ? cr * (1.f - dr) : 0.f) + cf;
     dOut[total + i] = (mf ? cg0 * dg + cg1 * (1.f - dg) : 0.f) - cf;
@@ -501,13 +506,14 @@ extern "C" int radmmm_mpd_unfold_audio(const float* dF, float* g, int ldg, int B
   return radmmm::check_launch("mpd_unfold_audio");
 }
 
-static int map_view(const char* who, int B, int p, int H, int C, int padded, MapView* v) {
+static int map_view(const char* who, int B, int p, int H, int C, int padded, int pad, MapView* v) {
   RADMMM_REQUIRE(B > 0 && p > 0 && H > 0 && C > 0, "%s: bad dims (B=%d p=%d H=%d C=%d)", who, B, p, H, C);
   RADMMM_REQUIRE(padded ? C % 4 == 0 : C == 1, "%s: a padded map needs C %% 4 == 0, the dense output C == 1 (C=%d)", who, C);
-  RADMMM_REQUIRE(2LL * B * p * (H + 4) * C * 4 < 0x7fffffffLL, "%s: the map exceeds 2 GiB", who);
+  RADMMM_REQUIRE(pad >= 0 && pad <= 20, "%s: pad must lie in [0, 20] (pad=%d)", who, pad);
+  RADMMM_REQUIRE(2LL * B * p * (H + 2 * pad) * C * 4 < 0x7fffffffLL, "%s: the map exceeds 2 GiB", who);
   v->B = B; v->p = p; v->H = H; v->C = C;
   if (padded) {
-    v->sh = C; v->sw = (long long)(H + 4) * C; v->sb = v->sw * p; v->ssig = v->sb * B;
+    v->sh = C; v->sw = (long long)(H + 2 * pad) * C; v->sb = v->sw * p; v->ssig = v->sb * B;
   } else {
     v->sh = p; v->sw = 1; v->sb = (long long)H * p; v->ssig = v->sb * B;
   }
@@ -519,44 +525,76 @@ extern "C" int64_t radmmm_mpd_fm_terms_parts(int B, int p, int H, int C) {
   return grid_for((long long)B * p * H * (C / V), 256, kTermsMaxBlocks);
 }
 
+static int fm_terms(const char* who, const float* X, const int32_t* cnt, float* part, int B, int p, int H, int C, int padded,
+                    int pad, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(X && part, "%s: null pointer", who);
+  MapView v;
+  if (int rc = map_view(who, B, p, H, C, padded, pad, &v)) return rc;
+  RADMMM_REQUIRE(!padded || radmmm::aligned16(X), "%s: 16B alignment", who);
+  hipLaunchKernelGGL(fm_terms_kernel, dim3((unsigned)radmmm_mpd_fm_terms_parts(B, p, H, C)), dim3(256), 0, ST(stream),
+                     padded ? X + pad * C : X, v, cnt, part);
+  return radmmm::check_launch(who);
+}
+
 extern "C" int radmmm_mpd_fm_terms(const float* X, const int32_t* cnt, float* part, int B, int p, int H, int C, int padded,
                                    radmmm_stream_t stream) {
-  RADMMM_REQUIRE(X && part, "mpd_fm_terms: null pointer");
-  MapView v;
-  if (int rc = map_view("mpd_fm_terms", B, p, H, C, padded, &v)) return rc;
-  RADMMM_REQUIRE(!padded || radmmm::aligned16(X), "mpd_fm_terms: 16B alignment");
-  hipLaunchKernelGGL(fm_terms_kernel, dim3((unsigned)radmmm_mpd_fm_terms_parts(B, p, H, C)), dim3(256), 0, ST(stream),
-                     padded ? X + 2 * C : X, v, cnt, part);
-  return radmmm::check_launch("mpd_fm_terms");
+  return fm_terms("mpd_fm_terms", X, cnt, part, B, p, H, C, padded, 2, stream);
+}
+
+// pad >= 0: a map [2B][pad + H + pad][C]; pad < 0: the dense output [2B][H] (C == 1)
+extern "C" int radmmm_msd_fm_terms(const float* X, const int32_t* cnt, float* part, int B, int H, int C, int pad,
+                                   radmmm_stream_t stream) {
+  return fm_terms("msd_fm_terms", X, cnt, part, B, 1, H, C, pad >= 0, pad >= 0 ? pad : 0, stream);
+}
+
+static int finish(const char* who, int n, const float* part, const int32_t* off, const int32_t* C, const int32_t* H, const float* out,
+                  const int32_t* cnt, float* res, double* norm, int B, int p, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(part && off && C && H && out && res && norm, "%s: null pointer", who);
+  RADMMM_REQUIRE(B > 0 && p > 0, "%s: bad dims (B=%d p=%d)", who, B, p);
+  RADMMM_REQUIRE((reinterpret_cast<uintptr_t>(norm) & 7) == 0, "%s: norm must be 8B aligned", who);
+  FinishArgs a = {};
+  a.part = part; a.out = out; a.cnt = cnt; a.B = B; a.p = p; a.n = n;
+  for (int l = 0; l <= n; ++l) a.off[l] = off[l];
+  for (int l = 0; l < n; ++l) {
+    RADMMM_REQUIRE(C[l] > 0 && H[l] > 0 && off[l + 1] >= off[l] && off[l] >= 0, "%s: bad map %d", who, l);
+    a.C[l] = C[l];
+    a.H[l] = H[l];
+  }
+  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(kFinishThreads), 0, ST(stream), a, res, norm);
+  return radmmm::check_launch(who);
 }
 
 extern "C" int radmmm_mpd_finish(const float* part, const int32_t* off /* host [7] */, const int32_t* C /* host [6] */,
                                  const int32_t* H /* host [6] */, const float* out, const int32_t* cnt, float* res, double* norm,
                                  int B, int p, radmmm_stream_t stream) {
-  RADMMM_REQUIRE(part && off && C && H && out && res && norm, "mpd_finish: null pointer");
-  RADMMM_REQUIRE(B > 0 && p > 0, "mpd_finish: bad dims (B=%d p=%d)", B, p);
-  RADMMM_REQUIRE((reinterpret_cast<uintptr_t>(norm) & 7) == 0, "mpd_finish: norm must be 8B aligned");
-  FinishArgs a;
-  a.part = part; a.out = out; a.cnt = cnt; a.B = B; a.p = p;
-  for (int l = 0; l < 7; ++l) a.off[l] = off[l];
-  for (int l = 0; l < 6; ++l) {
-    RADMMM_REQUIRE(C[l] > 0 && H[l] > 0 && off[l + 1] >= off[l] && off[l] >= 0, "mpd_finish: bad map %d", l);
-    a.C[l] = C[l];
-    a.H[l] = H[l];
-  }
-  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(kFinishThreads), 0, ST(stream), a, res, norm);
-  return radmmm::check_launch("mpd_finish");
+  return finish("mpd_finish", 6, part, off, C, H, out, cnt, res, norm, B, p, stream);
+}
+
+// eight maps (the seven convs and conv_post): off host [9], C and H host [8], cnt [9][B], norm [9]
+extern "C" int radmmm_msd_finish(const float* part, const int32_t* off, const int32_t* C, const int32_t* H, const float* out,
+                                 const int32_t* cnt, float* res, double* norm, int B, radmmm_stream_t stream) {
+  return finish("msd_finish", 8, part, off, C, H, out, cnt, res, norm, B, 1, stream);
+}
+
+static int fm_grad(const char* who, const float* X, const int32_t* cnt, const double* norm, const float* up, float* G, int B, int p,
+                   int H, int C, int pad, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(X && norm && up && G, "%s: null pointer", who);
+  MapView v;
+  if (int rc = map_view(who, B, p, H, C, 1, pad, &v)) return rc;
+  RADMMM_REQUIRE(radmmm::aligned16(X) && radmmm::aligned16(G), "%s: 16B alignment", who);
+  hipLaunchKernelGGL(fm_grad_kernel, dim3(grid_for((long long)B * p * H * (C / 4), 256)), dim3(256), 0, ST(stream), X + pad * C, v,
+                     cnt, norm, up, G + pad * C);
+  return radmmm::check_launch(who);
 }
 
 extern "C" int radmmm_mpd_fm_grad(const float* X, const int32_t* cnt, const double* norm, const float* up, float* G, int B, int p,
                                   int H, int C, radmmm_stream_t stream) {
-  RADMMM_REQUIRE(X && norm && up && G, "mpd_fm_grad: null pointer");
-  MapView v;
-  if (int rc = map_view("mpd_fm_grad", B, p, H, C, 1, &v)) return rc;
-  RADMMM_REQUIRE(radmmm::aligned16(X) && radmmm::aligned16(G), "mpd_fm_grad: 16B alignment");
-  hipLaunchKernelGGL(fm_grad_kernel, dim3(grid_for((long long)B * p * H * (C / 4), 256)), dim3(256), 0, ST(stream), X + 2 * C, v, cnt,
-                     norm, up, G + 2 * C);
-  return radmmm::check_launch("mpd_fm_grad");
+  return fm_grad("mpd_fm_grad", X, cnt, norm, up, G, B, p, H, C, 2, stream);
+}
+
+extern "C" int radmmm_msd_fm_grad(const float* X, const int32_t* cnt, const double* norm, const float* up, float* G, int B, int H,
+                                  int C, int pad, radmmm_stream_t stream) {
+  return fm_grad("msd_fm_grad", X, cnt, norm, up, G, B, 1, H, C, pad, stream);
 }
 
 extern "C" int radmmm_mpd_out_grad(const float* out, const int32_t* cnt, const double* norm, const float* up, float* dOut, int B,
@@ -564,6 +602,16 @@ extern "C" int radmmm_mpd_out_grad(const float* out, const int32_t* cnt, const d
   RADMMM_REQUIRE(out && norm && up && dOut, "mpd_out_grad: null pointer");
   RADMMM_REQUIRE(B > 0 && p > 0 && H > 0, "mpd_out_grad: bad dims (B=%d p=%d H=%d)", B, p, H);
   hipLaunchKernelGGL(out_grad_kernel, dim3(grid_for((long long)B * H * p, 256)), dim3(256), 0, ST(stream), out, cnt, norm, up, dOut,
-                     B, p, H);
+                     B, p, H, 6);
   return radmmm::check_launch("mpd_out_grad");
+}
+
+// the eight-map form: cnt [9][B], norm [9]
+extern "C" int radmmm_msd_out_grad(const float* out, const int32_t* cnt, const double* norm, const float* up, float* dOut, int B,
+                                   int H, radmmm_stream_t stream) {
+  RADMMM_REQUIRE(out && norm && up && dOut, "msd_out_grad: null pointer");
+  RADMMM_REQUIRE(B > 0 && H > 0, "msd_out_grad: bad dims (B=%d H=%d)", B, H);
+  hipLaunchKernelGGL(out_grad_kernel, dim3(grid_for((long long)B * H, 256)), dim3(256), 0, ST(stream), out, cnt, norm, up, dOut, B,
+                     1, H, 8);
+  return radmmm::check_launch("msd_out_grad");
 }

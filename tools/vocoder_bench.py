@@ -6,6 +6,7 @@
     python tools/vocoder_bench.py --stft-loss [--iters 5] [--warmup 2] [--out profiles/stft_loss.json]
     python tools/vocoder_bench.py --mel-loss [--iters 5] [--warmup 2] [--out profiles/mel_loss.json]
     python tools/vocoder_bench.py --mpd [--iters 5] [--warmup 2] [--out profiles/mpd.json]
+    python tools/vocoder_bench.py --msd [--iters 5] [--warmup 2] [--out profiles/msd.json]
 
 Generator and denoiser ms per call at (B, T) = (32, 800) and (1, 800) for the V1 and V3 configs (random weights
 from a seed), the real-time factor (seconds of 22.05 kHz audio per second of compute), per-stage ms of the generator
@@ -45,7 +46,11 @@ autograd (real and generated audio stacked in one pass, vectorised masks, no hos
 (one pass per signal, its mask builder's and gan_discriminator_loss's .item() calls).  Each stock step computes only the
 losses of that step: the D step the discriminator loss, the G side the feature and generator losses.  Per form and
 step: median ms of --iters runs after --warmup, device launches, host synchronisations, peak allocated memory.  The JSON
-also goes to --out (profiles/mpd.json)."""
+also goes to --out (profiles/mpd.json).
+
+--msd: the same for the multi-scale discriminator (the reference's widths and groups, training mode) against stock torch
+with conv1d(groups=), to profiles/msd.json; --msd --d-step-only runs the module's D step at 32 x 8192 alone, the workload
+of the kernel trace kept as profiles/msd_d_step_kernel_stats.csv."""
 import argparse
 import json
 import os
@@ -468,17 +473,98 @@ def stock_mpd(mpd, dev):
             "reference_form": (lambda y, yh, r: d_loss(y, yh, r, True), lambda y, yh, r: g_losses(y, yh, r, True))}
 
 
+def stock_msd(msd, dev):
+    """the multi-scale discriminator and its three losses with torch.nn.functional.conv1d(groups=) in fp32 under torch
+    autograd, on the HIP module's own parameters, in stock_mpd's two forms.  Both fold weight norm and spectral norm with the
+    module's torch ops (a training-mode call of the spectral-norm member advances its power iteration, once per signal, as
+    in the reference).  vectorised: the weight-normed members see real and generated audio stacked in one pass; the
+    spectral-norm member has one weight set per signal in training mode and runs them apart."""
+    import torch.nn.functional as F
+    from rad_mmm_amd.discriminators import MSD_KERNELS, MSD_STRIDES
+
+    def member(d, x):
+        ws = d._weights()
+        fm = []
+        for l in range(7):
+            x = F.leaky_relu(F.conv1d(x, ws[2 * l], ws[2 * l + 1], MSD_STRIDES[l], MSD_KERNELS[l] // 2, 1, d.groups[l]), 0.1)
+            fm.append(x)
+        x = F.conv1d(x, ws[14], ws[15], 1, 1)
+        fm.append(x)
+        return x.flatten(1), fm
+
+    def both(y, y_hat, item):
+        rs, frs, gs, fgs = [], [], [], []
+        for i, d in enumerate(msd.discriminators):
+            if i:
+                y, y_hat = F.avg_pool1d(y, 4, 2, 2), F.avg_pool1d(y_hat, 4, 2, 2)
+            if item or (d.use_spectral_norm and d.training):
+                (r, fr), (g, fg) = member(d, y), member(d, y_hat)
+            else:
+                B = y.shape[0]
+                o, fm = member(d, torch.cat([y, y_hat], 0))
+                r, fr, g, fg = o[:B], [m[:B] for m in fm], o[B:], [m[B:] for m in fm]
+            rs.append(r), frs.append(fr), gs.append(g), fgs.append(fg)
+        return rs, frs, gs, fgs
+
+    def mask_of(ratios, size, item):
+        n = (ratios * size).ceil().long()
+        if item:
+            size = int(n.max().item())                        # get_mask_from_lengths of the reference
+        return (torch.arange(size, device=dev)[None, :] < n[:, None]).float()
+
+    def d_loss(y, y_hat, ratios, item):
+        rs, _, gs, _ = both(y, y_hat, item)
+        disc = 0.0
+        for dr, dg in zip(rs, gs):
+            m = mask_of(ratios, dr.shape[1], item)
+            r_loss, g_loss = (((1 - dr) ** 2) * m).sum() / m.sum(), ((dg ** 2) * m).sum() / m.sum()
+            if item:
+                r_loss.item(), g_loss.item()
+            disc = disc + r_loss + g_loss
+        return disc
+
+    def g_losses(y, y_hat, ratios, item):
+        _, frs, gs, fgs = both(y, y_hat, item)
+        fm = gen = 0.0
+        for dg, fr, fg in zip(gs, frs, fgs):
+            for r, g in zip(fr, fg):
+                m = mask_of(ratios, r.shape[2], item)[:, None, :]
+                fm = fm + ((r - g).abs() * m).sum() / (m.sum() * r.shape[1])
+            m = mask_of(ratios, dg.shape[1], item)
+            gen = gen + (((1 - dg) ** 2) * m).sum() / m.sum()
+        return fm, gen
+    return {"vectorised": (lambda y, yh, r: d_loss(y, yh, r, False), lambda y, yh, r: g_losses(y, yh, r, False)),
+            "reference_form": (lambda y, yh, r: d_loss(y, yh, r, True), lambda y, yh, r: g_losses(y, yh, r, True))}
+
+
+def msd_bench(args, dev):
+    from rad_mmm_amd.discriminators import MultiScaleDiscriminator
+    torch.manual_seed(3)
+    msd = MultiScaleDiscriminator().to(dev).train()
+    note = ("one GPU, one process, one session; fp32; ragged len_ratios on the device (the last item full); median of iters "
+            "after warmup; training mode, so the spectral-norm member advances its power iteration in every form.  d_step: "
+            "discriminator loss forward + parameter gradients, y_hat detached.  g_side: feature + generator loss forward + "
+            "gradient of y_hat, parameters frozen.  torch_*: the same discriminator with torch.nn.functional.conv1d(groups=) "
+            "(MIOpen) under torch autograd, each step computing only the losses of that step; torch_vectorised stacks real "
+            "and generated audio in one pass for the weight-normed members")
+    return disc_bench(args, dev, msd, stock_msd(msd, dev), "msd_step_ms", note)
+
+
 def mpd_bench(args, dev):
     from rad_mmm_amd.discriminators import MultiPeriodDiscriminator
     torch.manual_seed(3)
     mpd = MultiPeriodDiscriminator().to(dev).train()
-    stock = stock_mpd(mpd, dev)
-    res = {"metric": "mpd_step_ms", "iters": args.iters, "warmup": args.warmup, "device": torch.cuda.get_device_name(0),
-           "note": "one GPU, one process, one session; fp32; ragged len_ratios on the device (the last item full); median of "
-                   "iters after warmup.  d_step: discriminator loss forward + parameter gradients, y_hat detached.  g_side: "
-                   "feature + generator loss forward + gradient of y_hat, parameters frozen.  torch_*: the same "
-                   "discriminator with torch.nn.functional.conv2d (MIOpen) under torch autograd, each step computing only "
-                   "the losses of that step; torch_vectorised stacks real and generated audio in one pass", "shapes": {}}
+    note = ("one GPU, one process, one session; fp32; ragged len_ratios on the device (the last item full); median of "
+            "iters after warmup.  d_step: discriminator loss forward + parameter gradients, y_hat detached.  g_side: "
+            "feature + generator loss forward + gradient of y_hat, parameters frozen.  torch_*: the same "
+            "discriminator with torch.nn.functional.conv2d (MIOpen) under torch autograd, each step computing only "
+            "the losses of that step; torch_vectorised stacks real and generated audio in one pass")
+    return disc_bench(args, dev, mpd, stock_mpd(mpd, dev), "mpd_step_ms", note)
+
+
+def disc_bench(args, dev, mpd, stock, metric, note):
+    res = {"metric": metric, "iters": args.iters, "warmup": args.warmup, "device": torch.cuda.get_device_name(0),
+           "note": note, "shapes": {}}
     g = torch.Generator().manual_seed(13)
     for B in (16, 32):
         T = 8192
@@ -543,11 +629,16 @@ def main():
     ap.add_argument("--mel-loss", action="store_true", help="time the mel L1 loss against stock torch")
     ap.add_argument("--mpd", action="store_true", help="time the multi-period discriminator's D step and G side against "
                                                        "stock torch")
-    ap.add_argument("--out", default=None, help="--stft-loss / --mel-loss / --mpd: result file (default "
-                                                "profiles/stft_loss.json / profiles/mel_loss.json / profiles/mpd.json)")
+    ap.add_argument("--msd", action="store_true", help="time the multi-scale discriminator's D step and G side against "
+                                                       "stock torch")
+    ap.add_argument("--d-step-only", action="store_true", help="--msd: run the module's D step at 32 x 8192 a few times and "
+                                                               "exit (the workload of a kernel trace)")
+    ap.add_argument("--out", default=None, help="--stft-loss / --mel-loss / --mpd / --msd: result file (default profiles/"
+                                                "stft_loss.json / mel_loss.json / mpd.json / msd.json)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "mpd.json" if args.mpd else "mel_loss.json" if args.mel_loss else "stft_loss.json")
+        args.out = os.path.join(ROOT, "profiles", "msd.json" if args.msd else "mpd.json" if args.mpd else
+                                "mel_loss.json" if args.mel_loss else "stft_loss.json")
     dev = torch.device("cuda:0")
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
@@ -559,6 +650,21 @@ def main():
         return mel_loss_bench(args, dev)
     if args.mpd:
         return mpd_bench(args, dev)
+    if args.msd and args.d_step_only:
+        from rad_mmm_amd.discriminators import MultiScaleDiscriminator
+        torch.manual_seed(3)
+        msd = MultiScaleDiscriminator().to(dev).train()
+        g = torch.Generator().manual_seed(13)
+        y = (torch.rand(32, 1, 8192, generator=g) * 2 - 1).to(dev)
+        y_hat = (y.cpu() + 0.3 * torch.randn(32, 1, 8192, generator=g)).clamp(-1, 1).to(dev)
+        ratios = (torch.linspace(8192 // 3, 8192, 32).round() / 8192).to(dev)
+        for _ in range(args.warmup + args.iters):
+            msd.zero_grad(set_to_none=True)
+            msd.discriminator_loss(y, y_hat, ratios)[0].backward()
+        torch.cuda.synchronize()
+        return
+    if args.msd:
+        return msd_bench(args, dev)
     res = {"metric": "vocoder_ms", "configs": {}}
     for name, cfg in (("V1", V1), ("V3", V3)):
         gen = HiFiGANGenerator(cfg)

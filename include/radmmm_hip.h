@@ -259,6 +259,8 @@ int radmmm_wgrad_f32_plan(const radmmm_wgrad_desc* d);
  *             (columns not hit by col() are left untouched: zero them once)
  *   backward: from `splits` slabs of dL/dW (layout of W) -> dL/dv [co][ci][tap], dL/dg [co] (+ *poison)
  * v is in the reference's checkpoint layout [Cout][Cin][taps].
+ * radmmm_weightnorm_bwd picks one of several kernels from the shape and the alignment of its operands; all of them give
+ * the same dv and dg up to the order in which the sum over (ci, tap) is added.
  * ------------------------------------------------------------------------------------ */
 int radmmm_weightnorm_fwd(const float* v, const float* g, float* W, float* inv_norm,
                           int Cout, int Cin, int taps, int ldw,
@@ -298,6 +300,7 @@ int radmmm_weightnorm_bwd_multi(const radmmm_wnb_item* items, int n, int taps, c
  *   X0[r, 0:D] = ctx[r, 0:D] ; X0[r, D:D+h] = z[r, 0:h] ; X0[r, D+h:ldx0] = 0
  * and its gradient scatter:
  *   gctx[r, 0:D] (+)= gX0[r, 0:D] ; gz[r, 0:h] += gX0[r, D:D+h]
+ * Columns beyond these ranges (gctx[r, D:ldctx], gz[r, h:ldz]) are never written.
  * ------------------------------------------------------------------------------------ */
 int radmmm_wn_input_fwd(const float* ctx, int ldctx, const float* z, int ldz,
                         float* X0 /* may be NULL when the split copy is written (ABI 3) */, int ldx0, int rows, int D, int h,
@@ -327,6 +330,7 @@ int radmmm_unsqueeze_rows(const float* gout, float* gin /* [B, C, T] */, int B, 
  * backward: given gzout, glog_s (may be NULL), O, z:
  *   gO[r, 0:h] = (gzout1 * z1 + glog_s * dlog_s/ds) * ds/dsu ; gO[r, h:2h] = gzout1
  *   gz[r, 0:h] = gzout[r, 0:h]; gz[r, h:2h] = gzout1 * s ; gz[r, 2h:ldz] = gzout[...]
+ * gO[r, 2h:ldo] is never written.
  * ------------------------------------------------------------------------------------ */
 int radmmm_affine_coupling_fwd(const float* O, int ldo, const float* z, int ldz,
                                float* zout, float* log_s, int rows, int h, int scaling,

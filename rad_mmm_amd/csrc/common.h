@@ -71,6 +71,17 @@ inline int check_launch(const char* what) {
 
 __host__ __device__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+inline hipStream_t ST(radmmm_stream_t s) { return static_cast<hipStream_t>(s); }
+
+// workgroups of a grid-stride launch over `total` elements.  The cap is part of a kernel's result wherever the grid fixes the
+// order of a reduction: files with another cap (elementwise.hip, film.hip, synth.hip, stft_kernels.h, waveglow.hip) keep their own.
+inline int grid_for(long long total, int block, int cap = 8192) {
+  long long g = (total + block - 1) / block;
+  if (g > cap) g = cap;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
 // The frame-shift origin of the row-major weight-gradient kernels (wgrad_rm.hip, wgrad_rm8.hip): the largest shift0 they take.
 // Their mask rule holds for ANY shift -- a row's partner frame f + shift is tested against the readable range [0, lim) of the
 // row's OWN utterance, and a row that fails has its DMA offset replaced by an out-of-range one whatever it was -- so a
@@ -160,6 +171,21 @@ __device__ __forceinline__ float block_sum(float v, float* sh /* >= 17 floats */
   __syncthreads();
   return sh[16];
 }
+
+// block-wide fp64 sum in a fixed tree order for a workgroup of exactly N threads (a power of two); result valid in all threads
+template <int N>
+__device__ __forceinline__ double block_sum_f64(double v, double* sh /* N doubles */) {
+  __syncthreads();
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = N / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : slope * v; }
 
 // weight of row r in a (bias-gradient) column sum: 0 none, 1 length mask, 2 mask x partial-conv ratio
 __device__ __forceinline__ float colsum_row_weight(int r, int row_weight, int T, const int* lens, int taps,

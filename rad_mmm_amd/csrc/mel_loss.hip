@@ -21,14 +21,9 @@
 
 namespace {
 
-inline hipStream_t ST(radmmm_stream_t s) { return static_cast<hipStream_t>(s); }
-
-inline int grid_for(long long total, int block) {
-  long long g = (total + block - 1) / block;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+using radmmm::block_sum_f64;
+using radmmm::grid_for;
+using radmmm::ST;
 
 constexpr int kRowsPerBlock = 4;   // one wave per row, four rows per workgroup
 constexpr int kFinishThreads = 1024;
@@ -173,17 +168,6 @@ __global__ void __launch_bounds__(256) terms_kernel(const float* __restrict__ me
   }
 }
 
-__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = kFinishThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
 // one workgroup: norm[0] = sum_b n[b], out[0] = sum over the rows f < n[b] of part / (n_mel * norm[0]); 0 when no frame counts
 __global__ void __launch_bounds__(kFinishThreads) finish_kernel(const float* __restrict__ part, const int32_t* __restrict__ lens,
                                                                 const int32_t* __restrict__ frames, float* __restrict__ out,
@@ -197,8 +181,8 @@ __global__ void __launch_bounds__(kFinishThreads) finish_kernel(const float* __r
     if (f < loss_frames(lens, frames, b, S, F, Ft, hop)) sum += (double)part[r];
   }
   for (int b = threadIdx.x; b < B; b += kFinishThreads) cnt += (double)loss_frames(lens, frames, b, S, F, Ft, hop);
-  sum = block_sum_f64(sum, sh);
-  cnt = block_sum_f64(cnt, sh);
+  sum = block_sum_f64<kFinishThreads>(sum, sh);
+  cnt = block_sum_f64<kFinishThreads>(cnt, sh);
   if (threadIdx.x == 0) {
     out[0] = cnt > 0.0 ? (float)(sum / ((double)n_mel * cnt)) : 0.f;
     norm[0] = cnt;

@@ -28,19 +28,15 @@
 
 namespace {
 
-inline hipStream_t ST(radmmm_stream_t s) { return static_cast<hipStream_t>(s); }
+using radmmm::block_sum_f64;
+using radmmm::grid_for;
+using radmmm::lrelu;
+using radmmm::ST;
 
 constexpr int kTermsMaxBlocks = 1024;
 constexpr int kFinishThreads = 1024;
 constexpr int kPostRows = 64;   // rows per partial of conv_post_wgrad
 constexpr int kMaxMaps = 8;     // maps of one discriminator, the output included
-
-inline int grid_for(long long total, int block, int cap = 8192) {
-  long long g = (total + block - 1) / block;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
 
 __device__ __forceinline__ int clamp_count(const int32_t* cnt, int b, int size) {
   if (!cnt) return size;
@@ -85,10 +81,10 @@ __global__ void __launch_bounds__(256) repad_kernel(const float* __restrict__ Z,
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (r >= 2 && r < 2 + H) {
       v = *reinterpret_cast<const float4*>(Z + (s * H + r - 2) * ldz + c);
-      v.x = v.x > 0.f ? v.x : slope * v.x;
-      v.y = v.y > 0.f ? v.y : slope * v.y;
-      v.z = v.z > 0.f ? v.z : slope * v.z;
-      v.w = v.w > 0.f ? v.w : slope * v.w;
+      v.x = lrelu(v.x, slope);
+      v.y = lrelu(v.y, slope);
+      v.z = lrelu(v.z, slope);
+      v.w = lrelu(v.w, slope);
     }
     *reinterpret_cast<float4*>(X + sr * C + c) = v;
   }
@@ -328,17 +324,6 @@ struct FinishArgs {
   int n;               // maps: 6 (multi-period), 8 (multi-scale)
 };
 
-__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = kFinishThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
 // res = (fm, mean (1 - dr)^2, mean dg^2, mean (1 - dg)^2), norm[l] = sum_b cnt[l][b] * C_l * p (l < n), norm[n] = sum_b cnt[n][b]
 __global__ void __launch_bounds__(kFinishThreads) finish_kernel(FinishArgs a, float* __restrict__ res, double* __restrict__ norm) {
   __shared__ double sh[kFinishThreads];
@@ -349,8 +334,8 @@ __global__ void __launch_bounds__(kFinishThreads) finish_kernel(FinishArgs a, fl
     double s = 0.0, c = 0.0;
     for (int i = a.off[l] + threadIdx.x; i < a.off[l + 1]; i += kFinishThreads) s += (double)a.part[i];
     for (int b = threadIdx.x; b < a.B; b += kFinishThreads) c += (double)clamp_count(a.cnt ? a.cnt + l * a.B : nullptr, b, a.H[l]);
-    s = block_sum_f64(s, sh);
-    c = block_sum_f64(c, sh) * (double)a.C[l] * (double)a.p;
+    s = block_sum_f64<kFinishThreads>(s, sh);
+    c = block_sum_f64<kFinishThreads>(c, sh) * (double)a.C[l] * (double)a.p;
     if (threadIdx.x == 0) norm[l] = c;
     fm += s / c;
   }
@@ -365,10 +350,10 @@ __global__ void __launch_bounds__(kFinishThreads) finish_kernel(FinishArgs a, fl
     g1 += (1.0 - dg) * (1.0 - dg);
   }
   for (int b = threadIdx.x; b < a.B; b += kFinishThreads) c += (double)clamp_count(cnt_out, b, n);
-  r1 = block_sum_f64(r1, sh);
-  g0 = block_sum_f64(g0, sh);
-  g1 = block_sum_f64(g1, sh);
-  c = block_sum_f64(c, sh);
+  r1 = block_sum_f64<kFinishThreads>(r1, sh);
+  g0 = block_sum_f64<kFinishThreads>(g0, sh);
+  g1 = block_sum_f64<kFinishThreads>(g1, sh);
+  c = block_sum_f64<kFinishThreads>(c, sh);
   if (threadIdx.x == 0) {
     norm[a.n] = c;
     res[0] = (float)fm;

@@ -22,7 +22,9 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-inline hipStream_t ST(radmmm_stream_t s) { return static_cast<hipStream_t>(s); }
+using radmmm::grid_for;
+using radmmm::lrelu;
+using radmmm::ST;
 
 constexpr int kRows = 32;        // output rows (fwd), input rows of one phase (dgrad), contraction rows per step (wgrad)
 constexpr int kChunk = 64;       // weight columns kk staged per step of the forward
@@ -34,8 +36,6 @@ struct GconvArgs {
   int S, Hin, Hout, G, Cin_g, Cout_g, k, st, pad_out;
   float slope;
 };
-
-__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : slope * v; }
 
 // Xs [st * 31 + k][Cin_g + 4]: the tile's input rows; Ws [64][kChunk + 4]: W[g][co][kk0 .. kk0 + 64).  Wave w owns the
 // 16 x 16 subtiles j = w, w + 4 of the 2 x ceil(Cout_g / 16) grid: row half j & 1, column block j >> 1.
@@ -284,13 +284,6 @@ __global__ void __launch_bounds__(256) gconv_wgrad_kernel(const float* __restric
         if (co < a.Cout_g) out[(long long)co * K + ci] = acc[i][j][e];
       }
     }
-}
-
-inline int grid_for(long long total, int block, int cap = 8192) {
-  long long g = (total + block - 1) / block;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
 }
 
 // out[(sig * B + b) * To + j] = (x[2j - 2] + x[2j - 1] + x[2j] + x[2j + 1]) / 4, x = 0 outside [0, T)

@@ -19,14 +19,9 @@
 
 namespace {
 
-inline hipStream_t ST(radmmm_stream_t s) { return static_cast<hipStream_t>(s); }
-
-inline int grid_for(long long total, int block) {
-  long long g = (total + block - 1) / block;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+using radmmm::block_sum_f64;
+using radmmm::grid_for;
+using radmmm::ST;
 
 constexpr float kClamp = 1e-7f;   // torch.clamp(re^2 + im^2, min=1e-7)
 constexpr int kRowsPerBlock = 4;  // one wave per frame row, four rows per workgroup
@@ -97,17 +92,6 @@ __global__ void __launch_bounds__(64 * kRowsPerBlock) terms_kernel(const float* 
   if (lane == 0) *reinterpret_cast<float4*>(part + r * 4) = make_float4(d, n, l, 0.f);
 }
 
-__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = kFinishThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
 // one workgroup: out = (sc, mag), norm = (S, sum D, sum N, 0) in fp64.  Ragged (frames != NULL): S = sum of the frame
 // counts, sc = sum_r sqrt(D_r) / sqrt(N_r) / S, mag = sum_r L_r / (S * cutoff).  Global: S = rows,
 // sc = sqrt(sum D) / sqrt(sum N), mag = sum L / (S * cutoff).
@@ -127,11 +111,11 @@ __global__ void __launch_bounds__(kFinishThreads) finish_kernel(const float* __r
     ratio += sqrt((double)p.x) / sqrt((double)p.y);
   }
   for (int b = threadIdx.x; b < B; b += kFinishThreads) cnt += (double)valid_frames(frames, b, F);
-  ratio = block_sum_f64(ratio, sh);
-  dsum = block_sum_f64(dsum, sh);
-  nsum = block_sum_f64(nsum, sh);
-  lsum = block_sum_f64(lsum, sh);
-  cnt = block_sum_f64(cnt, sh);
+  ratio = block_sum_f64<kFinishThreads>(ratio, sh);
+  dsum = block_sum_f64<kFinishThreads>(dsum, sh);
+  nsum = block_sum_f64<kFinishThreads>(nsum, sh);
+  lsum = block_sum_f64<kFinishThreads>(lsum, sh);
+  cnt = block_sum_f64<kFinishThreads>(cnt, sh);
   if (threadIdx.x == 0) {
     const double sc = frames ? ratio / cnt : sqrt(dsum) / sqrt(nsum);
     out[0] = (float)sc;

@@ -12,7 +12,7 @@
 
 namespace {
 
-inline hipStream_t ST(radmmm_stream_t s) { return static_cast<hipStream_t>(s); }
+using radmmm::ST;
 
 constexpr int SYN_BLOCK = 256;
 constexpr int SYN_MAX_DUR = 65536;      // frames per token: guards the prefix sums against absurd / non-finite predictions

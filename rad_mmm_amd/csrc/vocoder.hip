@@ -18,16 +18,9 @@
 
 namespace {
 
-inline hipStream_t ST(radmmm_stream_t s) { return static_cast<hipStream_t>(s); }
-
-inline int grid_for(long long total, int block) {
-  long long g = (total + block - 1) / block;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
+using radmmm::grid_for;
+using radmmm::lrelu;
+using radmmm::ST;
 
 // y[r, c] = lrelu(x[r, c] / div) for t < lens[b] (c < cols), 0 otherwise and in the padding columns
 // cols <= c < ldy.  ldx, ldy % 4 == 0: one float4 per thread.  x and y carry no __restrict__: the generator calls this

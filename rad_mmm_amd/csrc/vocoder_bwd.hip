@@ -9,9 +9,8 @@
 
 namespace {
 
-inline hipStream_t ST(radmmm_stream_t s) { return static_cast<hipStream_t>(s); }
-
-__device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
+using radmmm::lrelu;
+using radmmm::ST;
 
 // m = a > 0 ? gy : gy * slope ; q = m / div ; gx = accum ? gx + q : q  (the order the header states)
 __device__ __forceinline__ float dlrelu(float gy, float a, float base, float div, float slope, int accum) {

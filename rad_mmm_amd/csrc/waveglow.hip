@@ -30,7 +30,7 @@
 
 namespace {
 
-inline hipStream_t ST(radmmm_stream_t s) { return static_cast<hipStream_t>(s); }
+using radmmm::ST;
 
 inline int grid_for(long long total, int block) {
   long long g = (total + block - 1) / block;

@@ -277,6 +277,48 @@ def test_only_the_requested_gradients_are_computed(fx, monkeypatch):
     assert D.LAUNCHES["dgrad_audio"] == 5 and D.LAUNCHES["mpd_unfold_audio"] == 5
 
 
+@pytest.mark.parametrize("frozen", [(0, 1), (0, 1, 2, 3, 4)], ids=["convs_0_and_1", "all_but_conv_post"])
+def test_partially_frozen_d_step_stops_where_nothing_below_is_wanted(golden, monkeypatch, frozen):
+    """A D step (y_hat detached) with the convs `frozen` of every DiscriminatorP frozen, on the t64 fixture: the unfrozen
+    parameters' gradients have the bits of the fully unfrozen step, the frozen ones get none, and the backward walk stops
+    descending at the lowest unfrozen conv.  The module against itself across freezing patterns: no tolerance."""
+    import rad_mmm_amd.discriminators as D
+    d = golden("mpd_t64.npz")
+    y, y_hat, ratios = _dev(d["y"]), _dev(d["y_hat"]), _dev(d["len_ratios"])
+    mpd = _model(_sd(d), NARROW)
+
+    def d_step():
+        mpd.zero_grad(set_to_none=True)
+        mpd.discriminator_loss(y, y_hat.detach(), ratios)[0].backward()
+        return {k: None if p.grad is None else p.grad.clone() for k, p in mpd.named_parameters()}
+
+    full = d_step()
+    assert all(g is not None for g in full.values())
+    is_frozen = {k: any(f".convs.{l}." in k for l in frozen) for k in full}
+    assert sum(is_frozen.values()) == 5 * 3 * len(frozen)             # weight_g, weight_v, bias per conv and discriminator
+    for k, p in mpd.named_parameters():
+        p.requires_grad_(not is_frozen[k])
+    monkeypatch.setattr(D, "LAUNCHES", {})
+    part = d_step()
+    for k in full:
+        if is_frozen[k]:
+            assert part[k] is None, k
+        else:
+            assert torch.equal(part[k], full[k]), k
+    assert "dgrad_audio" not in D.LAUNCHES and "mpd_unfold_audio" not in D.LAUNCHES
+    # The walk goes conv_post, convs.4, .., convs.0.  The data gradient of framed conv l (1 .. 4) is launched while some conv
+    # below it, convs.0 .. convs.l-1, is unfrozen: with m the lowest unfrozen conv that is l = m + 1 .. 4, 4 - m levels (0 if
+    # all five are frozen), and conv_post's own data gradient is launched if any conv is unfrozen at all.
+    unfrozen = [l for l in range(5) if l not in frozen]
+    levels = 4 - min(unfrozen) if unfrozen else 0                     # convs 0, 1 frozen: 2; all five frozen: 0
+    assert D.LAUNCHES.get("dgrad", 0) == D.LAUNCHES.get("mpd_unframe", 0) == 5 * levels
+    assert D.LAUNCHES.get("mpd_conv_post_dgrad", 0) == (5 if unfrozen else 0)
+    assert D.LAUNCHES.get("wgrad", 0) == 5 * len(unfrozen)            # one per unfrozen framed or first conv
+    assert D.LAUNCHES["mpd_conv_post_wgrad"] == 5
+    if not unfrozen:
+        assert "dgrad" not in D.LAUNCHES and "mpd_conv_post_dgrad" not in D.LAUNCHES
+
+
 def test_repeatable_and_free_of_synchronisation(fx):
     mpd = _model(fx["sd"], NARROW)
     first = _step(mpd, fx["y"], fx["y_hat"], fx["ratios"])          # also warms every lazily initialised piece up

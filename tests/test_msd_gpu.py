@@ -251,6 +251,50 @@ def test_only_the_requested_gradients_are_computed(fx, monkeypatch):
     assert D.LAUNCHES["msd_gconv_dgrad"] == 3 * 5
 
 
+def test_partially_frozen_d_step_stops_where_nothing_below_is_wanted(golden, monkeypatch):
+    """A D step (y_hat detached) in training mode with convs.0 .. convs.2 of every member frozen, on the t64 fixture: the
+    unfrozen parameters' gradients have the bits of the fully unfrozen step, the frozen ones get none, and each of the four
+    passes (the spectral-norm member walks two) stops descending at convs.3.  The power iteration's buffers are put back
+    between the runs, so both see the same weights.  The module against itself: no tolerance."""
+    import rad_mmm_amd.discriminators as D
+    d = golden("msd_t64.npz")
+    y, y_hat, ratios = _dev(d["y"]), _dev(d["y_hat"]), _dev(d["len_ratios"])
+    msd = _model(_sd(d), tuple(int(c) for c in d["widths"]), tuple(int(g) for g in d["groups"]))
+    state = {k: v.clone() for k, v in _vectors(msd).items()}
+
+    def d_step():
+        msd.zero_grad(set_to_none=True)
+        with torch.no_grad():
+            for k, v in _vectors(msd).items():
+                v.copy_(state[k])
+        msd.discriminator_loss(y, y_hat.detach(), ratios)[0].backward()
+        return {k: None if p.grad is None else p.grad.clone() for k, p in msd.named_parameters()}
+
+    full = d_step()
+    assert all(g is not None for g in full.values())
+    frozen = (0, 1, 2)
+    is_frozen = {k: any(f".convs.{l}." in k for l in frozen) for k in full}
+    assert sum(is_frozen.values()) == len(frozen) * (2 + 3 + 3)       # weight_orig, bias; weight_g, weight_v, bias twice
+    for k, p in msd.named_parameters():
+        p.requires_grad_(not is_frozen[k])
+    monkeypatch.setattr(D, "LAUNCHES", {})
+    part = d_step()
+    for k in full:
+        if is_frozen[k]:
+            assert part[k] is None, k
+        else:
+            assert torch.equal(part[k], full[k]), k
+    assert not {"dgrad_audio", "msd_unframe15", "msd_avgpool_bwd"} & set(D.LAUNCHES)
+    # The walk goes conv_post, convs.6 (dense), convs.5 .. convs.1 (grouped), convs.0.  The data gradient of grouped conv l is
+    # launched while some conv below it is unfrozen: with convs.3 the lowest unfrozen one that is l = 4, 5, two levels.
+    passes, levels = 4, 5 - (max(frozen) + 1)
+    assert levels == 2
+    assert D.LAUNCHES["msd_gconv_dgrad"] == levels * passes
+    assert D.LAUNCHES["msd_gconv_wgrad"] == 3 * passes                # convs.3 .. convs.5
+    assert D.LAUNCHES["dgrad"] == passes and D.LAUNCHES["wgrad"] == passes        # convs.6 alone: convs.0 is frozen
+    assert D.LAUNCHES["mpd_conv_post_wgrad"] == passes
+
+
 def test_repeatable_and_free_of_synchronisation(fx):
     msd = _model(fx["sd"], *fx["narrow"])
     state = {k: v.clone() for k, v in _vectors(msd).items()}

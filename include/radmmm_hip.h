@@ -807,6 +807,44 @@ int32_t radmmm_voc_conv_post_bwd(const float* x, int ldx, const float* w, int ld
                              float* dx, int lddx, float* dw, float* dbias, float* scratch, int rows, int C, int taps,
                              int T, const int32_t* lens, float div, float slope, radmmm_stream_t stream);
 
+/* HiFi-GAN vocoding in f16 (additive entry points of ABI 4; csrc/vocoder_f16.hip): ONE dilated Conv1d(C, C, taps,
+ * dilation dil, padding "same") of a resblock on the f16 matrix cores (v_mfma_f32_32x32x16_f16, fp32 accumulate), the
+ * leaky-relu of its operand applied while the input tile is loaded, bias, residual and mask in the epilogue.  Rows are
+ * channels-last, r = b*T + t:
+ *     a(b, t, c) = h(lrelu(in_scale * X[r*ldx + c]))         for 0 <= t < lens[b], else 0
+ *                  lrelu(v) = v >= 0 ? v : in_slope * v        (fp32; in_slope = 1: none)
+ *                  h = round to nearest even to fp16 after the clamp to +-60000
+ *     v(b, t, n) = acc_scale * sum_{tap, c} Wh[(tap*C + n)*ldw + c] * a(b, t + (tap - taps/2)*dil, c)   (fp32 accumulate)
+ *     v += bias[n];  if (add) v += add[r*ldadd + n]            (in this order, fp32)
+ *     Y [r*ldy  + n] = t < lens[b] ? v : 0
+ *     Y2[r*ldy2 + n] = (y2_accum ? Y2[r*ldy2 + n] + : ) (t < lens[b] ? v : 0)         (Y2 optional)
+ * Wh: fp16 [taps][C][ldw] holding fp16(W * s), acc_scale = 1 / s.  lens == NULL: full length.  Nothing at or past a length
+ * is read into the result (X and add may hold NaN there).  Y must alias neither X, add nor Y2.  No atomics: two launches
+ * give the same bits.  X and Wh 16-byte aligned, ldx % 4 == 0, ldw % 8 == 0; columns C <= c < ld* are neither read nor
+ * written.
+ * Shapes taken: C a multiple of 16 in 16 .. 256, taps odd and <= 11, reach (taps/2)*dil <= 40.  radmmm_voc_conv_f16_plan
+ * (host only: no HIP call, no pointer dereferenced) returns RADMMM_VOC_F16_KERNEL_CODE(ntc, mi) of the instantiation a
+ * descriptor reaches -- ntc column tiles of 32 and mi row tiles of 32 per wave, a workgroup owning 128 * mi frames of one
+ * item -- or 0 with the reason in radmmm_last_error() for a shape that is not taken, or -1 for bad arguments (null
+ * pointers, dims, pitches, alignment, aliasing).  radmmm_voc_conv_f16 returns -1 in both cases before any HIP call: no
+ * kernel runs on a shape the plan refuses.  radmmm_voc_conv_f16_last_kernel: the code of the calling thread's last launch
+ * (0: none yet).  (int32_t, the same type as int here, as for the two entry points above.) */
+typedef struct {
+  const float* X; int ldx;
+  const void* Wh; int ldw;
+  float* Y; int ldy;
+  int B, T, C, taps, dil;
+  const int32_t* lens;
+  const float* bias;
+  const float* add; int ldadd;
+  float* Y2; int ldy2; int y2_accum;
+  float in_scale, in_slope, acc_scale;
+} radmmm_voc_conv_f16_desc;
+#define RADMMM_VOC_F16_KERNEL_CODE(ntc, mi) ((ntc) * 100 + (mi))
+int32_t radmmm_voc_conv_f16(const radmmm_voc_conv_f16_desc* d, radmmm_stream_t stream);
+int32_t radmmm_voc_conv_f16_plan(const radmmm_voc_conv_f16_desc* d);
+int32_t radmmm_voc_conv_f16_last_kernel(void);
+
 /* ------------------------------------------------------------------------------------
  * WaveGlow inference (vocoders/waveglow_for_LIMMITS23/glow.py:105-175 WN.forward, :251-293 WaveGlow.infer).  The wide
  * convolutions are radmmm_rowgemm_f32 launches (the ConvTranspose1d(n_mel, n_mel, 1024, 256) upsample as ONE polyphase

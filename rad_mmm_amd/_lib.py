@@ -117,6 +117,15 @@ class RowGemmH3Desc(C.Structure):
     ]
 
 
+class VocConvF16Desc(C.Structure):
+    """radmmm_voc_conv_f16_desc: one fused lrelu + dilated conv of a HiFi-GAN resblock on the f16 matrix cores"""
+    _fields_ = [("X", C.c_void_p), ("ldx", C.c_int), ("Wh", C.c_void_p), ("ldw", C.c_int), ("Y", C.c_void_p), ("ldy", C.c_int),
+                ("B", C.c_int), ("T", C.c_int), ("C", C.c_int), ("taps", C.c_int), ("dil", C.c_int),
+                ("lens", C.c_void_p), ("bias", C.c_void_p), ("add", C.c_void_p), ("ldadd", C.c_int),
+                ("Y2", C.c_void_p), ("ldy2", C.c_int), ("y2_accum", C.c_int),
+                ("in_scale", C.c_float), ("in_slope", C.c_float), ("acc_scale", C.c_float)]
+
+
 class WnItem(C.Structure):
     """radmmm_wn_item: one tensor of radmmm_weightnorm_fwd_h3_multi"""
     _fields_ = [("v", C.c_void_p), ("g", C.c_void_p), ("Wh", C.c_void_p), ("Wl", C.c_void_p), ("inv_norm", C.c_void_p),
@@ -236,6 +245,8 @@ def _load() -> C.CDLL:
         "radmmm_voc_normalize": [p, i, p, i, i, p],
         "radmmm_voc_lrelu_bwd": [p, i, p, i, p, i, i, i, i, p, f, f, i, p],
         "radmmm_voc_conv_post_bwd": [p, i, p, i, p, p, p, i, p, p, p, i, i, i, i, p, f, f, p],
+        "radmmm_voc_conv_f16": [C.POINTER(VocConvF16Desc), p], "radmmm_voc_conv_f16_plan": [C.POINTER(VocConvF16Desc)],
+        "radmmm_voc_conv_f16_last_kernel": [],
         "radmmm_wg_group_cond": [p, i64, p, i, p, i, i, i, i, p],
         "radmmm_wg_noise_rows": [p, f, p, i, i, i, p, i, i, p],
         "radmmm_wg_start": [p, i, i, i, p, p, p, i, i, p, i, i, p],
@@ -480,6 +491,46 @@ def _h3_desc(kw, addr=ptr):
             v = addr(v)
         setattr(d if k in _H3_KEYS else d.base, k, v)
     return d
+
+
+def _voc_f16_desc(kw, addr=ptr) -> VocConvF16Desc:
+    d = VocConvF16Desc()
+    d.taps = 1
+    d.dil = 1
+    d.in_scale = 1.0
+    d.in_slope = 1.0
+    d.acc_scale = 1.0
+    for k, v in kw.items():
+        if isinstance(v, torch.Tensor):
+            v = addr(v)
+        setattr(d, k, v)
+    return d
+
+
+def voc_f16_kernel_code(ntc: int, mi: int) -> int:
+    """RADMMM_VOC_F16_KERNEL_CODE of include/radmmm_hip.h: ntc column tiles of 32 and mi row tiles of 32 per wave (a
+    workgroup owns 128 * mi frames of one item)"""
+    return ntc * 100 + mi
+
+
+def voc_conv_f16(**kw) -> None:
+    """one fused lrelu + dilated conv on the f16 matrix cores (radmmm_voc_conv_f16): keys of VocConvF16Desc"""
+    check(lib.radmmm_voc_conv_f16(C.byref(_voc_f16_desc(kw)), stream()), "radmmm_voc_conv_f16")
+
+
+def voc_conv_f16_plan(**kw) -> int:
+    """which instantiation voc_conv_f16(**kw) would reach (radmmm_voc_conv_f16_plan), as voc_f16_kernel_code, or 0 for a
+    shape the family does not take (the reason: lib.radmmm_last_error()).  Host only, the tensors may live anywhere and an
+    integer stands for an address.  Raises on bad arguments."""
+    rc = int(lib.radmmm_voc_conv_f16_plan(C.byref(_voc_f16_desc(kw, _addr))))
+    if rc < 0:
+        check(rc, "radmmm_voc_conv_f16_plan")
+    return rc
+
+
+def voc_conv_f16_last_kernel() -> int:
+    """the code of this thread's last voc_conv_f16 launch (0: none yet)"""
+    return int(lib.radmmm_voc_conv_f16_last_kernel())
 
 
 def _wgrad_desc(kw, addr=ptr) -> WgradDesc:

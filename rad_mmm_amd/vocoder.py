@@ -15,6 +15,12 @@ radmmm_rowgemm_f32 launch (exact fp32 MFMA):
   * the inverse STFT is the same polyphase GEMM (u = hop, k = n_fft, N = hop), the trim folded into the packing.
 leaky_relu of a conv's operand, conv_post + tanh, the reflect pad, the bin rescale, the window-sum division and the
 normalisation are kernels of csrc/vocoder.hip.
+
+That is precision "fp32", the default.  With HiFiGANGenerator.precision "f16" (inference only, opt-in) every resblock conv
+of a stage whose width the kernel takes is ONE radmmm_voc_conv_f16 launch (csrc/vocoder_f16.hip): fp16 operands, fp32
+accumulation on the f16 matrix cores, the leaky-relu applied while the input tile is loaded, so no radmmm_voc_lrelu
+launch is left inside a resblock.  conv_pre, the transposed convs, conv_post and the denoiser stay fp32, and so does a
+stage the kernel does not take (widths such as 8 or 4): precision_plan() says what a config gets.
 """
 from __future__ import annotations
 
@@ -27,12 +33,13 @@ import torch
 from torch import nn
 
 from . import ops
-from ._lib import RadmmmError, check, f32c, fp32_region, lib, ptr, rowgemm, stream
+from ._lib import RadmmmError, check, f32c, fp32_region, lib, ptr, rowgemm, stream, voc_conv_f16, voc_conv_f16_plan
 from .audio_processing import _hann_periodic, windowed_dft_basis
 
 LRELU_SLOPE = 0.1          # hifigan_models.py:52 (the final leaky_relu before conv_post uses torch's default 0.01)
 POST_SLOPE = 0.01
 N_MEL = 80
+PRECISIONS = ("fp32", "f16")           # HiFiGANGenerator.precision: how inference runs the resblock convs
 _OPERAND_BYTES = 2 ** 31 - 2 ** 16     # the row GEMM's 16-row fast path needs operands below 2 GiB
 
 
@@ -172,8 +179,11 @@ class HiFiGANGenerator(nn.Module):
     """HiFi-GAN Generator(h) (hifigan_models.py:172-247): same sub-module and state_dict names (conv_pre, ups.{i},
     resblocks.{i}.{j}.convs1/convs2/convs.{n}, conv_post with .weight_g/.weight_v/.bias), forward on the GPU.
 
-    forward(mel [B, 80, T], lens=None) -> audio [B, 1, T * prod(upsample_rates)], zero past lens[b] * hop.
-    lens: host (list / CPU tensor: no synchronisation) or device lengths in mel frames."""
+    forward(mel [B, 80, T], lens=None, precision=None) -> audio [B, 1, T * prod(upsample_rates)], zero past lens[b] * hop.
+    lens: host (list / CPU tensor: no synchronisation) or device lengths in mel frames.
+    precision ("fp32", the default, or "f16"; the attribute `precision`, or per call): how inference runs the resblock
+    convs.  "f16": fp16 operands and fp32 accumulation on the f16 matrix cores in every stage the kernel takes
+    (precision_plan()); the rest of the model, and a training step, stay fp32."""
 
     def __init__(self, h):
         super().__init__()
@@ -214,6 +224,7 @@ class HiFiGANGenerator(nn.Module):
         self.conv_post = _wn(nn.Conv1d(ch, 1, 7, 1, padding=3))
         self._folded = None
         self._folded_key = None
+        self.precision = "fp32"
 
     def load_state_dict(self, state_dict, strict: bool = True):
         self._folded = None
@@ -265,6 +276,49 @@ class HiFiGANGenerator(nn.Module):
         self._folded, self._folded_key = f, key
         return f
 
+    # ---- precision "f16": which stages run on radmmm_voc_conv_f16, and their fp16 weights -----------------------------
+    @staticmethod
+    def _check_precision(precision: str) -> str:
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision {precision!r}: one of {PRECISIONS}")
+        return precision
+
+    def _mode(self, precision: Optional[str] = None) -> str:
+        """the mode a call runs in (None: the attribute), a known name; `precision` means inference only: in training
+        mode with grad enabled the step is the fp32 step whatever the name says"""
+        mode = self._check_precision(self.precision if precision is None else precision)
+        return "fp32" if self._train_active() else mode
+
+    def precision_plan(self, precision: Optional[str] = None) -> list:
+        """per stage (mode, reason): ("f16", "") when every resblock conv of the stage reaches a radmmm_voc_conv_f16
+        kernel, else ("fp32", why).  Host only (the kernel family's own plan query decides), any device."""
+        mode = self._check_precision(self.precision if precision is None else precision)
+        out = []
+        a = 0x10000                                      # stands for an address: the plan query dereferences nothing
+        for group in self.resblocks:
+            if mode == "fp32":
+                out.append(("fp32", "precision 'fp32'"))
+                continue
+            why = ""
+            for blk in group:
+                for c, d, _, _ in blk.plan():
+                    C = c.in_channels
+                    ld = ops.round_up(C, 8)
+                    if not voc_conv_f16_plan(X=a, ldx=ld, Wh=a, ldw=ld, Y=2 * a, ldy=ld, B=1, T=1, C=C, taps=c.kernel_size[0],
+                                             dil=d, bias=a):
+                        why = why or lib.radmmm_last_error().decode()
+            out.append(("fp32", why) if why else ("f16", ""))
+        return out
+
+    def _f16_weights(self, f: dict, i: int) -> list:
+        """fp16(W * ops.W_SCALE) of stage i's folded resblock weights, [taps, C, C] each, per block in conv order.  Made
+        once per fold and kept inside it, so they go when a parameter changes."""
+        cache = f.setdefault("f16", {})
+        if i not in cache:
+            cache[i] = [[ops.split_f16(Wc.view(-1, Wc.shape[2]), Wc.shape[2], ops.W_SCALE, Wc.shape[2], nprod=1)[0]
+                         for Wc, _, _, _, _, _ in blk] for blk in f["res"][i]]
+        return cache[i]
+
     # ---- training: the same forward under one autograd node whose backward is the HIP path -------------------------
     def _train_active(self) -> bool:
         return self.training and torch.is_grad_enabled()
@@ -306,9 +360,12 @@ class HiFiGANGenerator(nn.Module):
             raise ValueError("HiFiGANGenerator: conv_post's backward kernel holds at most 1024 channels")
 
     @fp32_region
-    def forward(self, mel: torch.Tensor, lens=None) -> torch.Tensor:
+    def forward(self, mel: torch.Tensor, lens=None, precision: Optional[str] = None) -> torch.Tensor:
         """In training mode with grad enabled, and when mel or a parameter requires grad, the audio carries a grad_fn
-        whose backward runs in HIP (same audio bits as eval mode); otherwise the plain launch sequence."""
+        whose backward runs in HIP (same audio bits as eval mode); otherwise the plain launch sequence.
+        precision ("fp32" or "f16"; None: the attribute `precision`): how inference runs the resblock convs; a training
+        step ignores it."""
+        mode = self._mode(precision)
         if not mel.is_cuda:
             raise RadmmmError("HiFiGANGenerator needs a GPU tensor (there is no CPU path)")
         if mel.dim() != 3 or mel.shape[1] != N_MEL:
@@ -319,15 +376,18 @@ class HiFiGANGenerator(nn.Module):
         if self._train_active() and (mel.requires_grad or any(p.requires_grad for p in self.parameters())):
             self._check_train_shape(B, T)
             return _GeneratorFn.apply(self, f32c(mel), lens_d, *self._train_weights())
-        return self._run(f32c(mel), lens_d)
+        return self._run(f32c(mel), lens_d, precision=mode)
 
     def _run(self, mel: torch.Tensor, lens_d: torch.Tensor, events: Optional[list] = None,
-             tape: Optional[dict] = None) -> torch.Tensor:
+             tape: Optional[dict] = None, precision: str = "fp32") -> torch.Tensor:
         """events: a list that receives a recorded device event after conv_pre, each stage and conv_post (timing).
         tape (a training step, _GeneratorFn): the same launches with the same arguments, but every conv's A operand goes
         to a buffer of its own and is recorded in tape with the shapes the backward walk needs; the audio's bits do not
-        depend on it."""
+        depend on it.
+        precision "f16" (never with a tape): the stages precision_plan marks "f16" run their resblock convs on
+        radmmm_voc_conv_f16; everything else is the fp32 launch sequence unchanged."""
         B, _, T = mel.shape
+        stage_mode = [m for m, _ in self.precision_plan(precision)] if tape is None else ["fp32"] * self.num_upsamples
         mark = (lambda: events.append(torch.cuda.Event(enable_timing=True)) or events[-1].record()) if events is not None \
             else (lambda: None)
         mark()
@@ -360,8 +420,21 @@ class HiFiGANGenerator(nn.Module):
             a = torch.empty(R, C, device=mel.device, dtype=torch.float32)
             t = torch.empty(R, C, device=mel.device, dtype=torch.float32)
             bufs = [torch.empty(R, C, device=mel.device, dtype=torch.float32) for _ in range(2)]
+            wh16 = self._f16_weights(f, i) if stage_mode[i] == "f16" else None
             for j, blk in enumerate(f["res"][i]):
                 xc, nxt = xu, 0
+                if wh16 is not None:           # c1 writes raw t; every conv applies the leaky-relu to what it loads
+                    for n, (Wc, bc, k, d, act, add) in enumerate(blk):
+                        last = n == len(blk) - 1
+                        out = bufs[nxt] if add else t
+                        voc_conv_f16(X=t if add and n > 0 and blk[n - 1][4] else xc, ldx=C, Wh=wh16[j][n], ldw=C, Y=out,
+                                     ldy=C, B=B, T=Tc, C=C, taps=k, dil=d, lens=lc, bias=bc, add=xc if add else None,
+                                     ldadd=C, Y2=xs if add and last else None, ldy2=C,
+                                     y2_accum=1 if (add and last and j > 0) else 0, in_scale=1.0, in_slope=LRELU_SLOPE,
+                                     acc_scale=1.0 / ops.W_SCALE)
+                        if add:
+                            xc, nxt = out, 1 - nxt
+                    continue
                 ops_j = []                     # tape: the A operand of every conv of this block, in order
                 for n, (Wc, bc, k, d, act, add) in enumerate(blk):
                     if tape is not None:       # a buffer per operand instead of the shared pair
@@ -571,7 +644,7 @@ class Denoiser(nn.Module):
     def _bias(self, dev):
         if self.bias_spec is None or self.bias_spec.device != dev:
             mel0 = torch.zeros(1, N_MEL, 88, device=dev)
-            audio = self.generator(mel0)[:, 0]
+            audio = self.generator(mel0, precision="fp32")[:, 0]       # always the fp32 path, once per model
             spec = self._spectrum(audio, None, torch.ones(1, dtype=torch.int32, device=dev), 1)
             mag = torch.empty(self.cutoff, device=dev, dtype=torch.float32)
             check(lib.radmmm_voc_spec_bins(ptr(spec), self.ldk, 1, self.cutoff, None, 0.0, ptr(mag), stream()),
@@ -631,18 +704,20 @@ class Denoiser(nn.Module):
 
 @fp32_region
 def vocode(generator: HiFiGANGenerator, denoiser: Optional[Denoiser], mels: torch.Tensor, out_lens,
-           strength: float = 0.001, normalize: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+           strength: float = 0.001, normalize: bool = True, precision: Optional[str] = None
+           ) -> Tuple[torch.Tensor, torch.Tensor]:
     """mels [B, 80, T] (descaled, as the reference passes them) + lengths in frames -> (audio [B, T*hop] zero padded,
     sample lengths [B] int64 on the host when out_lens was on the host, else on the device).  get_audio_for_mels
     (vocoder_utils.py:35-48) for the whole batch: generator, denoiser at `strength`, and with normalize each item
-    scaled by 1 / max|audio| over its own samples."""
+    scaled by 1 / max|audio| over its own samples.  precision: as HiFiGANGenerator.forward (None: generator.precision)."""
+    mode = generator._mode(precision)
     if not mels.is_cuda:
         raise RadmmmError("vocode needs GPU tensors (there is no CPU path)")
     B, _, T = mels.shape
     dev = mels.device
     lens_d, host = _lens_arg(out_lens, B, T, dev)
     hop = generator.hop
-    audio = generator._run(f32c(mels), lens_d)[:, 0]
+    audio = generator._run(f32c(mels), lens_d, precision=mode)[:, 0]
     s_lens = host * hop if host is not None else lens_d.long() * hop
     if denoiser is not None:
         audio = denoiser(audio, strength, s_lens)[:, 0]
@@ -654,10 +729,12 @@ def vocode(generator: HiFiGANGenerator, denoiser: Optional[Denoiser], mels: torc
     return audio, s_lens
 
 
-def load_hifigan_vocoder(checkpoint_path: str, config_path: str, device: Union[str, torch.device] = "cuda"):
+def load_hifigan_vocoder(checkpoint_path: str, config_path: str, device: Union[str, torch.device] = "cuda",
+                         precision: str = "fp32"):
     """load_hifigan_vocoder of vocoders/vocoder_utils.py:104-132: the config JSON + torch.load(path)['generator'];
     the Gaussian blur stays off unless the path names it ('blur'), which this package does not support (raises).
-    Returns (generator, denoiser) on `device`, in eval mode."""
+    Returns (generator, denoiser) on `device`, in eval mode.  precision: the generator's `precision` attribute."""
+    HiFiGANGenerator._check_precision(precision)
     with open(config_path) as fh:
         h = json.load(fh)
     if "blur" in checkpoint_path:
@@ -668,5 +745,6 @@ def load_hifigan_vocoder(checkpoint_path: str, config_path: str, device: Union[s
     gen = HiFiGANGenerator(h)
     gen.load_state_dict(sd)
     gen = gen.to(device).eval()
+    gen.precision = precision
     den = Denoiser(gen).to(device).eval()
     return gen, den

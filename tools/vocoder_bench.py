@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Batched HiFi-GAN vocoder benchmark (rad_mmm_amd/vocoder.py): one JSON line.
 
-    python tools/vocoder_bench.py [--iters 5] [--warmup 2] [--no-torch]
+    python tools/vocoder_bench.py [--iters 5] [--warmup 2] [--no-torch] [--precision {fp32,f16}] [--config V1|V3]
+                                  [--shape BxT]
     python tools/vocoder_bench.py --train [--iters 5] [--warmup 2]
     python tools/vocoder_bench.py --stft-loss [--iters 5] [--warmup 2] [--out profiles/stft_loss.json]
     python tools/vocoder_bench.py --mel-loss [--iters 5] [--warmup 2] [--out profiles/mel_loss.json]
@@ -11,7 +12,10 @@
 Generator and denoiser ms per call at (B, T) = (32, 800) and (1, 800) for the V1 and V3 configs (random weights
 from a seed), the real-time factor (seconds of 22.05 kHz audio per second of compute), per-stage ms of the generator
 with its FLOP, bytes and the fraction of the binding roof, and a side leg: the same generator written with stock
-torch.nn.functional fp32 convs on the same GPU.  Device events around each call, after warm-up.
+torch.nn.functional fp32 convs on the same GPU.  Device events around each call, after warm-up.  --precision f16 runs
+the generator in its f16 mode (HiFiGANGenerator.precision): a stage on radmmm_voc_conv_f16 is held against the f16 MFMA
+roof and its bytes count no leaky-relu copies; the row also carries the audio's rel-L2 distance from the fp32 mode.
+--config / --shape restrict the run to one config or one (B, T) (the workload of a kernel trace).
 
 --train: one training step of V1 (forward, a fixed quadratic loss on the audio, backward; weight norm on, as a
 training checkpoint) at upstream HiFi-GAN's training shape, batch 16 x 32 frames (8192 samples), and at batch 32 x 32
@@ -69,6 +73,7 @@ from rad_mmm_amd.vocoder import Denoiser, HiFiGANGenerator, fold_weight_norm  # 
 
 SR = 22050
 FP32_MFMA_TF = 157.3     # v_mfma_f32_32x32x2_f32, MI355X
+F16_MFMA_TF = 2500.0     # v_mfma_f32_32x32x16_f16, dense peak
 HBM_TBS = 8.0
 
 
@@ -87,8 +92,9 @@ def timed(fn, iters, warmup):
     return float(np.median(ts))
 
 
-def stage_costs(gen, cfg, B, T):
-    """FLOP and HBM bytes (fp32 tensors read/written by each launch) per stage: conv_pre, stages, conv_post"""
+def stage_costs(gen, cfg, B, T, plan=None):
+    """FLOP and HBM bytes (fp32 tensors read/written by each launch) per stage: conv_pre, stages, conv_post.  plan: the
+    modes per stage (HiFiGANGenerator.precision_plan); an "f16" stage has no leaky-relu copies"""
     c0 = cfg["upsample_initial_channel"]
     rows = B * T
     out = [("conv_pre", 2.0 * rows * 80 * c0 * 7, 4.0 * rows * (80 + c0))]
@@ -103,7 +109,8 @@ def stage_costs(gen, cfg, B, T):
             for m in blk.modules():
                 if isinstance(m, torch.nn.Conv1d):
                     flop += 2.0 * rows * C * C * m.kernel_size[0]
-                    byt += 4.0 * rows * C * 5          # lrelu copy (r+w), conv operand read, residual read, output write
+                    # lrelu copy (r+w), conv operand read, residual read, output write; f16: the copy is fused into the load
+                    byt += 4.0 * rows * C * (3 if plan and plan[i][0] == "f16" else 5)
         out.append((f"stage{i + 1}", flop, byt))
     out.append(("conv_post", 2.0 * rows * C * 7, 4.0 * rows * (C + 1)))
     return out
@@ -633,6 +640,9 @@ def main():
                                                        "stock torch")
     ap.add_argument("--d-step-only", action="store_true", help="--msd: run the module's D step at 32 x 8192 a few times and "
                                                                "exit (the workload of a kernel trace)")
+    ap.add_argument("--precision", choices=("fp32", "f16"), default="fp32", help="the generator's inference mode")
+    ap.add_argument("--config", choices=("V1", "V3"), default=None, help="only this config")
+    ap.add_argument("--shape", default=None, help="only this BxT, e.g. 32x800")
     ap.add_argument("--out", default=None, help="--stft-loss / --mel-loss / --mpd / --msd: result file (default profiles/"
                                                 "stft_loss.json / mel_loss.json / mpd.json / msd.json)")
     args = ap.parse_args()
@@ -665,15 +675,21 @@ def main():
         return
     if args.msd:
         return msd_bench(args, dev)
-    res = {"metric": "vocoder_ms", "configs": {}}
+    res = {"metric": "vocoder_ms", "precision": args.precision, "configs": {}}
+    shapes = ((32, 800), (1, 800)) if args.shape is None else (tuple(int(v) for v in args.shape.split("x")),)
     for name, cfg in (("V1", V1), ("V3", V3)):
+        if args.config not in (None, name):
+            continue
         gen = HiFiGANGenerator(cfg)
         sd = random_state(gen, 5, 0.2, 0.6)
         gen.load_state_dict(sd)
         gen = gen.to(dev).eval()
         den = Denoiser(gen).to(dev)
+        den._bias(dev)                       # on the fp32 path, before the switch
+        gen.precision = args.precision
+        plan = gen.precision_plan()
         g = torch.Generator().manual_seed(6)
-        for B, T in ((32, 800), (1, 800)):
+        for B, T in shapes:
             mel = (torch.randn(B, 80, T, generator=g) - 2.0).to(dev)
             lens = [T] * B
             audio = gen(mel, lens)[:, 0].contiguous()
@@ -684,18 +700,32 @@ def main():
             row = {"generator_ms": round(gms, 3), "denoiser_ms": round(dms, 3),
                    "rtf": round(secs / ((gms + dms) / 1e3), 1), "audio_s": round(secs, 2),
                    "generator_tflop": round(sum(c[1] for c in stage_costs(gen, cfg, B, T)) / 1e12, 3)}
+            if args.precision != "fp32":
+                a32 = gen(mel, lens, precision="fp32")[:, 0]
+                row["rel_l2_vs_fp32"] = float((audio - a32).norm() / a32.norm())
+                row["plan"] = [m for m, _ in plan]
+                del a32
             # per-stage: device events between the stages of one call
             ev = []
             lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
             for _ in range(2):
                 ev = []
-                gen._run(mel, lens_d, ev)
+                gen._run(mel, lens_d, ev, precision=args.precision)
             torch.cuda.synchronize()
             stages = []
-            for (sname, flop, byt), e0, e1 in zip(stage_costs(gen, cfg, B, T), ev[:-1], ev[1:]):
+            for (sname, flop, byt), e0, e1 in zip(stage_costs(gen, cfg, B, T, plan), ev[:-1], ev[1:]):
                 ms = e0.elapsed_time(e1)
-                t_c, t_m = flop / (FP32_MFMA_TF * 1e12), byt / (HBM_TBS * 1e12)
-                roof = "fp32_mfma" if t_c >= t_m else "hbm"
+                # an f16 stage: its transposed conv (fp32 MFMA) and its resblock convs (f16 MFMA) each at their own peak
+                f16 = sname.startswith("stage") and plan[int(sname[5:]) - 1][0] == "f16"
+                if f16:
+                    i = int(sname[5:]) - 1
+                    up = 2.0 * (B * T * int(np.prod(cfg["upsample_rates"][:i]))) * (cfg["upsample_initial_channel"] >> i) * \
+                        (cfg["upsample_initial_channel"] >> (i + 1)) * cfg["upsample_kernel_sizes"][i]
+                    t_c = up / (FP32_MFMA_TF * 1e12) + (flop - up) / (F16_MFMA_TF * 1e12)
+                else:
+                    t_c = flop / (FP32_MFMA_TF * 1e12)
+                t_m = byt / (HBM_TBS * 1e12)
+                roof = ("f16_mfma" if f16 else "fp32_mfma") if t_c >= t_m else "hbm"
                 stages.append({"stage": sname, "ms": round(ms, 3), "gflop": round(flop / 1e9, 1),
                                "mbytes": round(byt / 1e6, 1), "roof": roof,
                                "roof_fraction": round(max(t_c, t_m) * 1e3 / ms, 3) if ms > 0 else None})

@@ -749,6 +749,18 @@ int radmmm_sumsq(const float* x, int64_t n, float* partial, radmmm_stream_t stre
 int radmmm_radam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* clip_coef, float beta1,
                       float beta2, float eps, float step_size, float wd_lr, int use_denom, radmmm_stream_t stream);
 
+/* torch.optim.Adam (decoupled = 0) / AdamW (decoupled = 1) on a flat fp32 buffer, with torch's arithmetic:
+ *   g *= clip_coef[0] (optional device scalar);  decoupled ? p *= 1 - lr * wd : g += wd * p;
+ *   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps).
+ * The step count t lives on the device (int32 [1]): radmmm_adam_advance adds 1 to it once per optimizer step, then every
+ * bucket's radmmm_adam_step reads it and derives b1^t, b2^t in double.  skip: optional device int32 [1]; when non-zero
+ * neither call writes anything (p, m, v and the counter keep their bits, whatever g holds), without a host read.
+ * Pointers must be 16-byte aligned; -1 before any HIP call otherwise, on a null pointer and on n <= 0. */
+int radmmm_adam_advance(int32_t* step, const int32_t* skip, radmmm_stream_t stream);
+int radmmm_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* clip_coef, const int32_t* step,
+                     const int32_t* skip, double lr, double beta1, double beta2, double eps, double weight_decay,
+                     int decoupled, radmmm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * HiFi-GAN vocoder and STFT denoiser (vocoders/hifigan_models.py:104-247, vocoders/hifigan_denoiser.py:25-58,
  * audio_processing.py:195-291).  Every convolution is a radmmm_rowgemm_f32 launch (conv_pre and the resblock convs

@@ -166,7 +166,7 @@ def _load() -> C.CDLL:
     if lib.radmmm_abi_version() != 4:
         raise ImportError("libradmmm_hip.so ABI version mismatch")
     i, i64, p = C.c_int, C.c_int64, C.c_void_p
-    f = C.c_float
+    f, d = C.c_float, C.c_double
     so = C.POINTER(SplitOpts)
     sig = {
         "radmmm_rowgemm_f32": [C.POINTER(RowGemmDesc), p],
@@ -211,6 +211,8 @@ def _load() -> C.CDLL:
         "radmmm_pq_spline_inv": [p, i, p, i, p, i, i, i, i, p],
         "radmmm_sumsq": [p, i64, p, p],
         "radmmm_radam_step": [p, p, p, p, i64, p, f, f, f, f, f, i, p],
+        "radmmm_adam_advance": [p, p, p],
+        "radmmm_adam_step": [p, p, p, p, i64, p, p, p, d, d, d, d, d, i, p],
         "radmmm_transpose_split_act_colsum": [p, i, i, i, i, i, i, p, i, f, p, p, p, p, i, p, i, i, i, p],
         "radmmm_colsum_final": [p, p, i, i, p],
         "radmmm_colsum_final_multi": [C.POINTER(CsItem), i, p], "radmmm_rowgemm_h3_colsum_rows": [C.POINTER(RowGemmH3Desc)],

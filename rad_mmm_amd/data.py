@@ -412,3 +412,168 @@ class DeviceCollate:
         if self.timing_events is not None:
             self.timing_events[-1][1].record(cur)
         return batch
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Random fixed-length segments for vocoder training (upstream HiFi-GAN's meldataset: segment_size 8192): the crop happens
+# on the host while the staging buffer is filled, the unpack and the mel are DeviceCollate's kernels
+# ---------------------------------------------------------------------------------------------------------------------
+@dataclass
+class SegmentPlan:
+    """Where every item's segment comes from and goes (plan_segments); rows in the caller's order."""
+    starts: np.ndarray                  # int64 [B] first sample of the crop inside the item
+    counts: np.ndarray                  # int64 [B] samples staged, min(S_b - start, segment_size)
+    lens: np.ndarray                    # int64 [B] mel frames, counts // hop
+    offsets: np.ndarray                 # int64 [B] first sample of the crop in the packed sample section
+    n_samples: int                      # length of the packed section (elements)
+    segment_size: int
+    audio_dtype: np.dtype               # int16 or float32: one per batch
+
+
+def plan_segments(items: Sequence[dict], hop_length: int, filter_length: int = 1024, segment_size: int = 8192,
+                  starts: Optional[Sequence[int]] = None, generator: Optional[torch.Generator] = None) -> SegmentPlan:
+    """Host-side layout of a batch of segments (no GPU needed).  items: dicts with `audio`, 1-D int16 or float32 host
+    samples as plan_batch takes them.  starts: one per item, or None: drawn from `generator` (a CPU torch.Generator, None:
+    torch's default), uniformly from 0 .. S_b - segment_size (0 for an item shorter than the segment, which is staged whole).
+    Every staged range must hold more than filter_length // 2 samples, the reflect pad of the STFT."""
+    hop_length, filter_length, segment_size = int(hop_length), int(filter_length), int(segment_size)
+    if len(items) == 0:
+        raise ValueError("plan_segments: empty batch")
+    if segment_size <= filter_length // 2 or segment_size % hop_length:
+        raise ValueError(f"plan_segments: segment_size {segment_size} must be a multiple of hop_length {hop_length} above "
+                         f"filter_length // 2 = {filter_length // 2}")
+    if starts is not None and len(starts) != len(items):
+        raise ValueError(f"plan_segments: {len(starts)} starts for {len(items)} items")
+    dtypes, st, cnt = set(), [], []
+    for i, it in enumerate(items):
+        a = _host_array(it["audio"])
+        if a.ndim != 1 or a.dtype not in (np.int16, np.float32):
+            raise ValueError(f"plan_segments: item {i}: audio must be 1-D int16 or float32 samples (got {a.dtype}, {a.ndim}-D)")
+        dtypes.add(a.dtype)
+        s = int(a.shape[0])
+        if s <= filter_length // 2:
+            raise ValueError(f"plan_segments: item {i}: {s} samples; the reflect pad of the STFT needs more than "
+                             f"filter_length // 2 = {filter_length // 2}")
+        if starts is not None:
+            b = int(starts[i])
+            if not 0 <= b < s:
+                raise ValueError(f"plan_segments: item {i}: start {b} outside its {s} samples")
+        else:
+            hi = max(s - segment_size, 0)
+            b = int(torch.randint(0, hi + 1, (1,), generator=generator)) if hi > 0 else 0
+        n = min(s - b, segment_size)
+        if n <= filter_length // 2:
+            raise ValueError(f"plan_segments: item {i}: start {b} leaves {n} samples; the reflect pad of the STFT needs more "
+                             f"than filter_length // 2 = {filter_length // 2}")
+        st.append(b)
+        cnt.append(n)
+    if len(dtypes) != 1:
+        raise ValueError("plan_segments: int16 and float32 audio mixed in one batch")
+    so = [0]
+    for n in cnt:
+        so.append(so[-1] + _r(n, _SAMPLE_ALIGN))
+    i64 = lambda v: np.asarray(v, dtype=np.int64)
+    return SegmentPlan(starts=i64(st), counts=i64(cnt), lens=i64(cnt) // hop_length, offsets=i64(so[:-1]), n_samples=so[-1],
+                       segment_size=segment_size, audio_dtype=dtypes.pop())
+
+
+def segment_layout(plan: SegmentPlan):
+    """({section: (byte offset, bytes)}, total bytes) of the staging buffer: 16-byte aligned sections"""
+    B = len(plan.starts)
+    off, o = {}, 0
+    for k, n in (("offsets", B * 8), ("lens", 2 * B * 4), ("audio", plan.n_samples * plan.audio_dtype.itemsize)):
+        off[k] = (o, n)
+        o += _r(n, 16)
+    return off, o
+
+
+def stage_segments(plan: SegmentPlan, items: Sequence[dict], hb: np.ndarray) -> int:
+    """Fill the staging bytes `hb` (uint8, at least segment_layout(plan)[1] long): the packed offsets, the sample and frame
+    counts, and the cropped samples alone -- item b's [start, start + count).  Returns the bytes used."""
+    off, total = segment_layout(plan)
+    B = len(plan.starts)
+
+    def sec(name, dtype):
+        o, n = off[name]
+        return hb[o:o + n].view(dtype)
+    sec("offsets", np.int64)[:] = plan.offsets
+    lens = sec("lens", np.int32).reshape(2, B)
+    lens[0], lens[1] = plan.counts, plan.lens
+    audio = sec("audio", plan.audio_dtype)
+    for b, it in enumerate(items):
+        s, n, o = int(plan.starts[b]), int(plan.counts[b]), int(plan.offsets[b])
+        audio[o:o + n] = _host_array(it["audio"])[s:s + n]
+    return total
+
+
+class SegmentCollate:
+    """Batches of fixed-length segments for vocoder training, on the device: SegmentCollate(stft, segment_size, generator)
+    (items, starts=None) -> {"mel" [B, n_mel, segment_size // hop], "audio" [B, 1, segment_size], "lens" [B] valid frames
+    (int32, device), "lens_host" (int64 CPU tensor)}, rows in the caller's order.  Item b contributes its samples
+    [start, start + segment_size) (plan_segments); a shorter item is staged whole and zero-padded on the right, lens[b] =
+    min(S_b - start, segment_size) // hop.  The mel is the first segment_size // hop frames of the ragged log-mel of the
+    segments at their valid sample counts (stft.mel_spectrogram_ragged, each item reflect-padded at its own two ends), exact
+    zeros from frame lens[b] on.  int16 samples are scaled by 1 / max_wav_value.
+
+    Only the cropped ranges go through the pinned staging buffer: one host -> device copy per call, no device -> host read;
+    the unpack and the mel are DeviceCollate's kernels, and the buffers are kept between calls in the same way."""
+
+    def __init__(self, stft, segment_size: int = 8192, generator: Optional[torch.Generator] = None,
+                 max_wav_value: float = 32768.0):
+        dev = stft.mel_basis.device
+        if dev.type != "cuda":
+            raise RuntimeError("SegmentCollate: move the TacotronSTFT to the GPU first (there is no CPU path)")
+        s = stft.stft_fn
+        if int(segment_size) <= s.filter_length // 2 or int(segment_size) % s.hop_length:
+            raise ValueError(f"SegmentCollate: segment_size {segment_size} must be a multiple of hop_length {s.hop_length} "
+                             f"above filter_length // 2 = {s.filter_length // 2}")
+        self.stft, self.device, self.segment_size, self.generator = stft, dev, int(segment_size), generator
+        self.max_wav_value = float(max_wav_value)
+        self._slots = [{"host": _Grow(), "event": None}, {"host": _Grow(), "event": None}]
+        self._turn = 0
+        self._dev_staging, self._scratch = _Grow(), _Grow()
+        self._last_stream = None
+
+    def __call__(self, items: Sequence[dict], starts: Optional[Sequence[int]] = None) -> dict:
+        s = self.stft.stft_fn
+        hop, n_mel, seg, dev = s.hop_length, self.stft.n_mel_channels, self.segment_size, self.device
+        plan = plan_segments(items, hop, s.filter_length, seg, starts, self.generator)
+        B = len(items)
+        off, total = segment_layout(plan)
+
+        cur = torch.cuda.current_stream(dev)
+        if self._last_stream is not None and self._last_stream != cur:
+            cur.wait_stream(self._last_stream)               # the kept buffers were last used there
+        self._last_stream = cur
+        slot = self._slots[self._turn]
+        self._turn ^= 1
+        if slot["event"] is not None:
+            slot["event"].synchronize()                      # its previous host -> device copy (two calls ago) has left
+        host = slot["host"].get(total, dtype=torch.uint8, pin_memory=True)
+        stage_segments(plan, items, host.numpy())
+        dbuf = self._dev_staging.get(total, dtype=torch.uint8, device=dev)
+        dbuf[:total].copy_(host[:total], non_blocking=True)
+        if slot["event"] is None:
+            slot["event"] = torch.cuda.Event()
+        slot["event"].record(cur)
+
+        def dsec(name, dtype):
+            o, n = off[name]
+            return dbuf[o:o + n].view(dtype)
+        d_lens = dsec("lens", torch.int32).view(2, B)
+        packed = dsec("audio", torch.int16 if plan.audio_dtype == np.int16 else torch.float32)
+        Smax = int(plan.counts.max())
+        F = seg // hop
+        f32 = dict(device=dev, dtype=torch.float32)
+        audio = torch.empty(B, 1, Smax, **f32)
+        scratch = self._scratch.get(int(lib.radmmm_collate_scratch_floats(B, Smax, s.filter_length, hop, n_mel)), **f32)
+        # frames_device = lens: the ragged mel's last frame of an item, 1 + count // hop, is cut (exact zeros from lens[b] on)
+        mel = self.stft.mel_spectrogram_ragged(packed, plan.counts, None, lens_device=d_lens[0], frames_device=d_lens[1],
+                                               offsets=dsec("offsets", torch.int64), scale=1.0 / self.max_wav_value
+                                               if plan.audio_dtype == np.int16 else 1.0, audio_out=audio, scratch=scratch)
+        if Smax == seg:
+            mel = mel[:, :, :F].contiguous()
+        else:                                                # every item is shorter than the segment
+            mel = torch.nn.functional.pad(mel[:, :, :F], (0, F - min(F, mel.shape[2])))
+            audio = torch.nn.functional.pad(audio, (0, seg - Smax))
+        return {"mel": mel, "audio": audio, "lens": d_lens[1].clone(), "lens_host": torch.from_numpy(plan.lens.copy())}

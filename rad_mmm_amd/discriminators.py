@@ -722,12 +722,13 @@ class MultiPeriodDiscriminator(_MultiDiscriminator):
         self.discriminators = nn.ModuleList(DiscriminatorP(p, channels) for p in periods)
 
 
-def load_mpd(path: str, device="cuda") -> MultiPeriodDiscriminator:
-    """the `mpd` entry of an upstream do_* checkpoint -> MultiPeriodDiscriminator on `device`"""
+def load_mpd(path: str, device="cuda", **model_kwargs) -> MultiPeriodDiscriminator:
+    """the `mpd` entry of an upstream do_* checkpoint -> MultiPeriodDiscriminator on `device`; model_kwargs go to the
+    constructor (a checkpoint of a narrow model)"""
     ckpt = torch.load(path, map_location="cpu")
     if "mpd" not in ckpt:
         raise KeyError(f"{path} has no 'mpd' entry (keys: {sorted(ckpt)[:8]})")
-    mpd = MultiPeriodDiscriminator()
+    mpd = MultiPeriodDiscriminator(**model_kwargs)
     mpd.load_state_dict(ckpt["mpd"])
     return mpd.to(device)
 
@@ -781,11 +782,12 @@ class MultiScaleDiscriminator(_MultiDiscriminator):
         self.meanpools = nn.ModuleList([nn.AvgPool1d(4, 2, padding=2), nn.AvgPool1d(4, 2, padding=2)])   # (no parameters)
 
 
-def load_msd(path: str, device="cuda") -> MultiScaleDiscriminator:
-    """the `msd` entry of an upstream do_* checkpoint -> MultiScaleDiscriminator on `device`"""
+def load_msd(path: str, device="cuda", **model_kwargs) -> MultiScaleDiscriminator:
+    """the `msd` entry of an upstream do_* checkpoint -> MultiScaleDiscriminator on `device`; model_kwargs go to the
+    constructor (a checkpoint of a narrow model)"""
     ckpt = torch.load(path, map_location="cpu")
     if "msd" not in ckpt:
         raise KeyError(f"{path} has no 'msd' entry (keys: {sorted(ckpt)[:8]})")
-    msd = MultiScaleDiscriminator()
+    msd = MultiScaleDiscriminator(**model_kwargs)
     msd.load_state_dict(ckpt["msd"])
     return msd.to(device)

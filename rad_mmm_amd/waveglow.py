@@ -449,6 +449,15 @@ class WaveGlow(nn.Module):
         self._sat_flag.zero_()
         return hit
 
+    def saturation_flag(self) -> torch.Tensor:
+        """the device int32 [1] word grad_saturated() reads (created zeroed when no "h3" step has run yet), for a guard that
+        stays on the device: `FlatAdam.step(skip=model.saturation_flag())` turns a clamped step into a no-op without a
+        device -> host read.  Clearing it stays with grad_saturated()."""
+        dev = next(self.parameters()).device
+        if self._sat_flag is None or self._sat_flag.device != dev:
+            self._sat_flag = torch.zeros(1, device=dev, dtype=torch.int32)
+        return self._sat_flag
+
     @fp32_region
     def infer(self, mel: torch.Tensor, lens=None, sigma: float = 1.0, noise: Optional[Sequence[torch.Tensor]] = None,
               precision: Optional[str] = None) -> torch.Tensor:

@@ -8,6 +8,7 @@
     python tools/vocoder_bench.py --mel-loss [--iters 5] [--warmup 2] [--out profiles/mel_loss.json]
     python tools/vocoder_bench.py --mpd [--iters 5] [--warmup 2] [--out profiles/mpd.json]
     python tools/vocoder_bench.py --msd [--iters 5] [--warmup 2] [--out profiles/msd.json]
+    python tools/vocoder_bench.py --gan-step [--iters 5] [--warmup 2] [--out profiles/hifigan_gan_step.json]
 
 Generator and denoiser ms per call at (B, T) = (32, 800) and (1, 800) for the V1 and V3 configs (random weights
 from a seed), the real-time factor (seconds of 22.05 kHz audio per second of compute), per-stage ms of the generator
@@ -54,7 +55,15 @@ also goes to --out (profiles/mpd.json).
 
 --msd: the same for the multi-scale discriminator (the reference's widths and groups, training mode) against stock torch
 with conv1d(groups=), to profiles/msd.json; --msd --d-step-only runs the module's D step at 32 x 8192 alone, the workload
-of the kernel trace kept as profiles/msd_d_step_kernel_stats.csv."""
+of the kernel trace kept as profiles/msd_d_step_kernel_stats.csv.
+
+--gan-step: the whole HiFi-GAN fine-tuning step (V1, the default discriminators, the default three STFT resolutions, mel
+weight 45) at 16 x 32 and 32 x 32 frames (8192 samples) with ragged lens.  Leg a: rad_mmm_amd.vocoder_step.
+HiFiGANTrainingStep (two fused FlatAdam, the discriminators frozen during the G side).  Leg b: the README recipe as it is
+written, on the same modules, with two torch.optim.AdamW; its process then also times the recipe with the discriminators'
+parameters frozen during the G side (b_frozen), which isolates the optimizers.  Order a b b a, one fresh process per leg
+(the parent never opens the GPU), median of --iters steps after --warmup; per leg ms per step, device launches, host
+synchronisations and peak allocated memory.  The JSON also goes to --out."""
 import argparse
 import json
 import os
@@ -626,6 +635,109 @@ def disc_bench(args, dev, mpd, stock, metric, note):
     print(json.dumps(res))
 
 
+def gan_step_leg(args, dev):
+    """one leg of --gan-step in this process: one JSON line"""
+    from rad_mmm_amd.discriminators import MultiPeriodDiscriminator, MultiScaleDiscriminator
+    from rad_mmm_amd.mel_loss import MelSpectrogramLoss
+    from rad_mmm_amd.stft_loss import MultiResolutionSTFTLoss
+    gen = HiFiGANGenerator(V1)
+    gen.load_state_dict(random_state(gen, 5, 0.2, 0.6))
+    torch.manual_seed(3)
+    gen, mpd, msd = gen.to(dev).train(), MultiPeriodDiscriminator().to(dev).train(), MultiScaleDiscriminator().to(dev).train()
+    loss_fn, mel_loss = MultiResolutionSTFTLoss().to(dev), MelSpectrogramLoss().to(dev)
+    n_params = sum(p.numel() for m in (gen, mpd, msd) for p in m.parameters())
+    hop = gen.hop
+    d_params = list(mpd.parameters()) + list(msd.parameters())
+    if args.leg == "a":
+        from rad_mmm_amd.vocoder_step import HiFiGANTrainingStep
+        obj = HiFiGANTrainingStep(gen, mpd, msd, stft_loss=loss_fn, mel_loss=mel_loss)
+        forms = {"a": lambda mel, lens, target: obj.training_step(mel, lens, target)["g_total"]}
+    else:
+        opt_g = torch.optim.AdamW(gen.parameters(), 2e-4, betas=(0.8, 0.99))
+        opt_d = torch.optim.AdamW(d_params, 2e-4, betas=(0.8, 0.99))
+
+        def recipe(mel, lens, target, frozen=False):
+            lens = torch.as_tensor(lens, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+            audio = gen(mel, lens)
+            ratios = lens / lens.max()
+            opt_d.zero_grad()
+            loss_p, _, _ = mpd.discriminator_loss(target, audio.detach(), ratios)
+            loss_s, _, _ = msd.discriminator_loss(target, audio.detach(), ratios)
+            (loss_p + loss_s).backward()
+            opt_d.step()
+            opt_g.zero_grad()
+            for p in d_params:
+                p.requires_grad_(not frozen)
+            fm_p, gen_p = mpd.generator_losses(target, audio, ratios)
+            fm_s, gen_s = msd.generator_losses(target, audio, ratios)
+            sc, mag = loss_fn(audio[:, 0], target[:, 0], ratios)
+            total = 45 * mel_loss(audio[:, 0], mel, lens * hop, lens) + fm_p + fm_s + gen_p + gen_s + sc + mag
+            total.backward()
+            opt_g.step()
+            for p in d_params:
+                p.requires_grad_(True)
+            return total.detach()
+        forms = {"b": recipe, "b_frozen": lambda mel, lens, target: recipe(mel, lens, target, True)}
+    res = {"leg": args.leg, "device": torch.cuda.get_device_name(0), "parameters": n_params, "shapes": {}}
+    g = torch.Generator().manual_seed(17)
+    for B in (16, 32):
+        T = 32
+        lens = [int(v) for v in torch.linspace(T // 3, T, B).round()]
+        mel = (torch.randn(B, 80, T, generator=g) - 2.0).to(dev)
+        target = torch.rand(B, 1, T * hop, generator=g) * 2 - 1
+        for b, n in enumerate(lens):
+            target[b, :, n * hop:] = 0.0
+        target = target.to(dev)
+        row = {}
+        for key, fn in forms.items():
+            step = lambda: fn(mel, lens, target)
+            torch.cuda.empty_cache()
+            ms = timed(step, args.iters, args.warmup)
+            launches, syncs = count_launches_and_syncs(step)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            loss = step()
+            torch.cuda.synchronize()
+            row[key] = {"step_ms": round(ms, 3), "launches": launches, "host_syncs": syncs,
+                        "peak_allocated_mb": round(torch.cuda.max_memory_allocated() / 2 ** 20, 1), "g_total": float(loss)}
+        res["shapes"][f"B{B}_T{T}"] = row
+        print(json.dumps({f"B{B}_T{T}": row}), file=sys.stderr, flush=True)
+    print(json.dumps(res))
+
+
+def gan_step_bench(args):
+    """--gan-step: legs a b b a, each in a fresh process; this process never opens the GPU"""
+    import subprocess
+    runs = []
+    for leg in "abba":
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--gan-step", "--leg", leg, "--iters", str(args.iters),
+                              "--warmup", str(args.warmup)], check=True, stdout=subprocess.PIPE, text=True).stdout
+        runs.append(json.loads(out.strip().splitlines()[-1]))
+    res = {"metric": "hifigan_gan_step_ms", "config": "V1", "frames": 32, "iters": args.iters, "warmup": args.warmup,
+           "device": runs[0]["device"], "parameters": runs[0]["parameters"], "order": "a b b a",
+           "note": "one GPU, one fresh process per leg, one session; fp32; ragged host lens; median of iters after warmup.  "
+                   "a: HiFiGANTrainingStep (two FlatAdam, discriminators frozen during the G side).  b: the README recipe "
+                   "as written with two torch.optim.AdamW.  b_frozen: the recipe with the discriminators' parameters "
+                   "frozen during the G side (same process as b).  step_ms: both runs of the leg and their mean",
+           "shapes": {}}
+    for shape in runs[0]["shapes"]:
+        row = {}
+        for r in runs:
+            for key, v in r["shapes"][shape].items():
+                e = row.setdefault(key, dict(v, step_ms=[]))
+                e["step_ms"].append(v["step_ms"])
+        for e in row.values():
+            e["step_ms_mean"] = round(sum(e["step_ms"]) / len(e["step_ms"]), 3)
+        for key in ("b", "b_frozen"):
+            row[key]["over_a"] = round(row[key]["step_ms_mean"] / row["a"]["step_ms_mean"], 3)
+        res["shapes"][shape] = row
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
@@ -640,6 +752,10 @@ def main():
                                                        "stock torch")
     ap.add_argument("--d-step-only", action="store_true", help="--msd: run the module's D step at 32 x 8192 a few times and "
                                                                "exit (the workload of a kernel trace)")
+    ap.add_argument("--gan-step", action="store_true", help="time the whole HiFi-GAN fine-tuning step: HiFiGANTrainingStep "
+                                                            "against the README recipe with torch.optim.AdamW")
+    ap.add_argument("--leg", choices=("a", "b"), default=None, help="--gan-step: run this leg in this process (the driver "
+                                                                    "starts one process per leg)")
     ap.add_argument("--precision", choices=("fp32", "f16"), default="fp32", help="the generator's inference mode")
     ap.add_argument("--config", choices=("V1", "V3"), default=None, help="only this config")
     ap.add_argument("--shape", default=None, help="only this BxT, e.g. 32x800")
@@ -647,11 +763,15 @@ def main():
                                                 "stft_loss.json / mel_loss.json / mpd.json / msd.json)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "msd.json" if args.msd else "mpd.json" if args.mpd else
-                                "mel_loss.json" if args.mel_loss else "stft_loss.json")
+        args.out = os.path.join(ROOT, "profiles", "hifigan_gan_step.json" if args.gan_step else "msd.json" if args.msd else
+                                "mpd.json" if args.mpd else "mel_loss.json" if args.mel_loss else "stft_loss.json")
+    if args.gan_step and args.leg is None:
+        return gan_step_bench(args)
     dev = torch.device("cuda:0")
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
+    if args.gan_step:
+        return gan_step_leg(args, dev)
     if args.train:
         return train_bench(args, dev)
     if args.stft_loss:

@@ -1235,6 +1235,43 @@ int radmmm_mpd_out_grad(const float* out, const int32_t* cnt, const double* norm
                         int H, radmmm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * The multi-period discriminator's precision "h3" (csrc/mpd_h3.hip; additive entry points of ABI 4): the producers that feed
+ * the wide convs' three passes to radmmm_rowgemm_h3 / radmmm_wgrad_rm without an fp32 round trip.  Every pair is
+ * RADMMM_SPLIT_F16 of scale * value, element for element the bits of radmmm_split_f16; sat_flag (or NULL) as
+ * radmmm_split_opts.sat_flag, bit 0.  C % 8 == 0, 16-byte aligned arrays, pair pitches % 8 == 0; columns of a pair row at
+ * or beyond the matrix' width are left alone.  rows_pad: the pair holds max(rows, rows_pad) rows and the rows from `rows`
+ * on are written as zeros (radmmm_wgrad_rm contracts at least 32 rows; zero rows add nothing).  Memory-bound passes, no
+ * reductions: equal inputs give equal bits.  Bad arguments return -1 before any HIP call.
+ *   radmmm_mpdh3_repad            radmmm_mpd_repad (the same fp32 map X, bit for bit) + the map's pair Xh / Xl in the same
+ *                                  padded layout [S][H + 4][C], pad rows zero: the framed A operand of the next conv
+ *                                  (radmmm_rowgemm_h3 with a_item_stride = (H + 4) * C, lda_h = stride * C, K = 5 * C)
+ *   radmmm_mpdh3_frame            radmmm_mpd_frame written as a pair: Fh / Fl [max(S * Ho, rows_pad)][ldf], row
+ *                                  (s, h') = the 5 * C values of map s from padded row stride * h' on; no fp32 frames
+ *   radmmm_mpdh3_unframe          radmmm_mpd_unframe (the same dZ, bit for bit; dZ may be NULL) + the pair dZh / dZl
+ *                                  [max(S * H, rows_pad)][ldh] of scale * dZ
+ *   radmmm_mpdh3_conv_post_dgrad  radmmm_mpd_conv_post_dgrad in the same way
+ *   radmmm_mpdh3_plan             host only, like radmmm_rowgemm_h3_plan (< 0: bad dims): 1 when the dense 5-tap conv Cin -> Cout of stride `stride` on S
+ *                                  sequences of Hin rows (Hout windows) can run its three passes on the split kernels as
+ *                                  the discriminator launches them -- the framed forward GEMM and the data-gradient GEMM
+ *                                  pass radmmm_rowgemm_h3's plan, the weight gradient radmmm_wgrad_rm's checks at
+ *                                  max(S * Hout, 32) rows and one tap -- else 0 with the reason in radmmm_last_error
+ * radmmm_rowgemm_h3 takes the framed descriptor for this (ABI 4, additive): base.a_item_stride != 0, in HALVES of Ah / Al:
+ * item b, frame t at b * a_item_stride + t * lda_h, rows may overlap (lda_h < K); one tap, no extra segment, a_mask_mode 0,
+ * three or one product; a_item_stride % 8 == 0.
+ * ------------------------------------------------------------------------------------ */
+int radmmm_mpdh3_repad(const float* Z, int ldz, float* X, void* Xh, void* Xl, int S, int H, int C, float slope, float scale,
+                        int32_t* sat_flag, radmmm_stream_t stream);
+int radmmm_mpdh3_frame(const float* X, void* Fh, void* Fl, int ldf, int S, int H, int C, int Ho, int stride, int rows_pad,
+                        float scale, int32_t* sat_flag, radmmm_stream_t stream);
+int radmmm_mpdh3_unframe(const float* dF, const float* add, const float* X, float* dZ, void* dZh, void* dZl, int ldh, int S,
+                          int H, int C, int Ho, int stride, float slope, int rows_pad, float scale, int32_t* sat_flag,
+                          radmmm_stream_t stream);
+int radmmm_mpdh3_conv_post_dgrad(const float* dOut, const float* W, const float* add, const float* X, float* dZ, void* dZh,
+                                  void* dZl, int ldh, int B2, int p, int H, int C, float slope, int rows_pad, float scale,
+                                  int32_t* sat_flag, radmmm_stream_t stream);
+int radmmm_mpdh3_plan(int S, int Hin, int Cin, int Hout, int Cout, int stride);
+
+/* ------------------------------------------------------------------------------------
  * Grouped strided 1-d convolution on the fp32 matrix cores, forward and backward (additive entry points of ABI 4): the
  * kernel family of the HiFi-GAN multi-scale discriminator's five grouped 41-tap layers (hifigan_models.py: DiscriminatorS).
  * Geometry: S sequences, G groups, C_in = G*Cin_g, C_out = G*Cout_g, k taps (odd, <= 41), stride st in {1, 2, 4}, zero pad

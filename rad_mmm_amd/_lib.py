@@ -302,6 +302,11 @@ def _load() -> C.CDLL:
         "radmmm_mpd_finish": [p, p, p, p, p, p, p, p, i, i, p],
         "radmmm_mpd_fm_grad": [p, p, p, p, p, i, i, i, i, p],
         "radmmm_mpd_out_grad": [p, p, p, p, p, i, i, i, p],
+        "radmmm_mpdh3_repad": [p, i, p, p, p, i, i, i, f, f, p, p],
+        "radmmm_mpdh3_frame": [p, p, p, i, i, i, i, i, i, i, f, p, p],
+        "radmmm_mpdh3_unframe": [p, p, p, p, p, p, i, i, i, i, i, i, f, i, f, p, p],
+        "radmmm_mpdh3_conv_post_dgrad": [p, p, p, p, p, p, p, i, i, i, i, i, f, i, f, p, p],
+        "radmmm_mpdh3_plan": [i, i, i, i, i, i],
         "radmmm_msd_gconv_fwd": [p, p, p, p, i, i, i, i, i, i, i, i, i, f, p],
         "radmmm_msd_gconv_dgrad": [p, p, p, p, p, i, i, i, i, i, i, i, i, f, p],
         "radmmm_msd_gconv_wgrad": [p, p, p, i, i, i, i, i, i, i, i, p],

@@ -60,7 +60,9 @@ __global__ __launch_bounds__(256, 2) void rowgemm_h3_kernel(const radmmm_rowgemm
       const int b = r / p.T;
       a_t[i] = r - b * p.T;
       a_lim[i] = (p.a_mask_mode && p.lens) ? p.lens[b] : p.T;
-      a_base[i] = (b * p.T * q.lda_h + s_chunk * 8) * 2;
+      // (framed form: an item's rows start a_item_stride halves apart instead of T * lda_h; 32-bit is enough because
+      // plan_rowgemm_h3 keeps a_bytes, which covers every row below M, under 2 GiB)
+      a_base[i] = (b * (p.a_item_stride ? (int)p.a_item_stride : p.T * q.lda_h) + s_chunk * 8) * 2;
     }
     const int n = n0 + s_row + 64 * i;
     b_voff[i] = n < p.N ? (n * q.ldb_h + s_chunk * 8) * 2 : OOB;

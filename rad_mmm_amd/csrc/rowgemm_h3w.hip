@@ -136,8 +136,12 @@ int plan_rowgemm_h3(const radmmm_rowgemm_h3_desc* d, h3_plan* pl) {
   RADMMM_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0 && p.taps >= 1 && p.T > 0 && p.M % p.T == 0, "rowgemm_h3: bad dims");
   RADMMM_REQUIRE(p.K % BK == 0, "rowgemm_h3: K=%d must be a multiple of 32", p.K);
   RADMMM_REQUIRE(p.b_layout == 0, "rowgemm_h3: both operands are K-contiguous (use a transposed weight copy)");
-  RADMMM_REQUIRE(p.a_item_stride == 0, "rowgemm_h3: a_item_stride is not supported");
-  RADMMM_REQUIRE(d->lda_h % 8 == 0 && d->ldb_h % 8 == 0 && d->lda_h >= p.K && d->ldb_h >= p.K && d->b_tap_stride_h % 8 == 0,
+  // the framed form (include/radmmm_hip.h): item b, frame t at b * a_item_stride + t * lda_h halves, rows may overlap
+  const bool framed = p.a_item_stride != 0;
+  RADMMM_REQUIRE(!framed || (p.a_item_stride > 0 && p.a_item_stride % 8 == 0 && p.taps == 1 && !d->extra_tap && !p.a_mask_mode &&
+                             d->nprod != 2 && d->lda_h > 0),
+                 "rowgemm_h3: a_item_stride (halves, %% 8 == 0) needs one tap, no extra segment, a_mask_mode 0 and nprod 3 or 1");
+  RADMMM_REQUIRE(d->lda_h % 8 == 0 && d->ldb_h % 8 == 0 && (framed || d->lda_h >= p.K) && d->ldb_h >= p.K && d->b_tap_stride_h % 8 == 0,
                  "rowgemm_h3: split operands need ld %% 8 == 0 and ld >= K");
   RADMMM_REQUIRE(aligned16(d->Ah) && aligned16(d->Al) && aligned16(d->Bh) && aligned16(d->Bl),
                  "rowgemm_h3: split operands must be 16B aligned");
@@ -166,7 +170,8 @@ int plan_rowgemm_h3(const radmmm_rowgemm_h3_desc* d, h3_plan* pl) {
   RADMMM_REQUIRE(!d->extra_tap || (d->extra_a_rows >= p.M && p.taps >= 1 && !p.a_mask_mode),
                  "rowgemm_h3: the extra K segment needs extra_a_rows >= M (second matrix behind the first) and a_mask_mode 0");
   const int ntaps = p.taps + (d->extra_tap ? 1 : 0);
-  const long long a_bytes = ((long long)p.M + (d->extra_tap ? d->extra_a_rows : 0)) * d->lda_h * 2;
+  const long long a_bytes = framed ? ((long long)(p.M / p.T - 1) * p.a_item_stride + (long long)(p.T - 1) * d->lda_h + p.K) * 2
+                                   : ((long long)p.M + (d->extra_tap ? d->extra_a_rows : 0)) * d->lda_h * 2;
   const long long b_bytes = ((long long)(ntaps - 1) * d->b_tap_stride_h + (long long)p.N * d->ldb_h) * 2;
   RADMMM_REQUIRE(a_bytes < 0x7fffffffLL && b_bytes < 0x7fffffffLL, "rowgemm_h3: operand >= 2 GiB");
   pl->a_bytes = (int)a_bytes;

@@ -628,7 +628,9 @@ __global__ __launch_bounds__(256, 1) void rowgemm_h3d_kernel(const radmmm_rowgem
       const int b = r / p.T;
       a_t[k] = r - b * p.T;
       a_lim[k] = (p.a_mask_mode && p.lens) ? p.lens[b] : p.T;
-      a_base[k] = ((b * p.T + a_t[k]) * q.lda_h + d_chunk * 8) * 2;      // this lane's row at shift 0
+      // this lane's row at shift 0 (framed form: an item's rows start a_item_stride halves apart instead of T * lda_h;
+      // 32-bit is enough because plan_rowgemm_h3 keeps a_bytes, which covers every row below M, under 2 GiB)
+      a_base[k] = (b * (p.a_item_stride ? (int)p.a_item_stride : p.T * q.lda_h) + a_t[k] * q.lda_h + d_chunk * 8) * 2;
     }
     a_dst[k] = real ? a_isl[k] * G::A_BYTES + j * 1024 : -1;
     a_vo[k] = OOB;

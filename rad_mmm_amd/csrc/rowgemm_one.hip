@@ -43,7 +43,14 @@ __global__ __launch_bounds__(256, 1) void rowgemm_one_kernel(const radmmm_rowgem
       const int b = r / p.T;
       ok = r - b * p.T < p.lens[b];
     }
-    a_vo[k] = ok ? (r * q.lda_h + d_chunk * 8) * 2 : OOB;
+    int row_off = r * q.lda_h;
+    // framed form: item b, frame t at b * a_item_stride + t * lda_h.  32-bit: plan_rowgemm_h3 keeps a_bytes, which covers
+    // every row r < M, below 2 GiB; for r >= M the value may wrap and is discarded (ok is false)
+    if (p.a_item_stride) {
+      const int b = r / p.T;
+      row_off = b * (int)p.a_item_stride + (r - b * p.T) * q.lda_h;
+    }
+    a_vo[k] = ok ? (row_off + d_chunk * 8) * 2 : OOB;
     a_dst[k] = G::A_BASE + a_isl[k] * G::A_PLANE + j * 1024;
   }
 #pragma unroll

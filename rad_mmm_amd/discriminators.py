@@ -37,22 +37,34 @@ x[b, 0, h, w] = audio[b, h * p + w], AvgPool1d(4, 2, padding=2) between the mult
 factor 2 in the feature loss.  With len_ratios, item b counts ceil(len_ratios[b] * H_l) rows of a feature map and
 ceil(len_ratios[b] * H_post * p) flattened positions of a member's output, the torch expression evaluated on the device in
 len_ratios' dtype.  The reference's own mask only broadcasts when some ratio is 1; this module is defined by the formula for
-any ratios in [0, 1] (a count is read clamped to its size).  fp32 only.
+any ratios in [0, 1] (a count is read clamped to its size).  fp32 only: parameters and audio are float32.
+
+MultiPeriodDiscriminator.precision = "h3" (opt-in) keeps all of the above and moves the four wide convs of every
+member -- forward, data gradient, weight gradient -- to the f16 matrix cores with three split products: csrc/mpd_h3.hip
+writes the fp16 pairs in the passes that form the values, radmmm_rowgemm_h3 reads the padded pair through the same framed
+descriptor, radmmm_wgrad_rm contracts a framed pair with the gradient's pair.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 import warnings
 from typing import List, Optional, Sequence
 
 import torch
 from torch import nn
 
-from ._lib import RadmmmError, check, f32c, fp32_region, lib, ptr, rowgemm, stream
+from . import ops
+from ._lib import RadmmmError, check, f32c, fp32_region, lib, ptr, rowgemm, rowgemm_h3, stream
 from .vocoder import fold_weight_norm
 from .waveglow import _colsum, _wgrad
 
 LRELU_SLOPE = 0.1
+MPD_PRECISIONS = ("fp32", "h3")        # MultiPeriodDiscriminator.precision
+# precision "h3": an activation enters its fp16 pair times _ACT_SCALE (a pair clamps above 60000 / 64 = 937; the lo halves stay
+# normal numbers down to |x| = 2e-3 and the pair's absolute floor is 2^-25 / 64), a weight times ops.W_SCALE
+_ACT_SCALE = 64.0
+_WGRAD_RM_ROWS = 32                    # radmmm_wgrad_rm contracts at least 32 rows: the producers add zero rows up to it
 _OPERAND_BYTES = 2 ** 31 - 2 ** 16     # the row GEMM's operands and the kernels' matrices stay below 2 GiB
 MSD_KERNELS = (15, 41, 41, 41, 41, 41, 5)
 MSD_STRIDES = (1, 2, 2, 4, 4, 1, 1)
@@ -76,6 +88,40 @@ def _call(name: str, *args) -> None:
 def _gemm(name: str, **kw) -> None:
     _count(name)
     rowgemm(**kw)
+
+
+def _gemm_h3(name: str, **kw) -> None:
+    _count(name)
+    rowgemm_h3(nprod=3, **kw)
+
+
+def _halves(*shape, dev):
+    return torch.empty(*shape, device=dev, dtype=torch.float16), torch.empty(*shape, device=dev, dtype=torch.float16)
+
+
+def _framed_h3(Xp, S, Hin, Cin, st, Wp, Z, H, C, bias=None) -> dict:
+    """_framed on the split pairs: the window of the padded pair Xp (a_item_stride and lda_h count halves), the weights' pair
+    Wp [C][5 * Cin]"""
+    return dict(Ah=Xp[0], Al=Xp[1], lda_h=st * Cin, a_item_stride=(Hin + 4) * Cin, Bh=Wp[0], Bl=Wp[1], ldb_h=5 * Cin, C=Z, ldc=C,
+                M=S * H, N=C, K=5 * Cin, T=H, bias=bias, acc_scale=1.0 / (_ACT_SCALE * ops.W_SCALE))
+
+
+def _dgrad_h3(dZp, S, H, C, Cin, Tp, dF, g_scale) -> dict:
+    """the data gradient's GEMM on pairs: dZp [S * H][C] times the transposed weights' pair Tp [5 * Cin][C]"""
+    return dict(Ah=dZp[0], Al=dZp[1], lda_h=C, Bh=Tp[0], Bl=Tp[1], ldb_h=C, C=dF, ldc=5 * Cin, M=S * H, N=5 * Cin, K=C, T=H,
+                acc_scale=1.0 / (g_scale * ops.W_SCALE))
+
+
+def auto_grad_scale(B: int, T: int, period: int) -> float:
+    """the automatic gradient scale of one DiscriminatorP in precision "h3": 16 times the smallest power of two at or above
+    the number of its outputs B * H_post * p, from host sizes alone.  The adversarial terms are means over (at most) that
+    many outputs, so the scaled seed 2 (1 - d) g / n is of order 16 .. 64: twelve octaves of fp16 above it for what the
+    convs' gains and a ragged batch's smaller normaliser add, and the pairs' absolute floor 2^-25 nine decimal orders below."""
+    p = int(period)
+    h = (int(T) + p - 1) // p
+    for st in (3, 3, 3, 3, 1):
+        h = (h - 1) // st + 1
+    return 16.0 * float(2 ** max(0, (max(1, int(B) * h * p) - 1).bit_length()))
 
 
 def _framed(Xin, S, Hin, Cin, st, W, Z, H, C, bias=None) -> dict:
@@ -118,7 +164,15 @@ class _Member:
         w = dw.view(C, 5, Cin).permute(0, 2, 1)
         return w.unsqueeze(-1) if self.wtail else w, _colsum(dZ, C, R, C)
 
-    def conv_dgrad(self, l: int, dZ, W, add, Xin, n: int):
+    def post_dgrad(self, dOut, W, add, Xin, n: int, need32: bool):
+        """conv_post's data gradient on n sequences (+ add, times the leaky-relu derivative) -> dZ of the last conv.  need32:
+        is the fp32 array wanted (a weight gradient reads it)?  Only a precision that also keeps a pair asks"""
+        dZ = dOut.new_empty(n * self.H[-1], self.C[-1])
+        _call("mpd_conv_post_dgrad", ptr(dOut), ptr(W), ptr(add), ptr(Xin), ptr(dZ), n // self.p, self.p, self.H[-1], self.C[-1],
+              LRELU_SLOPE)
+        return dZ
+
+    def conv_dgrad(self, l: int, dZ, W, add, Xin, n: int, need32: bool = True):
         """dense 5-tap conv l on n sequences: the b_layout-1 GEMM, then mpd_unframe (+ add, times the leaky-relu derivative)"""
         C, H, Cin, Hin, R = self.C[l], self.H[l], self.C[l - 1], self.H[l - 1], n * self.H[l]
         dF = dZ.new_empty(R, 5 * Cin)
@@ -140,8 +194,12 @@ class _Geometry(_Member):
     """shapes of one DiscriminatorP for B items of T samples"""
     family, K0, taps0, wtail, period_axis = "mpd", 8, 5, (1,), True
 
-    def __init__(self, period: int, channels: Sequence[int], B: int, T: int):
+    def __init__(self, period: int, channels: Sequence[int], B: int, T: int, h3: Optional[dict] = None):
+        """h3: None (fp32), or the state of precision "h3": grad_scale (None: auto_grad_scale), flag (the device int32 [1]
+        saturation word), cache / keys (the owner's split weight copies and its parameters' versions per conv).  A plan
+        query passes an empty dict"""
         p = self.p = int(period)
+        self.h3 = h3
         self.B, self.T = B, T
         n_pad = (p - T % p) % p
         if T <= n_pad:
@@ -160,10 +218,53 @@ class _Geometry(_Member):
             raise ValueError(f"DiscriminatorP(period {p}): {B} x {T} samples need a GEMM operand of {4 * worst} bytes, above "
                              f"the row GEMM's limit of {_OPERAND_BYTES}: split the batch")
         self.lead = (B, p)
+        # per conv (conv_post last) how it runs and why: the ONE decision the launches and precision_plan() share
+        if h3 is None:
+            self.plan = [("fp32", "precision 'fp32'")] * 6
+        else:
+            self.plan = [("fp32", "one input channel: an 8-column frame matrix, not a split operand")]
+            for l in range(1, 5):
+                ok = int(lib.radmmm_mpdh3_plan(self.S, self.H[l - 1], self.C[l - 1], self.H[l], self.C[l], self.stride[l]))
+                self.plan.append(("h3", "") if ok == 1 else ("fp32", lib.radmmm_last_error().decode()))
+            self.plan.append(("fp32", "one output channel: a wave reduction, not a GEMM"))
+            self.g_scale = float(h3["grad_scale"]) if h3.get("grad_scale") is not None else auto_grad_scale(B, T, p)
+        self.mode = [m for m, _ in self.plan]
+        self.h3w: dict = {}                                       # conv -> (Wh, Wl, Th, Tl) of the pass that ran forward
+
+    def h3_descriptors(self, n: Optional[int] = None) -> List[dict]:
+        """every split GEMM descriptor an "h3" step over n sequences (default: all) builds, with the integer 256 for each
+        address: what rowgemm_h3_plan is asked in the tests"""
+        a, out = 256, []
+        n = self.S if n is None else n
+        for l in range(1, 5):
+            if self.mode[l] != "h3":
+                continue
+            C, H, Cin, Hin, st = self.C[l], self.H[l], self.C[l - 1], self.H[l - 1], self.stride[l]
+            out.append(_framed_h3((a, a), n, Hin, Cin, st, (a, a), a, H, C, a))
+            out.append(_dgrad_h3((a, a), n, H, C, Cin, (a, a), a, self.g_scale))
+        return out
 
     def map_sizes(self) -> List[int]:
         """what len_ratios is multiplied with: the rows of the six maps, then the flattened length of the output"""
         return self.H + [self.H[4], self.H[4] * self.p]
+
+    def _split_weights(self, l: int, w: torch.Tensor):
+        """the pair of conv l's packed weight [C][5 * Cin] times ops.W_SCALE and of its transpose [5 * Cin][C]: made once per
+        parameter version and kept with the owner, so a step after optimizer.step() splits again and two calls without one
+        share the copies.  The key is (data_ptr, _version) of the conv's raw parameters, as HiFiGANGenerator._fold's: a write
+        that moves neither (through .data or a raw pointer) would leave stale copies; FlatAdam.step advances the version"""
+        h3 = self.h3
+        key = (h3["keys"][l], w.device)
+        ent = h3["cache"].get(l)
+        if ent is None or ent[0] != key:
+            C, K = self.C[l], 5 * self.C[l - 1]
+            Wp = w.detach().float()[..., 0].permute(0, 2, 1).reshape(C, K).contiguous()
+            _count("split_w")
+            Wh, Wl = ops.split_f16(Wp, K, ops.W_SCALE, K, sat_flag=h3["flag"])
+            _count("transpose_w")
+            Th, Tl = ops.transpose_split(Wh.view(1, C, K), Wl.view(1, C, K), C, K, C)
+            ent = h3["cache"][l] = (key, Wh, Wl, Th[0], Tl[0])
+        return ent[1:]
 
     def terms_tail(self, l: int):
         return (int(l < 5),)                                      # a padded map, or the output
@@ -180,6 +281,13 @@ class _Geometry(_Member):
         W0[:, :5] = w0.reshape(self.C[0], 5)
         out.append(W0)
         for l in range(1, 5):
+            # "h3": its pairs instead.  The hi half only fills the tape's slot; the backward takes the four copies from
+            # self.h3w, which holds because a geometry is built per call and its node alone keeps it (ctx.geos).  The
+            # copies are the owner's cached tensors, never written again: a later version gets new tensors
+            if self.mode[l] == "h3":
+                self.h3w[l] = self._split_weights(l, ws[2 * l])
+                out.append(self.h3w[l][0])
+                continue
             out.append(ws[2 * l].detach().float()[..., 0].permute(0, 2, 1).reshape(self.C[l], 5 * self.C[l - 1]).contiguous())
         out.append(ws[10].detach().float().reshape(self.C[4], 3).t().contiguous())
         return out
@@ -196,17 +304,24 @@ class _Geometry(_Member):
         bias = [f32c(ws[2 * l + 1].detach()) for l in range(6)]
         F1 = empty(S * self.H[0], 8)
         _call("mpd_fold_frame", ptr(y), ptr(y_hat), ldy, ptr(F1), B, T, p, self.H0, self.H[0])
-        X = []
+        X, Xp = [], None                                          # Xp: the pair of the last map, when an "h3" conv reads it
         for l in range(5):
             C, H = self.C[l], self.H[l]
             Z = empty(S * H, C)
             if l == 0:
                 _gemm("conv", A=F1, lda=8, B=W[0], ldb=8, C=Z, ldc=C, M=S * H, N=C, K=8, T=H, bias=bias[0])
+            elif self.mode[l] == "h3":
+                _gemm_h3("conv_h3", **_framed_h3(Xp, S, self.H[l - 1], self.C[l - 1], self.stride[l], self.h3w[l], Z, H, C, bias[l]))
             else:
                 Cin, Hin, st = self.C[l - 1], self.H[l - 1], self.stride[l]
                 _gemm("conv", **_framed(X[l - 1], S, Hin, Cin, st, W[l], Z, H, C, bias[l]))
             Xl = empty(S, H + 4, C)
-            _call("mpd_repad", ptr(Z), C, ptr(Xl), S, H, C, LRELU_SLOPE)
+            if l < 4 and self.mode[l + 1] == "h3":
+                Xp = _halves(S, H + 4, C, dev=dev)
+                _call("mpdh3_repad", ptr(Z), C, ptr(Xl), ptr(Xp[0]), ptr(Xp[1]), S, H, C, LRELU_SLOPE, _ACT_SCALE, ptr(self.h3["flag"]))
+            else:
+                Xp = None
+                _call("mpd_repad", ptr(Z), C, ptr(Xl), S, H, C, LRELU_SLOPE)
             X.append(Xl)
         out = empty(2 * B, self.H[4], p)
         _call("mpd_conv_post", ptr(X[4]), ptr(W[5]), ptr(bias[5]), ptr(out), 2 * B, p, self.H[4], self.C[4])
@@ -217,6 +332,64 @@ class _Geometry(_Member):
         ga = dF.new_empty(self.B, self.T)
         _call("mpd_unfold_audio", ptr(dF), ptr(ga), self.T, self.B, self.T, self.p, self.H0, self.H[0], j)
         return ga
+
+    # ---- precision "h3": the gradient of an "h3" conv's output is (dZ fp32 or None, dZh, dZl), the pair times g_scale with
+    # zero rows up to radmmm_wgrad_rm's minimum; a producer writes it in the pass that forms the gradient
+    def _dz_h3(self, l: int, n: int, like, need32: bool):
+        R, C = n * self.H[l], self.C[l]
+        pair = _halves(max(R, _WGRAD_RM_ROWS), C, dev=like.device)
+        return (like.new_empty(R, C) if need32 else None), pair[0], pair[1]
+
+    def post_dgrad(self, dOut, W, add, Xin, n: int, need32: bool):
+        if self.mode[4] != "h3":
+            return super().post_dgrad(dOut, W, add, Xin, n, need32)
+        dZ = self._dz_h3(4, n, dOut, need32)
+        _call("mpdh3_conv_post_dgrad", ptr(dOut), ptr(W), ptr(add), ptr(Xin), ptr(dZ[0]), ptr(dZ[1]), ptr(dZ[2]), self.C[4],
+              n // self.p, self.p, self.H[4], self.C[4], LRELU_SLOPE, _WGRAD_RM_ROWS, self.g_scale, ptr(self.h3["flag"]))
+        return dZ
+
+    def conv_wgrad(self, l: int, dZ, Xin, n: int):
+        """an "h3" conv: the windows cut straight into a pair (no fp32 frames), contracted with the dZ pair by radmmm_wgrad_rm
+        at one tap over max(R, 32) rows as ONE utterance; the split-K slabs are added in a fixed order"""
+        if self.mode[l] != "h3":
+            return super().conv_wgrad(l, dZ, Xin, n)
+        C, H, Cin, Hin, R = self.C[l], self.H[l], self.C[l - 1], self.H[l - 1], n * self.H[l]
+        Rp, K = max(R, _WGRAD_RM_ROWS), 5 * Cin
+        Fp = _halves(Rp, K, dev=Xin.device)
+        _call("mpdh3_frame", ptr(Xin), ptr(Fp[0]), ptr(Fp[1]), K, n, Hin, Cin, H, self.stride[l], _WGRAD_RM_ROWS, _ACT_SCALE,
+              ptr(self.h3["flag"]))
+        _count("wgrad_rm")
+        P = ops.wgrad_rm_slabs((dZ[1], dZ[2]), Fp, 1, Rp, C, K, 1, 1, 1.0 / (self.g_scale * _ACT_SCALE))
+        del Fp
+        if P.shape[0] > 1:
+            dw = P.new_empty(C * K)
+            _call("colsum_final", ptr(P), ptr(dw), P.shape[0], C * K)
+        else:
+            dw = P
+        _count("colsum")
+        w = dw.view(C, 5, Cin).permute(0, 2, 1)
+        return w.unsqueeze(-1), _colsum(dZ[0], C, R, C)
+
+    def conv_dgrad(self, l: int, dZ, W, add, Xin, n: int, need32: bool = True):
+        """an "h3" conv: the dZ pair against the transposed weights' pair, then the unframing -- which writes the pair of the
+        conv below when that one is "h3" too"""
+        if self.mode[l] != "h3" and self.mode[l - 1] != "h3":
+            return super().conv_dgrad(l, dZ, W, add, Xin, n)
+        C, H, Cin, Hin, R = self.C[l], self.H[l], self.C[l - 1], self.H[l - 1], n * self.H[l]
+        if self.mode[l] != "h3":
+            dF = dZ.new_empty(R, 5 * Cin)
+            _gemm("dgrad", A=dZ, lda=C, B=W, ldb=5 * Cin, b_layout=1, C=dF, ldc=5 * Cin, M=R, N=5 * Cin, K=C, T=H)
+        else:
+            dF = Xin.new_empty(R, 5 * Cin)
+            _gemm_h3("dgrad_h3", **_dgrad_h3(dZ[1:], n, H, C, Cin, self.h3w[l][2:], dF, self.g_scale))
+        if self.mode[l - 1] != "h3":
+            dX = dF.new_empty(n * Hin, Cin)
+            _call("mpd_unframe", ptr(dF), ptr(add), ptr(Xin), ptr(dX), n, Hin, Cin, H, self.stride[l], LRELU_SLOPE)
+            return dX
+        dX = self._dz_h3(l - 1, n, dF, need32)
+        _call("mpdh3_unframe", ptr(dF), ptr(add), ptr(Xin), ptr(dX[0]), ptr(dX[1]), ptr(dX[2]), Cin, n, Hin, Cin, H, self.stride[l],
+              LRELU_SLOPE, _WGRAD_RM_ROWS, self.g_scale, ptr(self.h3["flag"]))
+        return dX
 
 
 class _GeometryS(_Member):
@@ -318,7 +491,7 @@ class _GeometryS(_Member):
         _count("colsum")
         return dw.view(self.C[l], k, cig).permute(0, 2, 1), _colsum(dZ, self.C[l], n * Hout, self.C[l])
 
-    def conv_dgrad(self, l: int, dZ, W, add, Xin, n: int):
+    def conv_dgrad(self, l: int, dZ, W, add, Xin, n: int, need32: bool = True):
         if l == 6:
             return super().conv_dgrad(l, dZ, W, add, Xin, n)
         dims = self._gconv_dims(l)
@@ -374,14 +547,13 @@ def _walk(g: _Member, tape: dict, W, s0: int, n: int, dOut, add, want_w: Sequenc
         grads[2 * nl], grads[2 * nl + 1] = dw[:cols - 1].view(3, C[-1]).t().reshape(1, C[-1], 3, *g.wtail), dw[cols - 1:]
     if not below(nl):
         return grads, g_audio
-    dZ = dOut.new_empty(n * H[-1], C[-1])
-    _call("mpd_conv_post_dgrad", ptr(dOut), ptr(W[nl]), ptr(add[-1]), ptr(X[-1]), ptr(dZ), n // p, p, H[-1], C[-1], LRELU_SLOPE)
+    dZ = g.post_dgrad(dOut, W[nl], add[-1], X[-1], n, want_w[nl - 1])
     for l in range(nl - 1, 0, -1):
         if want_w[l]:
             grads[2 * l], grads[2 * l + 1] = g.conv_wgrad(l, dZ, X[l - 1], n)
         if not below(l):
             return grads, g_audio
-        dZ = g.conv_dgrad(l, dZ, W[l], add[l - 1], X[l - 1], n)
+        dZ = g.conv_dgrad(l, dZ, W[l], add[l - 1], X[l - 1], n, want_w[l - 1])
     K, R = g.K0, n * H[0]
     if want_w[0]:
         _count("wgrad")
@@ -569,10 +741,11 @@ def _counts(len_ratios, geos: Sequence[_Member], B: int, dev: torch.device) -> O
 
 
 @fp32_region
-def _run(discs: Sequence["_Discriminator"], mode: str, y, y_hat, len_ratios):
+def _run(discs: Sequence["_Discriminator"], mode: str, y, y_hat, len_ratios, h3: Optional[dict] = None):
     y2, yh2 = _audio(y, y_hat)
     B, T = y2.shape
-    geos = discs[0]._geometries(discs, B, T)                              # every refusal comes before the first launch
+    # every refusal comes before the first launch
+    geos = discs[0]._geometries(discs, B, T) if h3 is None else discs[0]._geometries(discs, B, T, h3)
     for d in discs:
         if any(t.dtype != torch.float32 for t in (*d.parameters(), *d.buffers())):
             raise RadmmmError(f"{d._multi} is fp32 only")
@@ -707,29 +880,112 @@ class DiscriminatorP(_Discriminator):
             cin = c
         self.convs = nn.ModuleList(convs)
         self.conv_post = _wn(nn.Conv2d(cin, 1, (3, 1), 1, padding=(1, 0)))
+        self._h3_cache: dict = {}                   # precision "h3": conv -> (parameter versions, the weight's split copies)
 
     @staticmethod
-    def _geometries(discs, B: int, T: int):
-        return [_Geometry(d.period, d.channels, B, T) for d in discs]
+    def _geometries(discs, B: int, T: int, h3: Optional[dict] = None):
+        """h3: None, or what MultiPeriodDiscriminator hands down for precision "h3" (grad_scale, flag); every member adds its
+        own cache of split weights and the versions of its convs' parameters"""
+        if h3 is None:
+            return [_Geometry(d.period, d.channels, B, T) for d in discs]
+        return [_Geometry(d.period, d.channels, B, T,
+                          dict(h3, cache=d._h3_cache, keys=[tuple((p.data_ptr(), p._version) for p in m.parameters()) for m in d.convs]))
+                for d in discs]
+
+
+def _check_precision(name) -> str:
+    if name not in MPD_PRECISIONS:
+        raise ValueError(f"MultiPeriodDiscriminator: precision {name!r} is none of {MPD_PRECISIONS}")
+    return name
 
 
 class MultiPeriodDiscriminator(_MultiDiscriminator):
     """MultiPeriodDiscriminator of hifigan_models.py:286-310; state_dict keys discriminators.N.convs.M.{weight_g, weight_v,
-    bias} and discriminators.N.conv_post.*, so the `mpd` entry of an upstream checkpoint loads with load_state_dict."""
+    bias} and discriminators.N.conv_post.*, so the `mpd` entry of an upstream checkpoint loads with load_state_dict.
+
+    precision: "fp32" (default) or "h3"; forward, discriminator_loss and generator_losses take a per-call precision= that
+    overrides it, and any other name raises ValueError before any device work.  In "h3" convs.1 .. convs.4 of every member
+    run forward, data gradient and weight gradient on the f16 matrix cores with three split products (radmmm_rowgemm_h3,
+    radmmm_wgrad_rm; fp32-class accuracy): the leaky-relu pass writes the next conv's framed fp16 pair beside the fp32 map,
+    the backward's unframing writes the gradient's pair, the weight gradient's windows are cut straight into a pair, and the
+    weights' split copies are kept per parameter version.  convs.0, conv_post, the norm folds, the bias sums, the loss
+    reductions and every feature map stay fp32; a conv the split kernels refuse runs its fp32 path in all three passes
+    (precision_plan() says which and why).  Training, eval mode and no_grad all use the mode.  Gradients enter the pairs times
+    grad_scale -- None: auto_grad_scale(B, T, period) per member, from host sizes; or a power of two -- and .grad and the
+    audio gradient hold the true values.  A pair that clamps at fp16's range (a gradient or a forward activation) raises
+    saturation_flag(), the device word that `FlatAdam.step(skip=...)` takes; grad_saturated() reads and clears it, and
+    nothing else waits for the device.  A checkpoint does not store the mode."""
 
     def __init__(self, periods: Sequence[int] = (2, 3, 5, 7, 11), channels: Sequence[int] = (32, 128, 512, 1024, 1024)):
         super().__init__()
         self.discriminators = nn.ModuleList(DiscriminatorP(p, channels) for p in periods)
+        self.precision = "fp32"
+        self.grad_scale = None                      # precision "h3": None (auto_grad_scale per member) or a power of two
+        self._sat_flag = None                       # device int32 [1]: OR-ed by the pair producers of an "h3" call
+
+    def _h3(self, precision) -> Optional[dict]:
+        """what a call in `precision` (None: the attribute) hands to the geometries; None for "fp32\""""
+        if _check_precision(self.precision if precision is None else precision) == "fp32":
+            return None
+        g = self.grad_scale
+        if g is not None:
+            g = float(g)
+            if not (g > 0 and g < float("inf") and 2.0 ** round(math.log2(g)) == g):
+                raise ValueError(f"grad_scale {self.grad_scale!r} (precision 'h3'): None or a power of two")
+        return {"grad_scale": g, "flag": self.saturation_flag()}
+
+    def saturation_flag(self) -> torch.Tensor:
+        """the device int32 [1] word a clamped pair of an "h3" call raises (created zeroed), for a guard that stays on the
+        device: `FlatAdam.step(skip=mpd.saturation_flag())`.  Clearing it stays with grad_saturated()."""
+        dev = next(self.parameters()).device
+        if self._sat_flag is None or self._sat_flag.device != dev:
+            self._sat_flag = torch.zeros(1, device=dev, dtype=torch.int32)
+        return self._sat_flag
+
+    def grad_saturated(self) -> bool:
+        """True when a pair of an "h3" call clamped since the last call of this method: reads the device and clears the
+        word.  The step's gradients are then not to be used; lower grad_scale (or find the activation that left fp16's range)."""
+        if self._sat_flag is None:
+            return False
+        hit = bool(int(self._sat_flag.item()) & 1)
+        self._sat_flag.zero_()
+        return hit
+
+    def precision_plan(self, precision: Optional[str] = None, B: Optional[int] = None, T: Optional[int] = None) -> list:
+        """per member a dict conv name -> (mode, reason) for a batch of B x T samples (default 1 x 8192): ("h3", "") where the
+        three passes reach the split kernels, else ("fp32", why).  Host only: the launches take the same decision from the
+        same function (radmmm_mpdh3_plan, which asks radmmm_rowgemm_h3's own planner)."""
+        name = _check_precision(self.precision if precision is None else precision)
+        B, T = (1 if B is None else int(B)), (8192 if T is None else int(T))
+        names = [f"convs.{l}" for l in range(5)] + ["conv_post"]
+        return [dict(zip(names, _Geometry(d.period, d.channels, B, T, None if name == "fp32" else {}).plan))
+                for d in self.discriminators]
+
+    def forward(self, y, y_hat, precision: Optional[str] = None):
+        return _run(list(self.discriminators), "views", y, y_hat, None, self._h3(precision))
+
+    def discriminator_loss(self, y, y_hat, len_ratios=None, precision: Optional[str] = None):
+        return _run(list(self.discriminators), "disc", y, y_hat, len_ratios, self._h3(precision))
+
+    def generator_losses(self, y, y_hat, len_ratios=None, precision: Optional[str] = None):
+        return _run(list(self.discriminators), "gen", y, y_hat, len_ratios, self._h3(precision))
+
+    forward.__doc__ = _MultiDiscriminator.forward.__doc__
+    discriminator_loss.__doc__ = _MultiDiscriminator.discriminator_loss.__doc__
+    generator_losses.__doc__ = _MultiDiscriminator.generator_losses.__doc__
 
 
-def load_mpd(path: str, device="cuda", **model_kwargs) -> MultiPeriodDiscriminator:
+def load_mpd(path: str, device="cuda", precision: str = "fp32", **model_kwargs) -> MultiPeriodDiscriminator:
     """the `mpd` entry of an upstream do_* checkpoint -> MultiPeriodDiscriminator on `device`; model_kwargs go to the
-    constructor (a checkpoint of a narrow model)"""
+    constructor (a checkpoint of a narrow model).  precision: the model's mode (the file does not store one); a bad name
+    raises before the file is looked at"""
+    _check_precision(precision)
     ckpt = torch.load(path, map_location="cpu")
     if "mpd" not in ckpt:
         raise KeyError(f"{path} has no 'mpd' entry (keys: {sorted(ckpt)[:8]})")
     mpd = MultiPeriodDiscriminator(**model_kwargs)
     mpd.load_state_dict(ckpt["mpd"])
+    mpd.precision = precision
     return mpd.to(device)
 
 

@@ -10,6 +10,7 @@ from typing import Dict, Optional
 
 import torch
 
+from .discriminators import _check_precision
 from .mel_loss import MelSpectrogramLoss
 from .optim import FlatAdam
 from .vocoder import HiFiGANGenerator, _lens_arg
@@ -22,14 +23,23 @@ class HiFiGANTrainingStep:
     0.01, torch's) and `ExponentialLR(gamma=0.999)` per epoch.  mel_loss: None builds MelSpectrogramLoss() (the default
     TacotronSTFT) on the generator's device; its hop must be the generator's.  stft_loss: None leaves the two spectral terms
     out of the generator's loss.  clip: each optimizer clips its own global gradient norm to it (a total that is not finite
-    skips that optimizer's step on the device)."""
+    skips that optimizer's step on the device).  mpd_precision: None leaves the multi-period discriminator's mode as the
+    model has it ("fp32" unless it was set, e.g. by load_mpd(path, precision="h3")); "fp32" or "h3" sets it
+    (MultiPeriodDiscriminator.precision; a checkpoint does not store it).  In "h3" the discriminator's saturation word is the
+    `skip` of BOTH optimizers -- the audio gradient of the G side flows through the same fp16 pairs -- so a step in which a
+    pair clamped changes no parameter, moment or step count, without a device -> host read; the word stays raised until the
+    caller reads it with mpd.grad_saturated() (and lowers mpd.grad_scale)."""
 
     def __init__(self, generator: HiFiGANGenerator, mpd, msd, stft_loss=None, mel_loss=None, lr: float = 2e-4,
                  betas=(0.8, 0.99), weight_decay: float = 0.01, lr_decay: float = 0.999, mel_weight: float = 45.0,
-                 clip: Optional[float] = None):
+                 clip: Optional[float] = None, mpd_precision: Optional[str] = None):
+        if mpd_precision is not None:
+            _check_precision(mpd_precision)
         dev = next(generator.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("HiFiGANTrainingStep: move the modules to the GPU first (there is no CPU path)")
+        if mpd_precision is not None:
+            mpd.precision = mpd_precision
         self.generator, self.mpd, self.msd = generator.train(), mpd.train(), msd.train()
         self.stft_loss = stft_loss
         self.mel_loss = mel_loss if mel_loss is not None else MelSpectrogramLoss().to(dev)
@@ -48,7 +58,10 @@ class HiFiGANTrainingStep:
     def _optim_step(self, opt: FlatAdam) -> None:
         if self.clip is not None:
             opt.clip_grad_norm(self.clip)
-        opt.step()
+        if getattr(self.mpd, "precision", "fp32") == "h3":      # a clamped fp16 pair of the discriminator makes the step a no-op, on the device
+            opt.step(skip=self.mpd.saturation_flag())
+        else:
+            opt.step()
 
     def training_step(self, mel: torch.Tensor, lens, audio: torch.Tensor) -> Dict[str, torch.Tensor]:
         """mel [B, 80, T], lens in frames (host: no synchronisation; or device), audio [B, 1, T * hop] -> the terms of both

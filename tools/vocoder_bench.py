@@ -7,6 +7,8 @@
     python tools/vocoder_bench.py --stft-loss [--iters 5] [--warmup 2] [--out profiles/stft_loss.json]
     python tools/vocoder_bench.py --mel-loss [--iters 5] [--warmup 2] [--out profiles/mel_loss.json]
     python tools/vocoder_bench.py --mpd [--iters 5] [--warmup 2] [--out profiles/mpd.json]
+    python tools/vocoder_bench.py --mpd --precision h3 [--out profiles/mpd_h3.json]
+    python tools/vocoder_bench.py --gan-step --mpd-precision h3 [--out profiles/mpd_h3.json]
     python tools/vocoder_bench.py --msd [--iters 5] [--warmup 2] [--out profiles/msd.json]
     python tools/vocoder_bench.py --gan-step [--iters 5] [--warmup 2] [--out profiles/hifigan_gan_step.json]
 
@@ -52,6 +54,14 @@ autograd (real and generated audio stacked in one pass, vectorised masks, no hos
 losses of that step: the D step the discriminator loss, the G side the feature and generator losses.  Per form and
 step: median ms of --iters runs after --warmup, device launches, host synchronisations, peak allocated memory.  The JSON
 also goes to --out (profiles/mpd.json).
+
+--mpd --precision h3: MultiPeriodDiscriminator.precision "h3" (leg b) against "fp32" (leg a: the code path, launches and
+bits the module had before the mode existed) on the same batches, order a b b a, one fresh process per leg, median of
+--iters after --warmup: per leg and step both runs' ms, their spread, launches, host synchronisations, peak allocated
+memory, and for "h3" the relative L2 of its gradients against the fp32 mode's, to profiles/mpd_h3.json.  With
+--d-step-only: the "h3" D step at 32 x 8192 alone, the workload of profiles/mpd_h3_d_step_kernel_stats.csv.
+--gan-step --mpd-precision h3: HiFiGANTrainingStep(mpd_precision="h3") against "fp32" in the same way, added to that file
+under "gan_step".
 
 --msd: the same for the multi-scale discriminator (the reference's widths and groups, training mode) against stock torch
 with conv1d(groups=), to profiles/msd.json; --msd --d-step-only runs the module's D step at 32 x 8192 alone, the workload
@@ -635,6 +645,174 @@ def disc_bench(args, dev, mpd, stock, metric, note):
     print(json.dumps(res))
 
 
+def _mpd_batch(B, dev, g):
+    T = 8192
+    ratios = (torch.linspace(T // 3, T, B).round() / T).to(dev)
+    y = (torch.rand(B, 1, T, generator=g) * 2 - 1).to(dev)
+    y_hat = (y.cpu() + 0.3 * torch.randn(B, 1, T, generator=g)).clamp(-1, 1).to(dev)
+    return y, y_hat, ratios
+
+
+def mpd_leg(args, dev):
+    """one leg of --mpd --precision h3 in this process: leg a is precision "fp32" (the launches and bits of the module
+    before the mode existed), leg b precision "h3"; one JSON line"""
+    from rad_mmm_amd.discriminators import MultiPeriodDiscriminator
+    torch.manual_seed(3)
+    mpd = MultiPeriodDiscriminator().to(dev).train()
+    mpd.precision = "fp32" if args.leg == "a" else "h3"
+    res = {"leg": args.leg, "precision": mpd.precision, "device": torch.cuda.get_device_name(0), "shapes": {}}
+    g = torch.Generator().manual_seed(13)
+    for B in (16, 32):
+        y, y_hat, ratios = _mpd_batch(B, dev, g)
+
+        def d_step(**kw):
+            mpd.zero_grad(set_to_none=True)
+            loss = mpd.discriminator_loss(y, y_hat, ratios, **kw)[0]
+            loss.backward()
+            return loss.detach()
+
+        def g_side(**kw):
+            p = y_hat.detach().requires_grad_(True)
+            fm, gen = mpd.generator_losses(y, p, ratios, **kw)
+            (fm + gen).backward()
+            return fm.detach(), gen.detach(), p.grad
+        row = {}
+        for name, step, frozen in (("d_step", d_step, False), ("g_side", g_side, True)):
+            for q in mpd.parameters():
+                q.requires_grad_(not frozen)
+            ms = timed(step, args.iters, args.warmup)
+            launches, syncs = count_launches_and_syncs(step)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            got = step()
+            torch.cuda.synchronize()
+            row[name] = {"ms": round(ms, 3), "launches": launches, "host_syncs": syncs,
+                         "peak_allocated_mb": round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)}
+            if name == "d_step":
+                row[name]["loss"] = float(got)
+                if args.leg == "b":
+                    grads = torch.cat([q.grad.reshape(-1) for q in mpd.parameters()])
+                    d_step(precision="fp32")
+                    ref = torch.cat([q.grad.reshape(-1) for q in mpd.parameters()])
+                    row[name]["param_grad_rel_l2_vs_fp32"] = float((grads - ref).norm() / ref.norm())
+            else:
+                row[name].update(fm=float(got[0]), gen=float(got[1]))
+                if args.leg == "b":
+                    ref = g_side(precision="fp32")[2]
+                    row[name]["audio_grad_rel_l2_vs_fp32"] = float((got[2] - ref).norm() / ref.norm())
+        if args.leg == "b":
+            row["saturated"] = mpd.grad_saturated()
+            row["plan"] = [[m for m, _ in d.values()] for d in mpd.precision_plan(B=B, T=8192)]
+        res["shapes"][f"B{B}_T8192"] = row
+        print(json.dumps({f"B{B}_T8192": row}), file=sys.stderr, flush=True)
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
+def _abba(args, flags):
+    """legs a b b a, each in a fresh process (this process never opens the GPU) -> the four result lines"""
+    import subprocess
+    runs = []
+    for leg in "abba":
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), *flags, "--leg", leg, "--iters", str(args.iters),
+                              "--warmup", str(args.warmup)], check=True, stdout=subprocess.PIPE, text=True).stdout
+        runs.append(json.loads(out.strip().splitlines()[-1]))
+    return runs
+
+
+def _merge_legs(runs, field, ratio_of):
+    """per shape and leg: the last run's figures, both runs' times, their mean and spread; ratio_of: (step name or None)"""
+    shapes = {}
+    for shape in runs[0]["shapes"]:
+        row = {}
+        for r in runs:
+            e = row.setdefault(r["leg"], {})
+            for name, v in r["shapes"][shape].items():
+                if isinstance(v, dict) and field in v:
+                    d = e.setdefault(name, dict(v, **{field: []}))
+                    d[field].append(v[field])
+                else:
+                    e[name] = v
+        for e in row.values():
+            for d in e.values():
+                if isinstance(d, dict) and field in d:
+                    d[field + "_mean"] = round(sum(d[field]) / len(d[field]), 3)
+                    d[field + "_spread"] = round(max(d[field]) - min(d[field]), 3)
+        for name in ratio_of:
+            a, b = row["a"][name], row["b"][name]
+            b["fp32_over_h3"] = round(a[field + "_mean"] / b[field + "_mean"], 3)
+            b["faster_than_fp32_beyond_the_spread"] = bool(a[field + "_mean"] - b[field + "_mean"] > max(a[field + "_spread"], b[field + "_spread"]))
+        shapes[shape] = {"fp32": row["a"], "h3": row["b"]}
+    return shapes
+
+
+def mpd_h3_bench(args):
+    """--mpd --precision h3: precision "h3" (leg b) against precision "fp32" (leg a), order a b b a"""
+    runs = _abba(args, ["--mpd", "--precision", "h3"])
+    res = {"metric": "mpd_step_ms", "iters": args.iters, "warmup": args.warmup, "device": runs[0]["device"], "order": "a b b a",
+           "note": "one GPU, one fresh process per leg, one session; the reference's widths, ragged len_ratios on the device (the "
+                   "last item full), the batches of profiles/mpd.json; median of iters after warmup.  a: precision 'fp32' -- the "
+                   "code path, launches and bits of the module before the mode existed.  b: precision 'h3'.  d_step: "
+                   "discriminator loss forward + parameter gradients, y_hat detached.  g_side: feature + generator loss forward "
+                   "+ gradient of y_hat, parameters frozen.  ms: both runs of the leg; ms_spread: their difference",
+           "shapes": _merge_legs(runs, "ms", ("d_step", "g_side"))}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
+def gan_step_h3_leg(args, dev):
+    """one leg of --gan-step --mpd-precision h3: HiFiGANTrainingStep with mpd_precision "fp32" (a) or "h3" (b)"""
+    from rad_mmm_amd.discriminators import MultiPeriodDiscriminator, MultiScaleDiscriminator
+    from rad_mmm_amd.mel_loss import MelSpectrogramLoss
+    from rad_mmm_amd.stft_loss import MultiResolutionSTFTLoss
+    from rad_mmm_amd.vocoder_step import HiFiGANTrainingStep
+    gen = HiFiGANGenerator(V1)
+    gen.load_state_dict(random_state(gen, 5, 0.2, 0.6))
+    torch.manual_seed(3)
+    gen, mpd, msd = gen.to(dev).train(), MultiPeriodDiscriminator().to(dev).train(), MultiScaleDiscriminator().to(dev).train()
+    obj = HiFiGANTrainingStep(gen, mpd, msd, stft_loss=MultiResolutionSTFTLoss().to(dev), mel_loss=MelSpectrogramLoss().to(dev),
+                              mpd_precision="fp32" if args.leg == "a" else "h3")
+    res = {"leg": args.leg, "mpd_precision": mpd.precision, "device": torch.cuda.get_device_name(0), "shapes": {}}
+    g = torch.Generator().manual_seed(17)
+    hop = gen.hop
+    for B in (16, 32):
+        T = 32
+        lens = [int(v) for v in torch.linspace(T // 3, T, B).round()]
+        mel = (torch.randn(B, 80, T, generator=g) - 2.0).to(dev)
+        target = torch.rand(B, 1, T * hop, generator=g) * 2 - 1
+        for b, n in enumerate(lens):
+            target[b, :, n * hop:] = 0.0
+        target = target.to(dev)
+        step = lambda: obj.training_step(mel, lens, target)["g_total"]
+        torch.cuda.empty_cache()
+        ms = timed(step, args.iters, args.warmup)
+        launches, syncs = count_launches_and_syncs(step)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        loss = step()
+        torch.cuda.synchronize()
+        row = {"step": {"step_ms": round(ms, 3), "launches": launches, "host_syncs": syncs,
+                        "peak_allocated_mb": round(torch.cuda.max_memory_allocated() / 2 ** 20, 1), "g_total": float(loss)}}
+        if args.leg == "b":
+            row["saturated"] = mpd.grad_saturated()
+        res["shapes"][f"B{B}_T{T}"] = row
+        print(json.dumps({f"B{B}_T{T}": row}), file=sys.stderr, flush=True)
+    print(json.dumps(res))
+
+
+def gan_step_h3_bench(args):
+    """--gan-step --mpd-precision h3: the whole step with the multi-period discriminator in "h3" (b) against "fp32" (a)"""
+    runs = _abba(args, ["--gan-step", "--mpd-precision", "h3"])
+    return {"metric": "hifigan_gan_step_ms", "config": "V1", "frames": 32, "iters": args.iters, "warmup": args.warmup,
+            "device": runs[0]["device"], "order": "a b b a",
+            "note": "HiFiGANTrainingStep, one fresh process per leg, ragged host lens, the batches of profiles/"
+                    "hifigan_gan_step.json; a: mpd_precision 'fp32', b: mpd_precision 'h3'",
+            "shapes": _merge_legs(runs, "step_ms", ("step",))}
+
+
 def gan_step_leg(args, dev):
     """one leg of --gan-step in this process: one JSON line"""
     from rad_mmm_amd.discriminators import MultiPeriodDiscriminator, MultiScaleDiscriminator
@@ -750,28 +928,63 @@ def main():
                                                        "stock torch")
     ap.add_argument("--msd", action="store_true", help="time the multi-scale discriminator's D step and G side against "
                                                        "stock torch")
-    ap.add_argument("--d-step-only", action="store_true", help="--msd: run the module's D step at 32 x 8192 a few times and "
+    ap.add_argument("--d-step-only", action="store_true", help="--msd, or --mpd --precision h3: run the module's D step at 32 x 8192 a few times and "
                                                                "exit (the workload of a kernel trace)")
     ap.add_argument("--gan-step", action="store_true", help="time the whole HiFi-GAN fine-tuning step: HiFiGANTrainingStep "
                                                             "against the README recipe with torch.optim.AdamW")
     ap.add_argument("--leg", choices=("a", "b"), default=None, help="--gan-step: run this leg in this process (the driver "
                                                                     "starts one process per leg)")
-    ap.add_argument("--precision", choices=("fp32", "f16"), default="fp32", help="the generator's inference mode")
+    ap.add_argument("--precision", choices=("fp32", "f16", "h3"), default="fp32",
+                    help="the generator's inference mode (fp32 / f16); with --mpd: h3 times the multi-period discriminator's "
+                         "precision 'h3' against 'fp32', legs a b b a in fresh processes, into profiles/mpd_h3.json")
+    ap.add_argument("--mpd-precision", choices=("fp32", "h3"), default="fp32",
+                    help="--gan-step: h3 times HiFiGANTrainingStep(mpd_precision='h3') against 'fp32', legs a b b a; the result "
+                         "is added to --out (default profiles/mpd_h3.json) under 'gan_step'")
     ap.add_argument("--config", choices=("V1", "V3"), default=None, help="only this config")
     ap.add_argument("--shape", default=None, help="only this BxT, e.g. 32x800")
     ap.add_argument("--out", default=None, help="--stft-loss / --mel-loss / --mpd / --msd: result file (default profiles/"
                                                 "stft_loss.json / mel_loss.json / mpd.json / msd.json)")
     args = ap.parse_args()
+    h3_mpd, h3_step = args.mpd and args.precision == "h3", args.gan_step and args.mpd_precision == "h3"
+    if args.precision == "h3" and not args.mpd:
+        ap.error("--precision h3 is the multi-period discriminator's mode: use it with --mpd")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "hifigan_gan_step.json" if args.gan_step else "msd.json" if args.msd else
-                                "mpd.json" if args.mpd else "mel_loss.json" if args.mel_loss else "stft_loss.json")
+        args.out = os.path.join(ROOT, "profiles", "mpd_h3.json" if h3_mpd or h3_step else "hifigan_gan_step.json" if args.gan_step
+                                else "msd.json" if args.msd else "mpd.json" if args.mpd else "mel_loss.json" if args.mel_loss
+                                else "stft_loss.json")
+    if h3_mpd and args.leg is None and not args.d_step_only:
+        return mpd_h3_bench(args)
+    if h3_step and args.leg is None:
+        part = gan_step_h3_bench(args)
+        res = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        res["gan_step"] = part
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+            fh.write("\n")
+        print(json.dumps(part))
+        return
     if args.gan_step and args.leg is None:
         return gan_step_bench(args)
     dev = torch.device("cuda:0")
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
+    if h3_step:
+        return gan_step_h3_leg(args, dev)
     if args.gan_step:
         return gan_step_leg(args, dev)
+    if h3_mpd and args.d_step_only:         # the workload of a kernel trace: the D step at 32 x 8192 in precision "h3"
+        from rad_mmm_amd.discriminators import MultiPeriodDiscriminator
+        torch.manual_seed(3)
+        mpd = MultiPeriodDiscriminator().to(dev).train()
+        mpd.precision = "h3"
+        y, y_hat, ratios = _mpd_batch(32, dev, torch.Generator().manual_seed(13))
+        for _ in range(args.warmup + args.iters):
+            mpd.zero_grad(set_to_none=True)
+            mpd.discriminator_loss(y, y_hat, ratios)[0].backward()
+        torch.cuda.synchronize()
+        return
+    if h3_mpd:
+        return mpd_leg(args, dev)
     if args.train:
         return train_bench(args, dev)
     if args.stft_loss:

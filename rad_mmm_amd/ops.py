@@ -164,6 +164,51 @@ def wgrad_slabs(GY: torch.Tensor, Mc: int, X: torch.Tensor, Nc: int, ldp: int, T
 # ---------------------------------------------------------------------------------------
 # affine flow step: invertible 1x1 channel mix + WN + affine coupling, one autograd node
 # ---------------------------------------------------------------------------------------
+def _flow_dims(meta, start_v, layer_params):
+    """(B, T, C, D, n_layers, act, scaling, partial, h, N, Wc, Kp, in_p, res_p) of a flow-step node: sizes and modes from
+    `meta`, the WN width from the start conv, the K-padded width of the WN input, the parameter list cut in two"""
+    B, T, C, D, nl = meta["B"], meta["T"], meta["C"], meta["D"], meta["n_layers"]
+    return (B, T, C, D, nl, meta["act"], meta["scaling"], meta["partial"], C // 2, B * T, start_v.shape[0],
+            round_up(D + C // 2, 32), layer_params[: 3 * nl], layer_params[3 * nl:])
+
+
+def _mix_fwd(z_in, W_eff, b_eff, T):
+    """invertible 1x1 (common.py:546 / :613-615): z1 = z_in @ W_eff^T + b_eff"""
+    N = z_in.shape[0]
+    z1 = _empty(N, ZLD, like=z_in)
+    rowgemm(A=z_in, lda=ZLD, B=W_eff, ldb=ZLD, b_layout=0, C=z1, ldc=ZLD, M=N, N=ZLD, K=ZLD, T=T, bias=b_eff)
+    return z1
+
+
+def _mix_bwd(gz1, z_in, W_eff, T, g_W_eff=None):
+    """gradients of the invertible 1x1 -> (g_zin, g_W_eff): g_W_eff = gz1^T z_in on the fp32-MFMA weight-gradient kernel unless
+    the caller made it already (FlowPlan.mix_split), g_zin = gz1 @ W_eff"""
+    N = gz1.shape[0]
+    if g_W_eff is None:
+        g_W_eff = wgrad_slabs(gz1, ZLD, z_in, ZLD, ZLD, T, None).sum(0).view(ZLD, ZLD)
+    g_zin = _empty(N, ZLD, like=z_in)
+    rowgemm(A=gz1, lda=ZLD, B=W_eff, ldb=ZLD, b_layout=1, C=g_zin, ldc=ZLD, M=N, N=ZLD, K=ZLD, T=T)
+    return g_zin, g_W_eff
+
+
+def _coupling_fwd(O, z1, N, h, scaling):
+    """affine coupling (common.py:1174-1185) -> (z_out, log_s)"""
+    z_out = _empty(N, ZLD, like=z1)
+    log_s = _empty(N, h, like=z1)
+    check(lib.radmmm_affine_coupling_fwd(ptr(O), ZLD, ptr(z1), ZLD, ptr(z_out), ptr(log_s), N, h, scaling,
+                                         stream()), "affine_coupling_fwd")
+    return z_out, log_s
+
+
+def _coupling_bwd(O, z1, g_zout, g_logs, N, h, scaling, zero_gO=False):
+    """-> (gO, gz1).  zero_gO: columns >= C of gO must read as zeros (a consumer contracts all ZLD of them)"""
+    gO = torch.zeros(N, ZLD, device=z1.device, dtype=torch.float32) if zero_gO else _empty(N, ZLD, like=z1)
+    gz1 = _empty(N, ZLD, like=z1)
+    check(lib.radmmm_affine_coupling_bwd(ptr(O), ZLD, ptr(z1), ZLD, ptr(g_zout), ptr(g_logs), ptr(gO), ptr(gz1),
+                                         N, h, scaling, stream()), "affine_coupling_bwd")
+    return gO, gz1
+
+
 class AffineFlowStepFn(torch.autograd.Function):
     """FlowStep.forward of the reference (decoders.py:72-80) for the affine/WN coupling.
 
@@ -176,20 +221,11 @@ class AffineFlowStepFn(torch.autograd.Function):
     @amp_fwd
     def forward(ctx, meta, z_in, cond, lens, W_eff, b_eff, start_v, start_g, start_b, end_w, end_b,
                 *layer_params):
-        B, T, C, D, nl = meta["B"], meta["T"], meta["C"], meta["D"], meta["n_layers"]
-        act, scaling, partial = meta["act"], meta["scaling"], meta["partial"]
-        h = C // 2
-        N = B * T
-        Wc = start_v.shape[0]                       # WN width (1024)
-        Kp = round_up(D + h, 32)
-        in_p = layer_params[: 3 * nl]
-        res_p = layer_params[3 * nl:]
+        B, T, C, D, nl, act, scaling, partial, h, N, Wc, Kp, in_p, res_p = _flow_dims(meta, start_v, layer_params)
         assert z_in.shape == (N, ZLD) and cond.shape == (N, D) and z_in.is_contiguous() and cond.is_contiguous()
 
-        # 1. invertible 1x1 (common.py:546 / :613-615): z1 = z_in @ W_eff^T + b_eff
-        z1 = _empty(N, ZLD, like=z_in)
-        rowgemm(A=z_in, lda=ZLD, B=W_eff, ldb=ZLD, b_layout=0, C=z1, ldc=ZLD, M=N, N=ZLD, K=ZLD, T=T,
-                bias=b_eff)
+        # 1. invertible 1x1
+        z1 = _mix_fwd(z_in, W_eff, b_eff, T)
         # 2. WN input cat((z0, context)) (common.py:819), K-padded
         X0 = _empty(N, Kp, like=z_in)
         check(lib.radmmm_wn_input_fwd(ptr(cond), D, ptr(z1), ZLD, ptr(X0), Kp, N, D, h, None, None, None, stream()), "wn_input_fwd")
@@ -225,11 +261,8 @@ class AffineFlowStepFn(torch.autograd.Function):
         O = _empty(N, ZLD, like=z_in)
         end_w2 = end_w.view(C, Wc)
         rowgemm(A=OUT, lda=Wc, B=end_w2, ldb=Wc, b_layout=0, C=O, ldc=ZLD, M=N, N=C, K=Wc, T=T, bias=end_b)
-        # 7. affine coupling (common.py:1174-1185)
-        z_out = _empty(N, ZLD, like=z_in)
-        log_s = _empty(N, h, like=z_in)
-        check(lib.radmmm_affine_coupling_fwd(ptr(O), ZLD, ptr(z1), ZLD, ptr(z_out), ptr(log_s), N, h, scaling,
-                                             stream()), "affine_coupling_fwd")
+        # 7. affine coupling
+        z_out, log_s = _coupling_fwd(O, z1, N, h, scaling)
         ctx.meta = meta
         ctx.nl = nl
         ctx.save_for_backward(z_in, z1, X0, OUT, O, lens, W_eff, start_v, start_g, end_w, Ws, inv_s,
@@ -239,9 +272,7 @@ class AffineFlowStepFn(torch.autograd.Function):
     @staticmethod
     @amp_bwd
     def backward(ctx, g_zout, g_logs):
-        meta, nl = ctx.meta, ctx.nl
-        B, T, C, D = meta["B"], meta["T"], meta["C"], meta["D"]
-        act, scaling, partial = meta["act"], meta["scaling"], meta["partial"]
+        nl = ctx.nl
         sv = ctx.saved_tensors
         z_in, z1, X0, OUT, O, lens, W_eff, start_v, start_g, end_w, Ws, inv_s = sv[:12]
         p = 12
@@ -251,21 +282,13 @@ class AffineFlowStepFn(torch.autograd.Function):
         inv_i = sv[p: p + nl]; p += nl
         Wr = sv[p: p + nl]; p += nl
         inv_r = sv[p: p + nl]; p += nl
-        layer_params = sv[p:]
-        in_p, res_p = layer_params[: 3 * nl], layer_params[3 * nl:]
-        h = C // 2
-        N = B * T
-        Wc = start_v.shape[0]
-        Kp = X0.shape[1]
+        B, T, C, D, nl, act, scaling, partial, h, N, Wc, Kp, in_p, res_p = _flow_dims(ctx.meta, start_v, sv[p:])
         g_zout = g_zout.contiguous()
         if g_logs is not None:
             g_logs = g_logs.contiguous()
 
         # coupling
-        gO = _empty(N, ZLD, like=z_in)
-        gz1 = _empty(N, ZLD, like=z_in)
-        check(lib.radmmm_affine_coupling_bwd(ptr(O), ZLD, ptr(z1), ZLD, ptr(g_zout), ptr(g_logs), ptr(gO), ptr(gz1),
-                                             N, h, scaling, stream()), "affine_coupling_bwd")
+        gO, gz1 = _coupling_bwd(O, z1, g_zout, g_logs, N, h, scaling)
         # end conv
         g_end_b = colsum(gO, C)
         g_end_w = wgrad_slabs(gO, C, OUT, Wc, Wc, T, None).sum(0).view(C, Wc, 1)
@@ -308,9 +331,7 @@ class AffineFlowStepFn(torch.autograd.Function):
         check(lib.radmmm_wn_input_bwd(ptr(gX0), Kp, ptr(g_cond), D, 0, ptr(gz1), ZLD, N, D, h, stream()), "wn_input_bwd")
         # invertible 1x1
         g_b_eff = colsum(gz1, ZLD) if ctx.needs_input_grad[5] else None   # LUS conv: constant zero bias
-        g_W_eff = wgrad_slabs(gz1, ZLD, z_in, ZLD, ZLD, T, None).sum(0).view(ZLD, ZLD)
-        g_zin = _empty(N, ZLD, like=z_in)
-        rowgemm(A=gz1, lda=ZLD, B=W_eff, ldb=ZLD, b_layout=1, C=g_zin, ldc=ZLD, M=N, N=ZLD, K=ZLD, T=T)
+        g_zin, g_W_eff = _mix_bwd(gz1, z_in, W_eff, T)
         return (None, g_zin, g_cond, None, g_W_eff, g_b_eff, g_start_v, g_start_g, g_start_b, g_end_w, g_end_b,
                 *g_in, *g_res)
 
@@ -1405,25 +1426,41 @@ def ctx_acc_add(acc: dict, slot: int, alloc, write):
     return buf
 
 
-FlowPlan = collections.namedtuple("FlowPlan", "use_rm pair_only wgrad_products layout")
-FlowPlan.__doc__ = """Path decisions of one AffineFlowStepH3Fn node: made once, in forward, by shape and precision; backward reads them.
-use_rm: the weight gradients contract ROW-major split pairs (saved groups X0pair, Hh / Hl, OUTpair) and the bias gradients
-of the in_layer / start convs leave the data-gradient GEMMs' epilogues.  pair_only: these pairs are (hi, 8-bit cross array)
-for radmmm_wgrad_rm8 and there is no fp32 copy of X0, of the hidden states or of the pre-activation gradients.
-wgrad_products (pair_only): 1 = the WN convs' weight gradients (start, in_layers, res_skip layers, end) contract the hi planes
-alone (radmmm_wgrad_rmh), 2 = hi planes and FP8 cross terms (radmmm_wgrad_rm8); wgrad_products_env().
-layout: what save_groups returned."""
+FlowPlan = collections.namedtuple("FlowPlan", "use_rm pair_only wgrad_products res_src out_f32 pair_res multi grouped "
+                                              "wgrad mix_split")
+FlowPlan.__doc__ = """Path decisions of one AffineFlowStepH3Fn node (DESIGN 4.15.1): made once, on the host, by flow_plan(); forward
+follows them and keeps them on ctx, backward reads nothing else.
+use_rm: the weight gradients contract the ROW-major split pairs the GEMMs leave behind (saved groups X0pair, Hh / Hl, OUTpair)
+and the in_layer / start bias gradients leave the data-gradient GEMMs' epilogues.  pair_only: the pairs are (hi, 8-bit cross
+array) and there is no fp32 copy of X0, of the hidden states or of the pre-activation gradients.  wgrad_products (pair_only):
+the WN convs' weight gradients contract 1 = the hi planes alone, 2 = hi planes and FP8 cross terms; otherwise the product scheme.
+res_src: the last res/skip layer's epilogue forms the skip sum; out_f32: an fp32 OUT exists.  pair_res: res_skip[j] on a side
+stream.  multi: gQ of all res/skip layers in one pass over gOUT; grouped: their weight gradients in one launch.  wgrad: the
+weight-gradient strategy, "pairs" or "transposed".  mix_split: the channel mix's weight gradient takes split pairs too."""
 
 
 def wgrad_products_env() -> int:
     """RADMMM_WGRAD_PRODUCTS: products of the WN convs' weight gradients under the FP8-cross scheme, 1 (default) or 2.  A
     weight gradient is a leaf of the step -- its rounding feeds no other result -- and over the frames of a batch the
-    roundings of the fp16 hi planes average out (profiles/wgrad_one_pass_emulation.txt).  Read where a flow
-    step's plan is made (forward); backward follows the plan."""
+    roundings of the fp16 hi planes average out (profiles/wgrad_one_pass_emulation.txt)."""
     v = os.environ.get("RADMMM_WGRAD_PRODUCTS", "1")
     if v not in ("1", "2"):
         raise ValueError(f"RADMMM_WGRAD_PRODUCTS={v!r}: 1 or 2")
     return int(v)
+
+
+def flow_plan(nprod: int, B: int, T: int, n_layers: int, act: int, needs_grad: bool, is_cuda: bool = True) -> FlowPlan:
+    """The FlowPlan of a flow step of this shape under product scheme `nprod`: host only, every switch is read here, once
+    (RADMMM_RES_SRC, RADMMM_DACT_MULTI, RADMMM_WGRAD_GROUP, RADMMM_RES_STREAM: A/B switches under RADMMM_DEBUG)."""
+    use_rm = bool(nprod in (2, 3) and T >= 32 and B <= 1024 and needs_grad)
+    pair_only = use_rm and nprod == 2
+    wgrad_products = wgrad_products_env() if pair_only else nprod
+    res_src = bool(2 <= n_layers <= 4 and debug_env("RADMMM_RES_SRC", "1") != "0")
+    pair_res = bool(res_src and nprod == 2 and n_layers >= 2 and is_cuda and debug_env("RADMMM_RES_STREAM", "0") == "1")
+    multi = bool(use_rm and 2 <= n_layers <= 4 and act and debug_env("RADMMM_DACT_MULTI", "1") != "0")
+    grouped = bool(multi and pair_only and wgrad_products == 1 and debug_env("RADMMM_WGRAD_GROUP", "1") != "0")
+    return FlowPlan(use_rm, pair_only, wgrad_products, res_src, not (res_src and use_rm), pair_res, multi, grouped,
+                    "pairs" if use_rm else "transposed", bool(use_rm and T % 16 != 0))
 
 
 def save_groups(ctx, **groups):
@@ -1451,178 +1488,114 @@ def load_groups(ctx, layout):
     return types.SimpleNamespace(**out)
 
 
+def _side_launch(main, side, fn):
+    """FlowPlan.pair_res: fn() on stream `side`, behind everything queued on `main` so far -> the event that marks its end (the
+    caller keeps every tensor fn touches alive until the main stream has waited for it)"""
+    ev, done = torch.cuda.Event(), torch.cuda.Event()
+    ev.record(main)
+    with torch.cuda.stream(side):
+        side.wait_event(ev)
+        fn()
+        done.record(side)
+    return done
+
+
 class AffineFlowStepH3Fn(torch.autograd.Function):
     """Same contract as AffineFlowStepFn; the WN convs run on radmmm_rowgemm_h3 (split operands on the f16 / fp8 matrix
     cores, fp32 accumulate).  meta["nprod"]: 3 = split-f16 (three f16 products), 2 = f16 product + FP8 cross terms
     (second array of every row-major split pair is then the 8-bit cross array), 1 = fp16 throughput mode.
-    The 160-wide invertible 1x1, all weight gradients (contraction over frames, always split-f16 on transposed copies
-    made from the fp32 tensors) and every elementwise / reduction kernel stay fp32."""
+    The 160-wide invertible 1x1 and every elementwise / reduction kernel stay fp32.  flow_plan() decides the paths."""
 
     @staticmethod
     @amp_fwd
     def forward(ctx, meta, z_in, cond, lens, W_eff, b_eff, start_v, start_g, start_b, end_w, end_b,
                 *layer_params):
-        B, T, C, D, nl = meta["B"], meta["T"], meta["C"], meta["D"], meta["n_layers"]
-        act, scaling, partial = meta["act"], meta["scaling"], meta["partial"]
+        B, T, C, D, nl, act, scaling, partial, h, N, Wc, Kp, in_p, res_p = _flow_dims(meta, start_v, layer_params)
         NPR = meta.get("nprod", 3)               # product scheme, see the class docstring
-        box = meta["scale_box"]
-        flag = sat_flag_of(box)
-        fa = fmt_a(NPR)
-        h = C // 2
-        N = B * T
-        Wc = start_v.shape[0]
-        Kp = round_up(D + h, 32)
-        in_p, res_p = layer_params[: 3 * nl], layer_params[3 * nl:]
+        plan = flow_plan(NPR, B, T, nl, act, any(ctx.needs_input_grad), z_in.is_cuda)
         assert Wc % 32 == 0 and z_in.shape == (N, ZLD) and cond.shape == (N, D)
-        inv_ws = 1.0 / W_SCALE
         # keyword sets shared by the launches of this pass: operand exponents in, output format out
-        gin = dict(nprod=NPR, a8_exp=X8_ACT_EXP, b8_exp=X8_W_EXP, acc_scale=inv_ws, T=T, sat_flag=flag)
-        gout = dict(split_fmt=fa, ch_x8_exp=X8_ACT_EXP, c2h_x8_exp=X8_ACT_EXP)
-
-        # Weight gradients contract the ROW-major split pairs of the activations / gradients directly: the pairs of X0, of
-        # every hidden state and of OUT are kept for backward.  Three products: (hi, fp16 lo) pairs on radmmm_wgrad_rm;
-        # FP8-cross scheme: (hi, 8-bit cross array) pairs on radmmm_wgrad_rm8, the GEMMs' own operands.
-        use_rm = bool(NPR in (2, 3) and T >= 32 and B <= 1024 and any(ctx.needs_input_grad))
-        # Round 5: with the FP8-cross weight gradient NOTHING reads an fp32 copy of the WN input or of the hidden states
-        # any more -- the GEMMs and the weight gradients take the split pairs, and the data gradient's softplus' factor is
-        # rebuilt from the pair (radmmm_rowgemm_desc.dact_h / dact_x: hi + lo8 * 2^-(11+e), 2^-15 relative) -- so the
-        # producers write the pair only (C = NULL): 8 instead of 16 bytes per hidden-state element leave the forward
-        # epilogues, 311 MB per flow step at the benchmark size.
-        pair_only = use_rm and NPR == 2
-        hid = (lambda: None) if pair_only else (lambda: _empty(N, Wc, like=z_in))
-        z1 = _empty(N, ZLD, like=z_in)
-        rowgemm(A=z_in, lda=ZLD, B=W_eff, ldb=ZLD, b_layout=0, C=z1, ldc=ZLD, M=N, N=ZLD, K=ZLD, T=T, bias=b_eff)
-        X0 = None if pair_only else _empty(N, Kp, like=z_in)
+        gin = dict(nprod=NPR, a8_exp=X8_ACT_EXP, b8_exp=X8_W_EXP, acc_scale=1.0 / W_SCALE, T=T, sat_flag=sat_flag_of(meta["scale_box"]))
+        gout = dict(split_fmt=fmt_a(NPR), ch_x8_exp=X8_ACT_EXP, c2h_x8_exp=X8_ACT_EXP)
+        hid = (lambda: None) if plan.pair_only else (lambda: _empty(N, Wc, like=z_in))
+        z1 = _mix_fwd(z_in, W_eff, b_eff, T)
+        X0 = None if plan.pair_only else _empty(N, Kp, like=z_in)
         X0h, X0l = _halves(N, Kp, like=z_in)
         check(lib.radmmm_wn_input_fwd(ptr(cond), D, ptr(z1), ZLD, ptr(X0), Kp, N, D, h, ptr(X0h), ptr(X0l),
-                                      split_opts(fa, X8_ACT_EXP), stream()), "wn_input_fwd")
-        perm = (h, D, 0)
-        # all conv weights of the flow step in one launch (round 4)
-        specs = [(start_v, start_g, Kp, perm)]
-        for j in range(nl):
-            specs.append((in_p[3 * j], in_p[3 * j + 1], Wc, None))
-            specs.append((res_p[3 * j], res_p[3 * j + 1], Wc, None))
-        specs.append((end_w, None, Wc, None))
-        sw = split_weights(specs, NPR)
-        Wsh, Wsl, inv_s = sw[0]
-        Wih, Wil, inv_i = [sw[1 + 2 * j][0] for j in range(nl)], [sw[1 + 2 * j][1] for j in range(nl)], [sw[1 + 2 * j][2] for j in range(nl)]
-        Wrh, Wrl, inv_r = [sw[2 + 2 * j][0] for j in range(nl)], [sw[2 + 2 * j][1] for j in range(nl)], [sw[2 + 2 * j][2] for j in range(nl)]
-        Weh, Wel, _ = sw[-1]
-
+                                      split_opts(fmt_a(NPR), X8_ACT_EXP), stream()), "wn_input_fwd")
+        # all conv weights of the flow step in one launch: start, (in_layer j, res_skip j) per layer, end
+        sw = split_weights([(start_v, start_g, Kp, (h, D, 0))]
+                           + [(p[3 * j], p[3 * j + 1], Wc, None) for j in range(nl) for p in (in_p, res_p)]
+                           + [(end_w, None, Wc, None)], NPR)
+        (Wsh, Wsl, inv_s), (Weh, Wel, _) = sw[0], sw[-1]
+        Wih, Wil, inv_i = (list(t) for t in zip(*sw[1:-1:2]))
+        Wrh, Wrl, inv_r = (list(t) for t in zip(*sw[2:-1:2]))
         H = [hid()]
         Hh, Hl = _halves(N, Wc, like=z_in)
         rowgemm_h3(Ah=X0h, Al=X0l, lda_h=Kp, Bh=Wsh, Bl=Wsl, ldb_h=Kp, C=H[0], ldc=Wc, M=N, N=Wc, K=Kp,
                    bias=start_b, Ch=Hh, Cl=Hl, ldch=Wc, ch_scale=1.0, **gin, **gout)
         pairs = [(Hh, Hl)]
-        res_src = bool(2 <= nl <= 4 and debug_env("RADMMM_RES_SRC", "1") != "0")
-        # (no fp32 OUT at all when the backward takes OUT's split pair: the last layer's C2 stores are dropped)
-        OUT = None if (res_src and use_rm) else _empty(N, Wc, like=z_in)
+        OUT = _empty(N, Wc, like=z_in) if plan.out_f32 else None
         OUTh, OUTl = _halves(N, Wc, like=z_in)
-        R = []
-        # Round 6 (VERDICT r5 item 1a, measured before anything was built: tools/pair_overlap_probe.py,
-        # profiles/r06_pair_overlap.txt): res_skip[j] and in_layer[j+1] both read only h_{j+1} (common.py:829-832), so the 1x1
-        # launches of layers 0 .. nl-2 can run on a side stream BESIDE the next 5-tap launch -- what a grouped persistent grid
-        # would do at best, with the hardware's own workgroup dispatcher.  One flow step's forward chain stand-alone: 1241 ->
-        # 1190 us.  In the training step: 40.18 / 40.24 / 40.15 -> 40.13 / 40.16 / 40.16 ms, i.e. NOTHING (the 24 idle CUs and the
-        # exposed 1x1 epilogues are not where the step's time is), so the pairing is OFF and this stays as the A/B switch
-        # RADMMM_RES_STREAM=1 (RADMMM_DEBUG).  Same launches, same values; every tensor the side stream touches is kept alive
-        # by this function until the main stream has joined it in front of the last layer's launch.
-        pair_res = bool(res_src and NPR == 2 and nl >= 2 and z_in.is_cuda and debug_env("RADMMM_RES_STREAM", "0") == "1")
-        main_st = torch.cuda.current_stream(z_in.device) if pair_res else None
-        side_st = side_stream(z_in.device) if pair_res else None
-        side_done: List = []
+        R, side_done = [], []
+        main_st, side_st = (torch.cuda.current_stream(z_in.device), side_stream(z_in.device)) if plan.pair_res else (None, None)
         for j in range(nl):
-            d = 2 ** j
-            kt = in_p[3 * j].shape[2]
+            d, kt, last = 2 ** j, in_p[3 * j].shape[2], j == nl - 1
             Hn = hid()
-            Hnh, Hnl = _halves(N, Wc, like=z_in)
-            rowgemm_h3(Ah=Hh, Al=Hl, lda_h=Wc, Bh=Wih[j], Bl=Wil[j], ldb_h=Wc, b_tap_stride_h=Wih[j].stride(0),
+            Hh, Hl = _halves(N, Wc, like=z_in)
+            rowgemm_h3(Ah=pairs[j][0], Al=pairs[j][1], lda_h=Wc, Bh=Wih[j], Bl=Wil[j], ldb_h=Wc, b_tap_stride_h=Wih[j].stride(0),
                        C=Hn, ldc=Wc, M=N, N=Wc, K=Wc, taps=kt, dil=d, sign=1, lens=lens,
                        a_mask_mode=1 if partial else 0, bias=in_p[3 * j + 2], pconv=1 if partial else 0, ratio_taps=kt,
-                       ratio_dil=d, postmask=1, act=act, Ch=Hnh, Cl=Hnl, ldch=Wc, ch_scale=1.0, **gin, **gout)
+                       ratio_dil=d, postmask=1, act=act, Ch=Hh, Cl=Hl, ldch=Wc, ch_scale=1.0, **gin, **gout)
             H.append(Hn)
-            Hh, Hl = Hnh, Hnl
-            pairs.append((Hnh, Hnl))
+            pairs.append((Hh, Hl))
             Rj = _empty(N, Wc, like=z_in)
-            last = j == nl - 1
-            if pair_res and not last:
-                # res_skip[j] on the side stream, behind in_layer[j] (it reads h_{j+1} and its own weights only); the main
-                # stream goes on to in_layer[j+1] and meets the side stream again in front of the last layer's launch
-                ev = torch.cuda.Event()
-                ev.record(main_st)
-                with torch.cuda.stream(side_st):
-                    side_st.wait_event(ev)
-                    rowgemm_h3(Ah=Hh, Al=Hl, lda_h=Wc, Bh=Wrh[j], Bl=Wrl[j], ldb_h=Wc, C=Rj, ldc=Wc, M=N, N=Wc, K=Wc,
-                               bias=res_p[3 * j + 2], act=act, **gin, **gout)
-                    done = torch.cuda.Event()
-                    done.record(side_st)
-                side_done.append(done)
-                R.append(Rj)
-                continue
-            if pair_res:                                # (last layer: its epilogue sums the earlier layers' outputs)
-                for done in side_done:
-                    main_st.wait_event(done)
-            if res_src:
-                # Round 5: the skip sum is formed ONCE, by the last layer's epilogue, from the earlier layers' outputs
-                # (radmmm_rowgemm_desc.c2_src: ((R0 + R1) + R2) + R3, the running sum's association and bits) -- the earlier
-                # layers write their own output only, and with the end conv's weight gradient on OUT's split pair nobody reads
-                # an fp32 OUT: 208 MB less per flow step than four read-modify-writes of it.
-                if last:
-                    rowgemm_h3(Ah=Hh, Al=Hl, lda_h=Wc, Bh=Wrh[j], Bl=Wrl[j], ldb_h=Wc, C=Rj, ldc=Wc, M=N, N=Wc, K=Wc,
-                               bias=res_p[3 * j + 2], act=act, C2=OUT, ldc2=Wc, c2_src=R, C2h=OUTh, C2l=OUTl, ldc2h=Wc,
-                               c2h_scale=1.0, **gin, **gout)
-                else:
-                    rowgemm_h3(Ah=Hh, Al=Hl, lda_h=Wc, Bh=Wrh[j], Bl=Wrl[j], ldb_h=Wc, C=Rj, ldc=Wc, M=N, N=Wc, K=Wc,
-                               bias=res_p[3 * j + 2], act=act, **gin, **gout)
+            kw = dict(Ah=Hh, Al=Hl, lda_h=Wc, Bh=Wrh[j], Bl=Wrl[j], ldb_h=Wc, C=Rj, ldc=Wc, M=N, N=Wc, K=Wc,
+                      bias=res_p[3 * j + 2], act=act)
+            if not plan.res_src:                 # every layer read-modify-writes the fp32 skip sum
+                kw.update(C2=OUT, ldc2=Wc, c2_accum=1 if j > 0 else 0, C2h=OUTh if last else None, C2l=OUTl if last else None,
+                          ldc2h=Wc, c2h_scale=1.0)
+            elif last:
+                # the skip sum is formed ONCE, here, from the earlier layers' outputs (c2_src: the running sum's association and bits)
+                kw.update(C2=OUT, ldc2=Wc, c2_src=R, C2h=OUTh, C2l=OUTl, ldc2h=Wc, c2h_scale=1.0)
+            kw.update(**gin, **gout)
+            if plan.pair_res and not last:       # beside in_layer[j+1]: it reads h_{j+1} and its own weights only
+                side_done.append(_side_launch(main_st, side_st, lambda: rowgemm_h3(**kw)))
             else:
-                rowgemm_h3(Ah=Hh, Al=Hl, lda_h=Wc, Bh=Wrh[j], Bl=Wrl[j], ldb_h=Wc, C=Rj, ldc=Wc, M=N, N=Wc,
-                           K=Wc, bias=res_p[3 * j + 2], act=act, C2=OUT, ldc2=Wc, c2_accum=1 if j > 0 else 0,
-                           C2h=OUTh if last else None, C2l=OUTl if last else None, ldc2h=Wc, c2h_scale=1.0, **gin, **gout)
+                for done in side_done:           # (pair_res, last layer: its epilogue sums the earlier layers' outputs)
+                    main_st.wait_event(done)
+                rowgemm_h3(**kw)
             R.append(Rj)
         O = _empty(N, ZLD, like=z_in)
-        rowgemm_h3(Ah=OUTh, Al=OUTl, lda_h=Wc, Bh=Weh, Bl=Wel, ldb_h=Wc, C=O, ldc=ZLD, M=N, N=C, K=Wc,
-                   bias=end_b, **gin)
-        z_out = _empty(N, ZLD, like=z_in)
-        log_s = _empty(N, h, like=z_in)
-        check(lib.radmmm_affine_coupling_fwd(ptr(O), ZLD, ptr(z1), ZLD, ptr(z_out), ptr(log_s), N, h, scaling,
-                                             stream()), "affine_coupling_fwd")
-        ctx.meta = meta
-        ctx.nl = nl
-        # the end conv's weight gradient contracts gO with OUT: with OUT's split pair kept (52 MB per flow step) it runs on
-        # the same row-major kernels as every other weight gradient of the step instead of the fp32-MFMA one (50 -> ~25 us)
-        layout = save_groups(
+        rowgemm_h3(Ah=OUTh, Al=OUTl, lda_h=Wc, Bh=Weh, Bl=Wel, ldb_h=Wc, C=O, ldc=ZLD, M=N, N=C, K=Wc, bias=end_b, **gin)
+        z_out, log_s = _coupling_fwd(O, z1, N, h, scaling)
+        ctx.meta, ctx.nl, ctx.plan = meta, nl, plan
+        use_rm, pair_only = plan.use_rm, plan.pair_only
+        ctx.layout = save_groups(
             ctx, z_in=z_in, z1=z1, O=O, lens=lens, W_eff=W_eff, start_v=start_v, start_g=start_g, end_w=end_w, Wsh=Wsh, Wsl=Wsl,
             inv_s=inv_s, Weh=Weh, Wel=Wel, start_b=start_b, end_b=end_b, R=R, Wih=Wih, Wil=Wil, inv_i=inv_i, Wrh=Wrh, Wrl=Wrl,
             inv_r=inv_r, layer_params=layer_params,
             X0=None if pair_only else X0, H=None if pair_only else H, OUT=None if use_rm else OUT,
             X0pair=(X0h, X0l) if use_rm else None, Hh=[pr[0] for pr in pairs] if use_rm else None,
             Hl=[pr[1] for pr in pairs] if use_rm else None, OUTpair=(OUTh, OUTl) if use_rm else None)
-        ctx.plan = FlowPlan(use_rm, pair_only, wgrad_products_env() if pair_only else NPR, layout)
         return z_out, log_s
 
     @staticmethod
     @amp_bwd
     @traced_bwd
     def backward(ctx, g_zout, g_logs):
-        meta, nl = ctx.meta, ctx.nl
+        meta, plan = ctx.meta, ctx.plan
         NPR = meta.get("nprod", 3)
         WPR = 3 if NPR == 2 else NPR             # weight gradients: split-f16 (or the throughput mode's single product)
-        B, T, C, D = meta["B"], meta["T"], meta["C"], meta["D"]
-        act, scaling, partial = meta["act"], meta["scaling"], meta["partial"]
-        plan = ctx.plan
-        use_rm, pair_only = plan.use_rm, plan.pair_only
-        sv = load_groups(ctx, plan.layout)
+        use_rm, pair_only, multi, grouped = plan.use_rm, plan.pair_only, plan.multi, plan.grouped
+        sv = load_groups(ctx, ctx.layout)
         z_in, z1, O, lens, W_eff, start_v, start_g, end_w = sv.z_in, sv.z1, sv.O, sv.lens, sv.W_eff, sv.start_v, sv.start_g, sv.end_w
         Wsh, Wsl, inv_s, Weh, Wel, start_b, end_b = sv.Wsh, sv.Wsl, sv.inv_s, sv.Weh, sv.Wel, sv.start_b, sv.end_b
         R, Wih, Wil, inv_i, Wrh, Wrl, inv_r, layer_params = sv.R, sv.Wih, sv.Wil, sv.inv_i, sv.Wrh, sv.Wrl, sv.inv_r, sv.layer_params
         X0, H, OUT = sv.X0, sv.H, sv.OUT                   # fp32 copies: the paths without the split pairs below
         X0pair, OUTpair = sv.X0pair, sv.OUTpair           # use_rm: row-major split pairs of X0, OUT and of the hidden states
         Hpair = list(zip(sv.Hh, sv.Hl)) if use_rm else None
-        in_p, res_p = layer_params[: 3 * nl], layer_params[3 * nl:]
-        h = C // 2
-        N = B * T
-        Wc = start_v.shape[0]
-        Kp = Wsh.shape[2]
+        B, T, C, D, nl, act, scaling, partial, h, N, Wc, Kp, in_p, res_p = _flow_dims(meta, start_v, layer_params)
         g_zout = g_zout.contiguous()
         if g_logs is not None:
             g_logs = g_logs.contiguous()
@@ -1643,10 +1616,7 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
         gin = dict(nprod=NPR, a8_exp=GE, b8_exp=X8_W_EXP, acc_scale=inv_acc, T=T, sat_flag=flag)
         gout = dict(split_fmt=fa, ch_x8_exp=GE)
 
-        gO = torch.zeros(N, ZLD, device=z_in.device, dtype=torch.float32)      # columns >= C stay zero (K = ZLD)
-        gz1 = _empty(N, ZLD, like=z_in)
-        check(lib.radmmm_affine_coupling_bwd(ptr(O), ZLD, ptr(z1), ZLD, ptr(g_zout), ptr(g_logs), ptr(gO), ptr(gz1),
-                                             N, h, scaling, stream()), "affine_coupling_bwd")
+        gO, gz1 = _coupling_bwd(O, z1, g_zout, g_logs, N, h, scaling, zero_gO=True)      # columns >= C stay zero (K = ZLD)
         g_end_b = colsum(gO, C, out=grad_out(end_b))
         g_end_w = grad_out(end_w)
         gOh, gOl = split_f16(gO, ZLD, SG, ZLD, NPR, GE, flag)
@@ -1719,8 +1689,7 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
         x_prev = None
         # Round 5: gQ_j = gOUT * act'(R_j) of ALL res/skip layers in one pass over gOUT (radmmm_dact_mul_rows_multi; gOUT is the
         # same 52 MB for the four layers).  Their destinations are the second halves of the layer pairs, which are therefore
-        # allocated up front.  RADMMM_DACT_MULTI=0 (RADMMM_DEBUG): one launch per layer as before.
-        multi = bool(use_rm and 2 <= nl <= 4 and act and debug_env("RADMMM_DACT_MULTI", "1") != "0")
+        # allocated up front.  plan.multi; RADMMM_DACT_MULTI=0 (RADMMM_DEBUG): one launch per layer as before.
         pre_pairs, gq_pre = {}, None
         if multi:
             for j in range(nl - 1, 0, -1):
@@ -1733,8 +1702,7 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
         # All nl res/skip weight gradients dW_res[j] = gQ_j^T H_{j+1} are ready here (the gQ_j just written, the H_{j+1} saved
         # by forward) and nothing downstream reads them: ONE grouped launch (radmmm_wgrad_rmh_group) whose split factor is
         # picked for the tiles of all of them -- a quarter of the slabs of nl launches -- and ONE weight-norm backward
-        # (DESIGN 4.8).  One-product weight gradients only; RADMMM_WGRAD_GROUP=0 (RADMMM_DEBUG): per-layer launches as before.
-        grouped = bool(multi and pair_only and plan.wgrad_products == 1 and debug_env("RADMMM_WGRAD_GROUP", "1") != "0")
+        # (DESIGN 4.8).  plan.grouped: one-product weight gradients only; RADMMM_WGRAD_GROUP=0 (RADMMM_DEBUG): per-layer launches.
         if grouped:
             res_slabs = wgrad_rmh_group_slabs([(gq_dst[j][0], Hpair[j + 1][0], Wc, Wc) for j in range(nl)], B, T, 1, 1, 1.0 / SG)
             res_g = weightnorm_bwd_multi([res_p[3 * j] for j in range(nl)], [res_p[3 * j + 1] for j in range(nl)],
@@ -1801,9 +1769,10 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
                 x_t = transpose_split_act(H[j], Wc, B, T, lens, 1 if partial else 0, 1.0, "x", need_odd=(d % 2 == 1))
                 slabs = wgrad_h3_slabs(gy_t, x_t, Wc, Wc, Wc, kt, d, 1.0 / SG, WPR)
                 # reusable by layer j-1's res_skip gradient (even dilation: no advanced copy in the way).  The copy was made
-                # with the length mask (partial padding), the res_skip gradient wants H[j] unmasked: the two are the same
-                # tensor because H[j], j >= 1, is exactly zero at frames >= len (in_layer j-1's epilogue multiplies by the
-                # mask, common.py:186-190) -- independent of the upstream gradient, so any loss is handled exactly
+                # with the length mask (partial padding), the res_skip gradient wants H[j] unmasked.  At frames >= len H[j],
+                # j >= 1, is act(0) (in_layer j-1 masks BEFORE the activation: 0 under relu, ln 2 under softplus), so the two
+                # agree only where gQ is zero there: under every length-masked loss, not under an upstream gradient that
+                # reaches the padded frames (tests/test_flow_step_paths_gpu.py)
                 x_prev = x_t if (d % 2 == 0 and j >= 1) else None
             else:
                 x_prev = None
@@ -1861,7 +1830,8 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
             g_cond = _empty(N, D, like=z_in)
             check(lib.radmmm_wn_input_bwd(ptr(gX0), Kp, ptr(g_cond), D, 0, ptr(gz1), ZLD, N, D, h, stream()), "wn_input_bwd")
         g_b_eff = colsum(gz1, ZLD) if ctx.needs_input_grad[5] else None   # LUS conv: constant zero bias
-        if use_rm and T % 16 != 0:
+        g_W_eff = None
+        if plan.mix_split:
             # the channel mix's weight gradient (gz1^T z_in, 160 x 160 over all frames): the fp32-MFMA fast path needs K steps
             # of 16 frames inside one utterance (T % 16 == 0); where it does not apply (configs[4]: T' = 1000, 155 us on the
             # generic kernel) two 8-bit split passes + a one-tile launch of the row-major split kernel replace it.  At
@@ -1869,10 +1839,7 @@ class AffineFlowStepH3Fn(torch.autograd.Function):
             gzh, gzl = split_f16(gz1, ZLD, SG, ZLD, NPR, GE, flag)
             zh, zl = split_f16(z_in, ZLD, 1.0, ZLD, NPR, X8_ACT_EXP)
             g_W_eff = wg_rm((gzh, gzl), (zh, zl), ZLD, ZLD, 1, 1, leaf=False).sum(0).view(ZLD, ZLD)      # (not a WN conv: as it was)
-        else:
-            g_W_eff = wgrad_slabs(gz1, ZLD, z_in, ZLD, ZLD, T, None).sum(0).view(ZLD, ZLD)
-        g_zin = _empty(N, ZLD, like=z_in)
-        rowgemm(A=gz1, lda=ZLD, B=W_eff, ldb=ZLD, b_layout=1, C=g_zin, ldc=ZLD, M=N, N=ZLD, K=ZLD, T=T)
+        g_zin, g_W_eff = _mix_bwd(gz1, z_in, W_eff, T, g_W_eff)
         return (None, g_zin, g_cond, None, g_W_eff, g_b_eff, g_start_v, g_start_g, g_start_b, g_end_w, g_end_b,
                 *g_in, *g_res)
 
